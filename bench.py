@@ -8,6 +8,11 @@ dedupe -> L4 MinHash/LSH -> L1 dictionary DEFLATE) over this rank's shard of the
 resident in HBM when the timed region starts.  Workload = BASELINE.json configs[2]/[3]: the full
 pipeline over 10 GB of Wikipedia text (wiki-synth(seed=42) unless $HMSE_CORPUS_DIR has the real
 sample), total size fixed as N grows ("strong" scaling, the way BASELINE.json's metric is worded).
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds the side measurements:
+the CPU baseline, per-kernel durations and roofline, the read-path check, the manifest pack and BASELINE
+configs[1] / configs[4].  `--dump-outputs DIR` writes what the last timed step returned (rank 0) as
+DIR/<name>.npy, so that two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -49,13 +54,19 @@ def parse():
     ap.add_argument("--corpus", default="wikipedia")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong")
     ap.add_argument("--layers", default="full", help="ablation preset (hmse_amd.config.ABLATIONS)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: CPU baseline, per-kernel roofline, read-path check, manifest pack, configs[1] / configs[4]")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the arrays the last timed step returned (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--global-l4", action="store_true",
                     help="N > 1: base selection over all shards (signature all-gather + cross-GPU base fetch) instead of shard-local; "
                          "the stored bytes are then those of the 1-GPU run")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the side measurements of BASELINE configs[1] / configs[4] (one rank)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the side measurements of BASELINE configs[1] / configs[4] (one rank)")
     ap.add_argument("--cpu-sample-mib", type=int, default=0, help="CPU baseline sample (0 = 4 MiB x 2 x cores, <= 256 MiB)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 # ------------------------------------------------------------------------------------------ CPU leg
@@ -240,6 +251,88 @@ def other_configs(data, host, dev, cfg_full) -> dict:
     return out
 
 
+DUMP_ARRAYS = ("cuts", "digests", "first_occ", "refcount", "uniq_ids", "sig", "band_keys", "base", "stream_off", "kind", "streams",
+               "base_global")
+DUMP_VALUES = 1 << 19     # values kept per array: at most 4 MiB per file, 42 MiB for all of them
+DUMP_SEED = 42
+
+
+def dump_outputs(res, out_dir: str) -> None:
+    """The arrays of the ShardResult the last timed step returned, as out_dir/<name>.npy: integers as float64 (exact below 2**53),
+    bytes as float32.  An array of more than DUMP_VALUES values keeps a seeded sample of its rows, the first and the last among
+    them; the sample depends only on the row count, so two builds given the same arguments dump the same rows."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name in DUMP_ARRAYS:
+        t = getattr(res, name)
+        if t is None:
+            continue
+        rows = t.shape[0]
+        keep = max(2, DUMP_VALUES // max(1, t[0].numel() if rows else 1))
+        if rows > keep:
+            inner = 1 + np.sort(np.random.default_rng(DUMP_SEED).choice(rows - 2, keep - 2, replace=False))
+            idx = np.concatenate(([0], inner, [rows - 1]))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32 if a.dtype == np.uint8 else np.float64))
+
+
+def stage_roofline(lib, res, st: dict, n_local: int) -> dict:
+    """Per-kernel durations of the timed steps (HIP events on the launch stream, inside the C-ABI, recorded while --full enables
+    them) against the algorithmic bytes of each launch."""
+    import torch
+    from hmse_amd import ops
+    kern = {}
+    tokens = {}          # tokens written (match kernels) / read (encode kernels) per launch, counted on the device
+    for s, name in STAGE_NAMES.items():
+        ms, n, tk = C.c_double(), C.c_uint64(), C.c_uint64()
+        lib.hmse_profile_read(s, C.byref(ms), C.byref(n), 1)
+        lib.hmse_profile_counter(s, C.byref(tk), 1)
+        if n.value:
+            kern[name] = {"avg_ms": ms.value / n.value, "launches": int(n.value)}
+            tokens[name] = tk.value / n.value
+    # algorithmic bytes per launch (SURVEY.md §8d): L2/L3 read every input byte once; L4a reads the unique
+    # bytes; L1 reads unique + dictionary bytes and writes the streams
+    lens = res.cuts[1:] - res.cuts[:-1]
+    dict_bytes = 0
+    if res.base is not None and res.uniq_ids.numel():
+        hb = res.base >= 0
+        dict_bytes = int(lens[res.uniq_ids[res.base[hb]]].sum().item()) if bool(hb.any()) else 0
+    alg = {"l2_hash_kernel": n_local, "l3_sha256_kernel": n_local + 32 * st["chunks"],
+           "l4_minhash_kernel": st["unique_bytes"] + 512 * st["unique"]}
+    # DEFLATE jobs per size class: window bytes read (chunk + dictionary) + the share of stream bytes written
+    if res.kind is not None and res.uniq_ids.numel():
+        ul = lens[res.uniq_ids]
+        hb = res.base >= 0 if res.base is not None else torch.zeros_like(ul, dtype=torch.bool)
+        dl = torch.clamp(ul[res.base.clamp(min=0)], max=32768) if res.base is not None else torch.zeros_like(ul)
+        # match jobs: one per chunk — its own window, or chunk + dictionary for a chunk with a base (that job emits both the
+        # FULL and the DELTA token list); encode jobs: one per record
+
+        def by_class(T, Ltok, off):
+            c_s, c_s2, c_sg, c_sg2, c_sg3 = ops.DEFLATE_CLASS_CAPS
+            cls = torch.where(T <= c_s, 0, torch.where(T <= c_s2, 4, torch.where(T <= c_sg, 5, torch.where(T <= c_sg2, 1, torch.where(T <= c_sg3, 2, 3)))))
+            for c, slot in DEFLATE_CLASS_SLOT.items():
+                m = cls == c
+                # match kernel: window read + token list written (4 B per token, COUNTED by the kernel: hmse_profile_counter)
+                alg[STAGE_NAMES[slot + off]] = int(T[m].sum().item() + 4 * tokens.get(STAGE_NAMES[slot + off], 0))
+
+        by_class(ul[~hb], ul[~hb], 0)                # plain jobs
+        by_class((ul + dl)[hb], ul[hb], 10)          # dictionary jobs (one token list: the DELTA record's)
+        enc_slots = (14, 15, 30, 31)
+        tot_tok = sum(tokens.get(STAGE_NAMES[sl], 0) for sl in enc_slots) or 1
+        for slot in enc_slots:
+            # encode kernel: token list read (counted), stream written (share of the stored bytes by token share)
+            alg[STAGE_NAMES[slot]] = int(4 * tokens.get(STAGE_NAMES[slot], 0) + st["stored_bytes"] * tokens.get(STAGE_NAMES[slot], 0) / tot_tok)
+    stage_roof = {}
+    for name, k in kern.items():
+        if name not in alg:
+            continue
+        gbps = alg[name] / (k["avg_ms"] * 1e-3) / 1e9
+        stage_roof[name] = {"avg_ms": round(k["avg_ms"], 4), "alg_bytes": int(alg[name]), "GBps": round(gbps, 2),
+                            "frac_hbm": round(gbps / HBM_PEAK_GBPS, 5)}
+    return stage_roof
+
+
 # ------------------------------------------------------------------------------------------ main
 def launch_ranks(a) -> int:
     """`python bench.py --gpus N` started WITHOUT torch.distributed.run (no RANK / WORLD_SIZE in the environment): start the N ranks
@@ -318,7 +411,7 @@ def main():
     t_gen = time.time() - t0
     # CPU baseline leg first: it forks worker processes, which must happen before this process initialises the GPU
     cpu = None
-    if not a.no_cpu_baseline and world == 1 and a.layers == "full":
+    if a.full and not a.no_cpu_baseline and world == 1 and a.layers == "full":
         try:
             cpu = cpu_baseline(host, a.cpu_sample_mib)
         except Exception as e:  # noqa: BLE001 — the baseline leg must not lose the GPU measurement
@@ -362,9 +455,10 @@ def main():
     for _ in range(a.warmup):
         res = None  # free the previous step's outputs first: the caching allocator then reuses them
         res = step()
-    lib.hmse_profile_enable(1)
-    for s in STAGE_NAMES:
-        lib.hmse_profile_read(s, None, None, 1)
+    if a.full:
+        lib.hmse_profile_enable(1)
+        for s in STAGE_NAMES:
+            lib.hmse_profile_read(s, None, None, 1)
     barrier()
     t0 = time.perf_counter()
     step_marks = []      # host clock after every step's return (no extra synchronisation: a step ends in its own read-backs)
@@ -380,66 +474,20 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device="cpu" if rehearse else dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(res, a.dump_outputs)
 
-    # per-kernel durations of the timed steps (HIP events on the launch stream, inside the C-ABI)
-    kern = {}
-    tokens = {}          # tokens written (match kernels) / read (encode kernels) per launch, counted on the device
-    for s, name in STAGE_NAMES.items():
-        ms, n, tk = C.c_double(), C.c_uint64(), C.c_uint64()
-        lib.hmse_profile_read(s, C.byref(ms), C.byref(n), 1)
-        lib.hmse_profile_counter(s, C.byref(tk), 1)
-        if n.value:
-            kern[name] = {"avg_ms": ms.value / n.value, "launches": int(n.value)}
-            tokens[name] = tk.value / n.value
     st = ingest.shard_stats(res)
-    # algorithmic bytes per launch: L2/L3 read every input byte once; L4a reads the unique
-    # bytes; L1 reads unique + dictionary bytes and writes the streams
-    lens = res.cuts[1:] - res.cuts[:-1]
-    dict_bytes = 0
-    if res.base is not None and res.uniq_ids.numel():
-        hb = res.base >= 0
-        dict_bytes = int(lens[res.uniq_ids[res.base[hb]]].sum().item()) if bool(hb.any()) else 0
-    alg = {"l2_hash_kernel": n_local, "l3_sha256_kernel": n_local + 32 * st["chunks"],
-           "l4_minhash_kernel": st["unique_bytes"] + 512 * st["unique"]}
-    # DEFLATE jobs per size class: window bytes read (chunk + dictionary) + the share of stream bytes written
-    if res.kind is not None and res.uniq_ids.numel():
-        ul = lens[res.uniq_ids]
-        hb = res.base >= 0 if res.base is not None else torch.zeros_like(ul, dtype=torch.bool)
-        dl = torch.clamp(ul[res.base.clamp(min=0)], max=32768) if res.base is not None else torch.zeros_like(ul)
-        # match jobs: one per chunk — its own window, or chunk + dictionary for a chunk with a base (that job emits both the
-        # FULL and the DELTA token list); encode jobs: one per record
-
-        def by_class(T, Ltok, off):
-            c_s, c_s2, c_sg, c_sg2, c_sg3 = ops.DEFLATE_CLASS_CAPS
-            cls = torch.where(T <= c_s, 0, torch.where(T <= c_s2, 4, torch.where(T <= c_sg, 5, torch.where(T <= c_sg2, 1, torch.where(T <= c_sg3, 2, 3)))))
-            for c, slot in DEFLATE_CLASS_SLOT.items():
-                m = cls == c
-                # match kernel: window read + token list written (4 B per token, COUNTED by the kernel: hmse_profile_counter)
-                alg[STAGE_NAMES[slot + off]] = int(T[m].sum().item() + 4 * tokens.get(STAGE_NAMES[slot + off], 0))
-
-        by_class(ul[~hb], ul[~hb], 0)                # plain jobs
-        by_class((ul + dl)[hb], ul[hb], 10)          # dictionary jobs (one token list: the DELTA record's)
-        enc_slots = (14, 15, 30, 31)
-        tot_tok = sum(tokens.get(STAGE_NAMES[sl], 0) for sl in enc_slots) or 1
-        for slot in enc_slots:
-            # encode kernel: token list read (counted), stream written (share of the stored bytes by token share)
-            alg[STAGE_NAMES[slot]] = int(4 * tokens.get(STAGE_NAMES[slot], 0) + st["stored_bytes"] * tokens.get(STAGE_NAMES[slot], 0) / tot_tok)
-    stage_roof = {}
-    for name, k in kern.items():
-        if name not in alg:
-            continue
-        gbps = alg[name] / (k["avg_ms"] * 1e-3) / 1e9
-        stage_roof[name] = {"avg_ms": round(k["avg_ms"], 4), "alg_bytes": int(alg[name]), "GBps": round(gbps, 2),
-                            "frac_hbm": round(gbps / HBM_PEAK_GBPS, 5)}
+    stage_roof = stage_roofline(lib, res, st, n_local) if a.full else {}
     dom = max(stage_roof, key=lambda nme: stage_roof[nme]["avg_ms"]) if stage_roof else None
 
     # read path, outside the timed region: every stored record is inflated on the GPU and its SHA-256
     # re-checked; on one GPU the whole corpus is also reassembled (pointers included) and compared byte for byte
     read_info = None
     remote_dicts = a.global_l4 and distributed   # records may then name dictionaries stored on other ranks: no per-rank read-back
-    if remote_dicts:
+    if a.full and remote_dicts:
         read_info = {"scope": "skipped: with --global-l4 a record's dictionary may be stored on another rank (read.read_store decodes the merged store, read.reconstruct_shards the shard results)"}
-    elif res.streams is not None and res.digests is not None and os.environ.get("HMSE_BENCH_NO_VERIFY") != "1":
+    elif a.full and res.streams is not None and res.digests is not None and os.environ.get("HMSE_BENCH_NO_VERIFY") != "1":
         from hmse_amd import read
         for s in (16, 17):
             lib.hmse_profile_read(s, None, None, 1)
@@ -468,7 +516,7 @@ def main():
 
     # the product's output: the shard's manifest records, packed on the GPU (outside the timed region, reported beside it)
     manifest_info = None
-    if res.streams is not None and os.environ.get("HMSE_BENCH_NO_MANIFEST") != "1":
+    if a.full and res.streams is not None and os.environ.get("HMSE_BENCH_NO_MANIFEST") != "1":
         from hmse_amd import manifest
         sb = res.shard_bases
         manifest.pack_manifest_device(res, rank, world if sb else 1)   # warm-up (allocator, first launch)
@@ -482,7 +530,7 @@ def main():
                          "scope": "hmse_manifest_pack + record/pointer prefix sums, records resident in HBM when the clock stops (rank 0)"}
         del blob, index, cmap, ptrs
     other = None
-    if world == 1 and not distributed and a.layers == "full" and os.environ.get("HMSE_BENCH_NO_OTHER") != "1" and not a.no_other_configs:
+    if a.full and world == 1 and not distributed and a.layers == "full" and os.environ.get("HMSE_BENCH_NO_OTHER") != "1" and not a.no_other_configs:
         try:
             other = other_configs(data, host, dev, cfg)
         except Exception as e:  # noqa: BLE001 — a side measurement must not lose the headline
@@ -538,7 +586,8 @@ def main():
             out["manifest_inclusive_GiB_per_s"] = round(tot["bytes"] / (dt / a.steps + manifest_info["pack_ms"] * 1e-3) / 2**30, 3)
         if other:
             out["other_configs"] = other
-        out["stage_roofline"] = stage_roof
+        if a.full:
+            out["stage_roofline"] = stage_roof
         if read_info:
             out["read_path"] = read_info
         if cpu is not None:

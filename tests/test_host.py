@@ -357,6 +357,35 @@ def test_bench_started_bare_with_gpus_2_runs_two_ranks_or_fails():
         assert q.returncode != 0 and not [ln for ln in q.stdout.decode().splitlines() if ln.startswith("{")]
 
 
+def test_bench_dump_outputs_writes_the_step_s_arrays_or_a_seeded_sample(orc, tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: every array of the step's result as float32 (bytes) / float64 (integers) .npy, whole and
+    exact up to the cap; above it a sample of rows, first and last included, that two dumps of equal results share.  The
+    cap keeps the whole dump within 64 MB."""
+    import bench
+    from hmse_amd import corpus
+    res = _shard_result_from_oracle(orc, corpus.wiki_synth(3 << 20, seed=42), {"seg_size": 1 << 20})
+    assert len(bench.DUMP_ARRAYS) * bench.DUMP_VALUES * 8 <= 64e6
+    bench.dump_outputs(res, str(tmp_path / "whole"))
+    monkeypatch.setattr(bench, "DUMP_VALUES", 256)
+    bench.dump_outputs(res, str(tmp_path / "a"))
+    bench.dump_outputs(res, str(tmp_path / "b"))
+    sampled = 0
+    for name in bench.DUMP_ARRAYS:
+        if getattr(res, name) is None:
+            assert not (tmp_path / "whole" / (name + ".npy")).exists()
+            continue
+        src = getattr(res, name).numpy()
+        whole, a, b = (np.load(tmp_path / d / (name + ".npy")) for d in ("whole", "a", "b"))
+        assert whole.dtype == a.dtype == (np.float32 if src.dtype == np.uint8 else np.float64), name
+        if src.size <= 1 << 19:
+            assert np.array_equal(whole, src), name
+        keep = max(2, 256 // max(1, src[0].size))
+        assert a.shape == (min(len(src), keep),) + src.shape[1:] and np.array_equal(a, b), name
+        assert np.array_equal(a[0], src[0]) and np.array_equal(a[-1], src[-1]), name
+        sampled += len(src) > keep
+    assert sampled >= 5
+
+
 def test_isa_audit_finds_nothing_unpinned():
     """a static guard for the hazard that hung the GPU in rounds 1 and 3 (a cross-lane read inside a loop the
     compiler structurised as divergent).  tools/isa_audit.py disassembles the shipped library (CPU only); every finding must be
