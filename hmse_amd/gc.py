@@ -1,0 +1,299 @@
+"""Garbage collection: drop segments from a one-shard store and collect its records on the GPU.
+
+The ChunkIndex refcount is kept "for garbage collection" (README.md:1268, 1886); this module is what reads it back
+out of the chunk map.  The unit of deletion is the SEGMENT: L2 restarts its Gear hash at every segment start, so a segment
+boundary is always a cut, and the store that remains after dropping segments is defined exactly — it is, byte for byte, what
+`build_manifest(ingest_shard(R, cfg, seg_off=R_seg_off))` writes for the concatenation R of the surviving segments:
+  * L2  the surviving segments keep their cuts;
+  * L3  digests come from the old ChunkIndex; a slot's new first occurrence is its first SURVIVING reference (hmse_gc_plan), so a
+        POINTER whose stored chunk was dropped is promoted to a stored chunk;
+  * L4  a signature depends only on the chunk's bytes: hmse_l4_lsh runs again over the surviving signatures in their new order;
+  * L1  the record of a (chunk, dictionary) pair is deterministic: it is reused when the pair is unchanged and re-encoded by
+        hmse_l1_deflate otherwise; hmse_record_gather assembles the dense streams from both sources in one launch.
+The packing is the unchanged manifest.pack_manifest_device of a fresh ingest.  Cross-shard GC (n_shards > 1, remote
+dictionaries, a multi-rank stream's pieces) is out of scope and refused.
+"""
+from __future__ import annotations
+
+import time
+
+import numpy as np
+
+from .config import KIND_DELTA, KIND_POINTER, LAYER_L1, LAYER_L2, LAYER_L3, LAYER_L4, IngestConfig
+from .manifest import CHUNK_INDEX_DTYPE, MAP_DTYPE, POINTER_DTYPE, Manifest, Store
+
+SUPPORTED_LAYERS = (LAYER_L1 | LAYER_L2 | LAYER_L3 | LAYER_L4, LAYER_L1 | LAYER_L2 | LAYER_L3)   # "full", "l1_cdc_dedupe"
+
+
+def _one_manifest(m) -> Manifest:
+    if isinstance(m, Store):
+        if len(m.shards) != 1:
+            raise ValueError(f"gc: a store of {len(m.shards)} shards — cross-shard garbage collection is not supported")
+        m = m.shards[0]
+    if m.n_shards != 1:
+        raise ValueError(f"gc: shard {m.shard} of {m.n_shards} — cross-shard garbage collection is not supported")
+    if m.n_remote():
+        raise ValueError("gc: records of this manifest use dictionaries stored in other shards (remote_bases)")
+    if m.pieces is not None:
+        raise ValueError("gc: the manifest is one rank's part of a multi-rank stream (pieces)")
+    return m
+
+
+def _check_layers(cfg: IngestConfig) -> None:
+    if not (cfg.layers & LAYER_L1 and cfg.layers & LAYER_L3):
+        raise ValueError("gc: the store needs the L1 records and the L3 index (layer masks without L1 or L3 are not collectable)")
+    if cfg.layers not in SUPPORTED_LAYERS:
+        raise ValueError(f"gc: layer mask {cfg.layers:#x} is not supported (full or l1_cdc_dedupe)")
+
+
+def store_cuts(m: Manifest) -> np.ndarray:
+    """Old chunk ends from the chunk map's raw lengths: int64[n_chunks + 1]."""
+    return np.concatenate([[0], np.cumsum(m.chunk_map["raw_length"].astype(np.int64))]).astype(np.int64)
+
+
+def store_seg_off(m: Manifest, cfg: IngestConfig, seg_off=None, cuts: np.ndarray | None = None) -> np.ndarray:
+    """The store's segment table (None: the fixed cfg.seg_size grid), checked against its cut list: every segment boundary must
+    be a cut, otherwise the store was not ingested with this seg_size / seg_off."""
+    cuts = store_cuts(m) if cuts is None else cuts
+    n = int(cuts[-1])
+    if seg_off is None:
+        k = max(1, -(-n // cfg.seg_size))
+        so = np.minimum(np.arange(k + 1, dtype=np.int64) * cfg.seg_size, n)
+    else:
+        so = np.asarray(seg_off.cpu() if hasattr(seg_off, "cpu") else seg_off, np.int64).reshape(-1)
+        if len(so) < 2 or so[0] != 0 or so[-1] != n or (np.diff(so) < 0).any():
+            raise ValueError(f"gc: seg_off must run from 0 to the store's {n} bytes, ascending")
+    missing = so[~np.isin(so, cuts)]
+    if len(missing):
+        raise ValueError(f"gc: the store's cut list misses segment boundary {int(missing[0])} (and {len(missing) - 1} more): "
+                         "it was not ingested with this seg_size / seg_off")
+    return so
+
+
+def segments_of_ranges(seg_off: np.ndarray, ranges) -> list:
+    """[(offset, len), ...] of segment-aligned byte ranges -> the sorted segment indices they cover.  A range that does not start
+    and end on a segment boundary raises ValueError naming the nearest boundaries."""
+    so = np.asarray(seg_off, np.int64)
+    out = set()
+    for off, ln in ranges:
+        off, ln = int(off), int(ln)
+        if off < 0 or ln < 0 or off + ln > int(so[-1]):
+            raise ValueError(f"gc: range ({off}, {ln}) lies outside the store's {int(so[-1])} bytes")
+        for x in (off, off + ln):
+            if not (so == x).any():
+                i = int(np.searchsorted(so, x))
+                raise ValueError(f"gc: range ({off}, {ln}) is not segment-aligned: byte {x} lies between segment boundaries "
+                                 f"{int(so[i - 1])} and {int(so[i])}")
+        lo = int(np.searchsorted(so, off, side="left"))
+        hi = int(np.searchsorted(so, off + ln, side="left"))
+        out.update(range(lo, hi))
+    return sorted(out)
+
+
+def drop_ranges(m, ranges, cfg: IngestConfig, device, band_tables: bytes | None = None, seg_off=None, verify: bool = True, timings=None):
+    """drop_segments() of the segments that the segment-aligned byte ranges [(offset, len), ...] cover."""
+    m = _one_manifest(m)
+    _check_layers(cfg)
+    so = store_seg_off(m, cfg, seg_off)
+    return drop_segments(m, segments_of_ranges(so, ranges), cfg, device, band_tables, so, verify, timings)
+
+
+def drop_segments(m, drop, cfg: IngestConfig, device, band_tables: bytes | None = None, seg_off=None, verify: bool = True, timings=None):
+    """Drop the segments `drop` (indices into the store's segment table: `seg_off`, or the fixed cfg.seg_size grid when None) from
+    a one-shard store and collect its records.  Returns (Manifest, sidecar bytes or None, stats):
+      * Manifest.to_bytes() equals that of build_manifest(ingest_shard(R, cfg, seg_off=R_seg_off)), R = the surviving segments;
+      * the sidecar equals StreamIngest.index_sidecar() after ingesting R (layer mask "full"; None for "l1_cdc_dedupe").
+    `band_tables` is the store's band-table sidecar (StreamIngest.index_sidecar()): with it only the records to re-encode and their
+    new dictionaries are decoded (one hmse_l1_inflate over their dictionary closure).  WITHOUT it the whole store is decoded and
+    every stored chunk goes through hmse_l4_minhash — the cost of a read of the store plus the MinHash stage of an ingest.
+    The old record of a stored chunk is reused iff it was made with the dictionary the new LSH picks; the old dictionaries of FULL
+    records (rule 7 fallbacks do not store one) are recomputed by hmse_l4_lsh over all old signatures, and every DELTA header must
+    agree with that recomputation — otherwise the store was not written under this cfg (a windowed stream, other LSH parameters)
+    and ValueError is raised rather than a store that differs from a fresh ingest.  `verify` checks the SHA-256 of every decoded
+    chunk.  Supported layer masks: "full" and "l1_cdc_dedupe"; one shard only (cross-shard GC is out of scope).
+    `timings` (a dict, diagnostics): filled with per-phase milliseconds (synchronising between phases)."""
+    m = _one_manifest(m)
+    _check_layers(cfg)
+    cuts_np = store_cuts(m)
+    so = store_seg_off(m, cfg, seg_off, cuts_np)
+    n_seg = len(so) - 1
+    drop = sorted({int(d) for d in drop})
+    if drop and (drop[0] < 0 or drop[-1] >= n_seg):
+        raise ValueError(f"gc: segment index out of range (the store has {n_seg} segments)")
+    nc, nu = len(m.chunk_map), len(m.index)
+    own = np.nonzero(m.chunk_map["kind"] != KIND_POINTER)[0]
+    if len(own) != nu or not np.array_equal(m.chunk_map["slot"][own], np.arange(nu)):
+        raise ValueError("gc: manifest index and chunk map disagree on the stored chunks")
+    if nu and not m.index["sha256"].any():
+        raise ValueError("gc: the store carries no SHA-256 digests (L3)")
+    use_l4 = bool(cfg.layers & LAYER_L4)
+    if use_l4 and band_tables is not None:
+        from . import bandtable
+        keys_side, sig_side = bandtable.read_signatures(band_tables)
+        if sig_side is None or sig_side.shape != (nu, cfg.n_hashes) or keys_side.shape != (nu, cfg.bands):
+            raise ValueError("gc: the band-table sidecar does not belong to this manifest / configuration")
+
+    import torch
+
+    from . import ingest, manifest, ops, read
+    dev = torch.device(device)
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).copy()).to(dt).to(dev)
+    clock = _Clock(timings)
+    drop_mask = np.zeros(n_seg, np.uint8)
+    drop_mask[drop] = 1
+    stats = {"segments_dropped": len(drop), "chunks_before": nc, "stored_before": nu, "blob_bytes_before": int(m.blob.size),
+             "bytes_decoded": 0}
+
+    # --- plan: survival, new chunk and slot numbering, L3 arrays (hmse_gc_plan)
+    cuts_old = t(cuts_np, torch.int64)
+    plan = ops.gc_plan(cuts_old, t(m.chunk_map["slot"].astype(np.int32), torch.int32), nu, t(so, torch.int64), t(drop_mask, torch.uint8),
+                       t(m.index["sha256"], torch.uint8).reshape(nu, 32))
+    n_new, u_new = plan["old_chunk"].numel(), plan["old_slot"].numel()
+    lens_old = cuts_old[1:] - cuts_old[:-1]
+    cuts_new = torch.zeros(n_new + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(lens_old[plan["old_chunk"]], 0, out=cuts_new[1:])
+    old_slot, new_slot_of_old = plan["old_slot"], plan["new_slot_of_old"]
+    clock.lap("plan")
+    if n_new == 0:
+        stats.update(_counts(0, 0, 0, 0, 0, 0, 0, 0))
+        empty = Manifest(1, np.zeros(0, CHUNK_INDEX_DTYPE), np.zeros(0, MAP_DTYPE), np.zeros(0, POINTER_DTYPE), np.zeros(0, np.uint8))
+        side = _sidecar(np.zeros((0, cfg.bands), np.int32), np.zeros((0, cfg.n_hashes), np.int32), cfg) if use_l4 else None
+        return empty, side, stats
+
+    rd = read.StoreReader(m, dev)                    # blob in HBM, record headers parsed (one shard: slot order, base < slot)
+    kind_old = t(rd.kind, torch.uint8)
+    raw_all = raw_off_all = None
+
+    def decode(slots: np.ndarray):
+        """One hmse_l1_inflate over `slots` (ascending, closed under dictionaries) -> (raw, raw_off)."""
+        b = rd.base[slots]
+        base_sel = np.where(b >= 0, np.searchsorted(slots, np.maximum(b, 0)), -1)
+        raw, raw_off, _ = ops.l1_inflate(rd.blob, t(rd.stream_off[slots], torch.int64), t(rd.kind[slots], torch.uint8), t(base_sel, torch.int64),
+                                         t(rd.raw_len[slots], torch.int64), stream_len=t(rd.stream_len[slots], torch.int32))
+        if verify:
+            read.verify_digests(raw, raw_off, t(rd.sha[slots], torch.uint8))
+        stats["bytes_decoded"] += int(rd.raw_len[slots].sum())
+        return raw, raw_off
+
+    # --- L4: signatures of the old stored chunks, the old dictionaries (recomputed), the new ones
+    sig_new = keys_new = base_new = None
+    if use_l4:
+        if band_tables is not None:
+            sig_old = t(sig_side.view(np.int32), torch.int32)
+        else:
+            raw_all, raw_off_all = decode(np.arange(nu, dtype=np.int64))
+            clock.lap("decode")
+            sig_old = ops.l4_minhash(raw_all, raw_off_all, cfg)
+            clock.lap("minhash")
+        keys_old, base_old = ops.l4_lsh(sig_old, cfg)
+        hdr_base = t(rd.base, torch.int64)
+        if not bool(((kind_old != KIND_DELTA) | (hdr_base == base_old)).all()):
+            raise ValueError("gc: a DELTA record's dictionary is not the LSH base of its chunk under this configuration "
+                             "(the store was written with other LSH parameters or by a windowed stream)")
+        if band_tables is not None and not torch.equal(keys_old, t(keys_side.view(np.int32), torch.int32)):
+            raise ValueError("gc: the sidecar's band keys are not those of its signatures under this configuration")
+        sig_new = sig_old[old_slot]
+        keys_new, base_new = ops.l4_lsh(sig_new, cfg)
+        base_new_old = torch.where(base_new >= 0, old_slot[base_new.clamp(min=0)], base_new)   # new dictionary as an old slot
+        old_base = base_old[old_slot]
+        reuse = old_base == base_new_old
+        clock.lap("lsh")
+    else:
+        base_new_old = old_base = torch.full((u_new,), -1, dtype=torch.int64, device=dev)
+        reuse = torch.ones(u_new, dtype=torch.bool, device=dev)
+
+    # --- why each stored chunk is re-encoded: promoted POINTER, old dictionary dropped or now behind it, dictionary changed
+    j_idx = torch.arange(u_new, dtype=torch.int64, device=dev)
+    own_old = t(own, torch.int64)
+    promoted = plan["old_chunk"][plan["uniq_ids"]] != own_old[old_slot]
+    ob_new = torch.where(old_base >= 0, new_slot_of_old[old_base.clamp(min=0)], old_base)
+    base_gone = (old_base >= 0) & ((ob_new < 0) | (ob_new > j_idx))
+    redo = ~reuse
+    enc = redo.nonzero().flatten()
+    n_enc = int(enc.numel())
+
+    # --- L1: re-encode what cannot be reused (hmse_l1_deflate, dictionaries by chunk id into the decoded closure)
+    src1 = None
+    kind_e = torch.zeros(0, dtype=torch.uint8, device=dev)
+    off_e = torch.zeros(1, dtype=torch.int64, device=dev)
+    if n_enc:
+        slots_e = old_slot[enc]
+        bases_e = base_new_old[enc]
+        if raw_all is not None:                     # the whole store is decoded already
+            data, dcuts = raw_all, raw_off_all
+            cid, bid = slots_e, bases_e
+        else:
+            se, be = slots_e.cpu().numpy(), bases_e.cpu().numpy()
+            need = rd.closure(np.concatenate([se, be[be >= 0]]))
+            data, dcuts = decode(need)
+            clock.lap("decode")
+            need_d = t(need, torch.int64)
+            cid = torch.searchsorted(need_d, slots_e)
+            bid = torch.where(bases_e >= 0, torch.searchsorted(need_d, bases_e.clamp(min=0)), bases_e)
+        src1, off_e, kind_e = ops.l1_deflate(data, dcuts, cfg, cid, bid, base_is_chunk_id=True)
+        del data, dcuts
+        clock.lap("reencode")
+    raw_all = raw_off_all = None
+
+    # --- gather: dense streams of the new store from the old blob (reused) and the DEFLATE output (re-encoded)
+    # per stored chunk: its re-encoded record's number, or n_enc (a spare zero entry) for a reused one — every index stays in range
+    rec_e = torch.full((u_new,), n_enc, dtype=torch.int64, device=dev)
+    rec_e[enc] = torch.arange(n_enc, dtype=torch.int64, device=dev)
+    z64 = torch.zeros(1, dtype=torch.int64, device=dev)
+    e_off, e_len = torch.cat([off_e[:-1], z64]), torch.cat([off_e[1:] - off_e[:-1], z64])
+    e_kind = torch.cat([kind_e, torch.zeros(1, dtype=torch.uint8, device=dev)])
+    s_off_old, s_len_old = t(rd.stream_off, torch.int64), t(rd.stream_len, torch.int64)
+    src_off = torch.where(redo, e_off[rec_e], s_off_old[old_slot])
+    s_len = torch.where(redo, e_len[rec_e], s_len_old[old_slot])
+    kind_new = torch.where(redo, e_kind[rec_e], kind_old[old_slot])
+    stream_off = torch.zeros(u_new + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(s_len, 0, out=stream_off[1:])
+    streams = ops.record_gather(rd.blob, src1, src_off, redo.to(torch.uint8), stream_off)
+    clock.lap("gather", nbytes=2 * int(streams.numel()))
+    del rd, src1
+
+    # --- pack: the ShardResult a fresh ingest of the remainder returns, through the unchanged packing code
+    res = ingest.ShardResult(int(cuts_new[-1].item()), cuts_new, plan["digests"], 0, n_new, plan["first_occ"], plan["refcount"],
+                             plan["uniq_ids"], sig_new, keys_new, base_new if use_l4 else None, streams, stream_off, kind_new)
+    out = manifest.build_manifest(res)
+    side = _sidecar(keys_new.cpu().numpy(), sig_new.cpu().numpy(), cfg) if use_l4 else None
+    clock.lap("pack")
+    changed = redo & (kind_new != kind_old[old_slot])
+    stats.update(_counts(n_new, u_new, u_new - n_enc, int((redo & promoted).sum()), int((redo & ~promoted & base_gone).sum()),
+                         int((redo & ~promoted & ~base_gone).sum()), int(promoted.sum()), int(changed.sum())))
+    stats["blob_bytes_after"] = int(out.blob.size)
+    return out, side, stats
+
+
+def _counts(n_new, u_new, reused, r_prom, r_gone, r_changed, promoted, kind_changed) -> dict:
+    return {"chunks_after": n_new, "stored_after": u_new, "records_reused": reused, "records_reencoded": r_prom + r_gone + r_changed,
+            "reencoded_promoted": r_prom, "reencoded_base_dropped_or_moved": r_gone, "reencoded_base_changed": r_changed,
+            "promoted": promoted, "kind_changed": kind_changed, "blob_bytes_after": 0}
+
+
+def _sidecar(keys: np.ndarray, sig: np.ndarray, cfg: IngestConfig) -> bytes:
+    from . import bandtable
+    return bandtable.write_band_tables(keys, cfg.band_bits, signatures=sig)
+
+
+class _Clock:
+    """Per-phase wall time with a device sync at every lap — only when the caller asked for timings."""
+
+    def __init__(self, out):
+        self.out = out
+        if out is not None:
+            import torch
+            torch.cuda.synchronize()
+            self.t = time.perf_counter()
+
+    def lap(self, name: str, nbytes: int = 0) -> None:
+        if self.out is None:
+            return
+        import torch
+        torch.cuda.synchronize()
+        now = time.perf_counter()
+        ms = (now - self.t) * 1e3
+        self.out[name] = self.out.get(name, 0.0) + ms
+        if nbytes:
+            self.out[name + "_bytes"] = nbytes
+        self.t = now

@@ -16,6 +16,7 @@ from .config import IngestConfig
 
 STAGE_L2, STAGE_SHA, STAGE_DEDUP, STAGE_MINHASH, STAGE_LSH, STAGE_DEFLATE = 2, 3, 4, 5, 6, 7
 STAGE_INFLATE, STAGE_ASSEMBLE, STAGE_MANIFEST = 16, 17, 18
+STAGE_GC_PLAN, STAGE_RECORD_GATHER = 24, 25
 
 
 class HmseError(RuntimeError):
@@ -375,6 +376,66 @@ def manifest_pack(res, shard: int, n_shards: int, shard_bases, rec_off: torch.Te
     st = int(status.item())
     if st:
         raise HmseError(-2, f"hmse_manifest_pack device status {st:#x}")
+
+
+def gc_plan(cuts: torch.Tensor, slot: torch.Tensor, n_slots: int, seg_off: torch.Tensor, drop: torch.Tensor, digests_old: torch.Tensor) -> dict:
+    """hmse_gc_plan: the old chunk map (`cuts` int64[n+1], `slot` int32[n]) and the dropped segments (`seg_off` int64[n_seg+1], `drop`
+    uint8[n_seg]) -> the L3 arrays of the surviving store as a fresh ingest of the remainder numbers them.  `digests_old` uint8[n_slots, 32].
+    Returns {old_chunk, first_occ, refcount, digests, uniq_ids, old_slot (int64[u_new]), new_slot_of_old (int64[n_slots], -1 gone)}.
+    README.md:1268, 1886 (the refcount kept for garbage collection)."""
+    for t, nm in ((cuts, "cuts"), (slot, "slot"), (seg_off, "seg_off"), (drop, "drop"), (digests_old, "digests_old")):
+        _require_gpu(t, nm)
+    dev = cuts.device
+    n = cuts.numel() - 1
+    n_seg = seg_off.numel() - 1
+    if slot.numel() != n or drop.numel() != n_seg or digests_old.shape != (n_slots, 32) or n_seg < 1:
+        raise HmseError(-1, "gc_plan: slot / drop / digests_old do not match cuts / seg_off / n_slots")
+    counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    e = lambda *shape, dt=torch.int64: torch.empty(shape, dtype=dt, device=dev)
+    old_chunk, first_occ, refcount, digests = e(max(n, 1)), e(max(n, 1)), e(max(n, 1), dt=torch.int32), e(max(n, 1), 32, dt=torch.uint8)
+    uniq_ids, old_slot, new_slot_of_old = e(max(n_slots, 1)), e(max(n_slots, 1)), e(max(n_slots, 1))
+    ws = _ws(workspace_bytes(STAGE_GC_PLAN, n, IngestConfig()), dev)
+    rc = _lib.hip_lib().hmse_gc_plan(_ptr(cuts), n, _ptr(slot), int(n_slots), _ptr(seg_off), n_seg, _ptr(drop), _ptr(digests_old), _ptr(counts),
+                                     _ptr(old_chunk), _ptr(first_occ), _ptr(refcount), _ptr(digests), _ptr(uniq_ids), _ptr(old_slot),
+                                     _ptr(new_slot_of_old), _ptr(status), ws.data_ptr(), ws.numel(), _stream())
+    _check(rc, "hmse_gc_plan")
+    n_new, u_new, st = (int(v) for v in torch.cat([counts, status.to(torch.int64)]).tolist())   # the one host sync: output sizes
+    if st:
+        raise HmseError(-2, f"hmse_gc_plan device status {st:#x}")
+    if n_new > n or u_new > min(n_new, n_slots):
+        raise HmseError(-2, f"hmse_gc_plan: {n_new} chunks / {u_new} slots survive of {n} / {n_slots}")
+    if u_new:   # every index the caller will gather with lies inside its array (torch's device-side indexing does not check)
+        lim = torch.stack([old_chunk[:n_new].min(), old_chunk[:n_new].max(), uniq_ids[:u_new].min(), uniq_ids[:u_new].max(),
+                           old_slot[:u_new].min(), old_slot[:u_new].max()]).tolist()
+        if lim[0] < 0 or lim[1] >= n or lim[2] < 0 or lim[3] >= n_new or lim[4] < 0 or lim[5] >= n_slots:
+            raise HmseError(-2, f"hmse_gc_plan: an index outside its array ({lim})")
+    return {"old_chunk": old_chunk[:n_new], "first_occ": first_occ[:n_new], "refcount": refcount[:n_new], "digests": digests[:n_new],
+            "uniq_ids": uniq_ids[:u_new], "old_slot": old_slot[:u_new], "new_slot_of_old": new_slot_of_old[:n_slots]}
+
+
+def record_gather(src0: torch.Tensor, src1: torch.Tensor | None, src_off: torch.Tensor, src_sel: torch.Tensor, dst_off: torch.Tensor,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """hmse_record_gather: record k = bytes [src_off[k], + dst_off[k+1] - dst_off[k]) of (src1 if src_sel[k] else src0), laid out
+    densely at dst_off (int64[n+1]).  Returns the uint8 destination (`out`, or a new tensor of dst_off[-1] bytes)."""
+    srcs = [src0] + ([src1] if src1 is not None else [])
+    for t, nm in [(t, "src") for t in srcs] + [(src_off, "src_off"), (src_sel, "src_sel"), (dst_off, "dst_off")]:
+        _require_gpu(t, nm)
+    dev = dst_off.device
+    n = src_sel.numel()
+    if src_off.numel() != n or dst_off.numel() != n + 1:
+        raise HmseError(-1, "record_gather: src_off / src_sel / dst_off do not match")
+    if out is None:
+        out = torch.empty(int(dst_off[-1].item()), dtype=torch.uint8, device=dev)
+    _require_gpu(out, "out")
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    keep = lambda t: t if t is not None and t.numel() else None
+    rc = _lib.hip_lib().hmse_record_gather(_ptr(keep(src0)), src0.numel(), _ptr(keep(src1)), 0 if src1 is None else src1.numel(), _ptr(src_off),
+                                           _ptr(src_sel), _ptr(dst_off), n, _ptr(out) if out.numel() else None, out.numel(), _ptr(status), _stream())
+    _check(rc, "hmse_record_gather")
+    if n and int(status.item()):
+        raise HmseError(-2, "hmse_record_gather: a record lies outside its source or the destination")
+    return out
 
 
 def stream_batch_workspace_bytes(batch_bytes: int, cfg: IngestConfig) -> int:

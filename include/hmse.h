@@ -50,7 +50,10 @@ enum {
   /* read path; ids 8..15 are the DEFLATE kernels' profiling slots */
   HMSE_STAGE_L1_INFLATE    = 16,
   HMSE_STAGE_READ_ASSEMBLE = 17,
-  HMSE_STAGE_MANIFEST_PACK = 18
+  HMSE_STAGE_MANIFEST_PACK = 18,
+  /* garbage collection of dropped segments (hmse_gc_plan; hmse_record_gather's profiling slot) */
+  HMSE_STAGE_GC_PLAN       = 24,
+  HMSE_STAGE_RECORD_GATHER = 25
 };
 
 /* layer-enable mask == the reference's ablation matrix / degradation modes
@@ -429,6 +432,39 @@ int hmse_manifest_pack_ex(const uint8_t* streams, const uint64_t* stream_off, co
                           const uint64_t* rec_off, uint32_t lba_unit, const uint64_t* ptr_index, uint8_t* blob,
                           uint64_t blob_bytes, void* index, void* chunk_map, void* pointers, uint64_t n_pointers,
                           uint32_t* status, void* ws, size_t ws_bytes, void* stream);
+
+/*
+ * Garbage collection, plan (the ChunkIndex refcount is kept "for garbage collection", README.md:1268, 1886): the chunk map of a
+ * one-shard store and a set of dropped segments -> the L3 arrays of the store that holds only the surviving segments, numbered
+ * as a fresh ingest of that remainder numbers them (a segment boundary is always a cut, so the surviving chunks keep their cuts).
+ *   cuts        DEVICE u64[n_chunks+1] old chunk ends;  slot DEVICE u32[n_chunks] the old chunk map's index slot of each chunk
+ *   seg_off     DEVICE u64[n_seg+1] the store's segment table (seg_off[n_seg] == cuts[n_chunks]); drop DEVICE u8[n_seg], 1 = dropped
+ *   digests_old DEVICE u8[n_slots][32] the old ChunkIndex digests
+ *   counts      DEVICE u64[2] out: {surviving chunks n_new, surviving slots u_new}
+ *   old_chunk   DEVICE i64[n_chunks]: [k < n_new] old index of new chunk k
+ *   first_occ   DEVICE i64[n_chunks], refcount DEVICE u32[n_chunks], digests DEVICE u8[n_chunks][32]: [k < n_new] as hmse_l3_dedup
+ *               over the surviving digests (refcount counts the surviving references in the map, never the packed u16)
+ *   uniq_ids    DEVICE i64[n_slots]: [j < u_new] new chunk index of new slot j (its first surviving reference, ascending)
+ *   old_slot    DEVICE i64[n_slots]: [j < u_new] old slot of new slot j;  new_slot_of_old DEVICE i64[n_slots]: inverse, -1 = gone
+ *   status      DEVICE u32[1]: bit0 = a map slot >= n_slots
+ *   ws          hmse_workspace_bytes(HMSE_STAGE_GC_PLAN, n_chunks, cfg)
+ */
+int hmse_gc_plan(const uint64_t* cuts, uint64_t n_chunks, const uint32_t* slot, uint64_t n_slots, const uint64_t* seg_off,
+                 uint32_t n_seg, const uint8_t* drop, const uint8_t* digests_old, uint64_t* counts, int64_t* old_chunk,
+                 int64_t* first_occ, uint32_t* refcount, uint8_t* digests, int64_t* uniq_ids, int64_t* old_slot,
+                 int64_t* new_slot_of_old, uint32_t* status, void* ws, size_t ws_bytes, void* stream);
+
+/*
+ * Garbage collection, records: the dense DEFLATE streams of the collected store from two sources in one launch (one wavefront
+ * per record).  Record k is src_sel[k] ? src1 : src0, bytes [src_off[k], src_off[k] + dst_off[k+1] - dst_off[k]), copied to
+ * dst[dst_off[k] ..).  src0 is typically the old blob (a reused record's stream, behind its DeltaChunk header; any byte
+ * offset: lba_unit may be 1), src1 the hmse_l1_deflate output of the re-encoded records.
+ *   src_off DEVICE u64[n]; src_sel DEVICE u8[n]; dst_off DEVICE u64[n+1]; dst DEVICE u8[dst_bytes]
+ *   status  DEVICE u32[1]: bit0 = a record outside its source or the destination (that record is not copied)
+ */
+int hmse_record_gather(const uint8_t* src0, uint64_t src0_bytes, const uint8_t* src1, uint64_t src1_bytes, const uint64_t* src_off,
+                       const uint8_t* src_sel, const uint64_t* dst_off, uint64_t n, uint8_t* dst, uint64_t dst_bytes,
+                       uint32_t* status, void* stream);
 
 /*
  * Diagnostics (bench.py's roofline leg): when enabled, every entry point brackets its DOMINANT
