@@ -55,6 +55,13 @@ def write_band_tables(band_keys: np.ndarray, band_bits: int = 16, signatures: np
     return b"".join(out)
 
 
+def write_band_tables_device(band_keys, band_bits: int = 16, signatures=None) -> bytes:
+    """write_band_tables() of device tensors (int32 band keys [n, bands], signatures [n, n_hashes] or None), written on the GPU by
+    hmse_band_tables_write (hmse_amd/csrc/bandtable.hip) — the same bytes; only the finished sidecar crosses to the host."""
+    from . import ops
+    return ops.band_tables_write(band_keys.contiguous(), None if signatures is None else signatures.contiguous(), band_bits).cpu().numpy().tobytes()
+
+
 def read_signatures(buf: bytes):
     """-> (band keys u32[n][bands], signatures u32[n][n_hashes] or None) from the trailing section of write_band_tables()."""
     assert buf[:8] == MAGIC

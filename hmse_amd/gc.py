@@ -10,8 +10,11 @@ boundary is always a cut, and the store that remains after dropping segments is 
   * L4  a signature depends only on the chunk's bytes: hmse_l4_lsh runs again over the surviving signatures in their new order;
   * L1  the record of a (chunk, dictionary) pair is deterministic: it is reused when the pair is unchanged and re-encoded by
         hmse_l1_deflate otherwise; hmse_record_gather assembles the dense streams from both sources in one launch.
-The packing is the unchanged manifest.pack_manifest_device of a fresh ingest.  Cross-shard GC (n_shards > 1, remote
-dictionaries, a multi-rank stream's pieces) is out of scope and refused.
+The packing is the unchanged manifest.pack_manifest_device of a fresh ingest.
+A merged store of several shards (drop_sharded) has the same definition shard by shard — the store a fresh sharded ingest
+(ingest_shards_local) of every shard's surviving segments writes — with one plan over the concatenated chunk map, L4 in the store's
+scope (shard-local or global, remote dictionaries included) and stored chunks that move to the shard of their first surviving
+reference.  A multi-rank stream's store (pieces) and an unmerged part are refused.
 """
 from __future__ import annotations
 
@@ -28,15 +31,37 @@ SUPPORTED_LAYERS = (LAYER_L1 | LAYER_L2 | LAYER_L3 | LAYER_L4, LAYER_L1 | LAYER_
 def _one_manifest(m) -> Manifest:
     if isinstance(m, Store):
         if len(m.shards) != 1:
-            raise ValueError(f"gc: a store of {len(m.shards)} shards — cross-shard garbage collection is not supported")
+            raise ValueError(f"gc: a store of {len(m.shards)} shards goes through the sharded path (drop_segments of the Store)")
         m = m.shards[0]
     if m.n_shards != 1:
-        raise ValueError(f"gc: shard {m.shard} of {m.n_shards} — cross-shard garbage collection is not supported")
+        raise ValueError(f"gc: shard {m.shard} of {m.n_shards} is one part of a sharded store: merge_manifests() the parts and "
+                         "collect the merged Store")
     if m.n_remote():
         raise ValueError("gc: records of this manifest use dictionaries stored in other shards (remote_bases)")
     if m.pieces is not None:
         raise ValueError("gc: the manifest is one rank's part of a multi-rank stream (pieces)")
     return m
+
+
+def _sharded(m) -> bool:
+    return isinstance(m, Store) and len(m.shards) > 1
+
+
+def _check_store(store: Store) -> list:
+    """The shards of a merged multi-shard store, checked before any device work: shard numbers, chunk bases, no stream pieces."""
+    shards = list(store.shards)
+    n = len(shards)
+    if any(m.pieces is not None for m in shards):
+        raise ValueError("gc: a multi-rank stream store (pieces: its shards' chunks interleave in stream order) is not collectable")
+    base = 0
+    for i, m in enumerate(shards):
+        if m.shard != i or m.n_shards != n:
+            raise ValueError(f"gc: the store's shard {i} is manifest shard {m.shard} of {m.n_shards}: not a merged store of {n} shards "
+                             "(merge_manifests)")
+        if m.chunk_base != base:
+            raise ValueError(f"gc: shard {i} starts at chunk {m.chunk_base}, not {base}: not a merged store (merge_manifests)")
+        base += len(m.chunk_map)
+    return shards
 
 
 def _check_layers(cfg: IngestConfig) -> None:
@@ -90,15 +115,45 @@ def segments_of_ranges(seg_off: np.ndarray, ranges) -> list:
     return sorted(out)
 
 
-def drop_ranges(m, ranges, cfg: IngestConfig, device, band_tables: bytes | None = None, seg_off=None, verify: bool = True, timings=None):
-    """drop_segments() of the segments that the segment-aligned byte ranges [(offset, len), ...] cover."""
-    m = _one_manifest(m)
+def shard_segments(store: Store, cfg: IngestConfig, seg_off=None):
+    """A merged multi-shard store's segment tables: (per shard its own table, checked against its cut list as store_seg_off does;
+    the global table — the shards' tables shifted by the shard byte offsets, shard 0's segments first; the first global segment
+    index of every shard, int64[n_shards + 1]).  `seg_off`: a list of per-shard local tables (None entries or None: cfg.seg_size)."""
+    shards = _check_store(store)
+    if seg_off is not None and len(seg_off) != len(shards):
+        raise ValueError(f"gc: seg_off must hold one segment table per shard ({len(shards)}), got {len(seg_off)}")
+    sos = [store_seg_off(m, cfg, None if seg_off is None else seg_off[i]) for i, m in enumerate(shards)]
+    byte_base = np.cumsum([0] + [int(so[-1]) for so in sos]).astype(np.int64)
+    so_g = np.concatenate([[0]] + [so[1:] + byte_base[i] for i, so in enumerate(sos)]).astype(np.int64)
+    seg_base = np.cumsum([0] + [len(so) - 1 for so in sos]).astype(np.int64)
+    return sos, so_g, seg_base
+
+
+def split_segments(seg_base: np.ndarray, drop) -> list:
+    """Global segment indices -> per shard the sorted local segment indices they name."""
+    d = np.asarray(sorted({int(x) for x in drop}), np.int64)
+    if len(d) and (d[0] < 0 or d[-1] >= int(seg_base[-1])):
+        raise ValueError(f"gc: segment index out of range (the store has {int(seg_base[-1])} segments)")
+    sh = np.searchsorted(seg_base, d, side="right") - 1
+    return [(d[sh == i] - seg_base[i]).tolist() for i in range(len(seg_base) - 1)]
+
+
+def drop_ranges(m, ranges, cfg: IngestConfig, device, band_tables=None, seg_off=None, global_l4: bool = False, verify: bool = True,
+                timings=None):
+    """drop_segments() of the segments that the segment-aligned byte ranges [(offset, len), ...] cover (a sharded store: ranges of
+    the original corpus, the shards concatenated in shard order)."""
     _check_layers(cfg)
+    if _sharded(m):
+        _, so_g, _ = shard_segments(m, cfg, seg_off)
+        return drop_segments(m, segments_of_ranges(so_g, ranges), cfg, device, band_tables=band_tables, seg_off=seg_off,
+                             global_l4=global_l4, verify=verify, timings=timings)
+    m = _one_manifest(m)
     so = store_seg_off(m, cfg, seg_off)
-    return drop_segments(m, segments_of_ranges(so, ranges), cfg, device, band_tables, so, verify, timings)
+    return drop_segments(m, segments_of_ranges(so, ranges), cfg, device, band_tables=band_tables, seg_off=so, verify=verify, timings=timings)
 
 
-def drop_segments(m, drop, cfg: IngestConfig, device, band_tables: bytes | None = None, seg_off=None, verify: bool = True, timings=None):
+def drop_segments(m, drop, cfg: IngestConfig, device, band_tables=None, seg_off=None, global_l4: bool = False, verify: bool = True,
+                  timings=None):
     """Drop the segments `drop` (indices into the store's segment table: `seg_off`, or the fixed cfg.seg_size grid when None) from
     a one-shard store and collect its records.  Returns (Manifest, sidecar bytes or None, stats):
       * Manifest.to_bytes() equals that of build_manifest(ingest_shard(R, cfg, seg_off=R_seg_off)), R = the surviving segments;
@@ -111,7 +166,11 @@ def drop_segments(m, drop, cfg: IngestConfig, device, band_tables: bytes | None 
     agree with that recomputation — otherwise the store was not written under this cfg (a windowed stream, other LSH parameters)
     and ValueError is raised rather than a store that differs from a fresh ingest.  `verify` checks the SHA-256 of every decoded
     chunk.  Supported layer masks: "full" and "l1_cdc_dedupe"; one shard only (cross-shard GC is out of scope).
-    `timings` (a dict, diagnostics): filled with per-phase milliseconds (synchronising between phases)."""
+    `timings` (a dict, diagnostics): filled with per-phase milliseconds (synchronising between phases).
+    A merged Store of more than one shard takes the sharded path (drop_sharded: one sidecar and one segment table per shard,
+    `global_l4` names the store's dictionary scope); `global_l4` means nothing to a one-shard store."""
+    if _sharded(m):
+        return drop_sharded(m, drop, cfg, device, band_tables, seg_off, global_l4, verify, timings)
     m = _one_manifest(m)
     _check_layers(cfg)
     cuts_np = store_cuts(m)
@@ -263,6 +322,222 @@ def drop_segments(m, drop, cfg: IngestConfig, device, band_tables: bytes | None 
                          int((redo & ~promoted & ~base_gone).sum()), int(promoted.sum()), int(changed.sum())))
     stats["blob_bytes_after"] = int(out.blob.size)
     return out, side, stats
+
+
+def drop_sharded(store: Store, drop, cfg: IngestConfig, device, band_tables=None, seg_off=None, global_l4: bool = False,
+                 verify: bool = True, timings=None):
+    """drop_segments() of a merged store of N > 1 shards.  `drop`: GLOBAL segment indices (shard 0's segments first, each shard's
+    as store_seg_off numbers them; a zero-byte shard keeps its one empty segment).  `band_tables`: one sidecar per shard or None;
+    `seg_off`: per-shard local segment tables or None.  Returns (Store, [N sidecars] or None, stats): with R_i the surviving segments
+    of shard i, Store.to_bytes() equals merge_manifests([build_manifest(r, i, N) for r in ingest_shards_local([R_0..], cfg,
+    global_l4=global_l4, seg_offs=[..])]) and sidecar i equals write_band_tables(r_i.band_keys, cfg.band_bits, signatures=r_i.sig).
+    One hmse_gc_plan runs over the concatenated chunk map (global slot = slot base of the chunk map's shard + slot; the global chunk
+    order (shard, local) is the order in which a sharded ingest picks first occurrences), so the plan's new chunk and slot numbers
+    are the fresh run's global numbers; they are split per shard at the new chunk bases.  A stored chunk whose first surviving
+    reference lies on another shard MIGRATES there.  L4 is recomputed per shard (shard-local) or over all shards (`global_l4`); a
+    record is reused iff its dictionary (an old global slot) is unchanged — from the old blobs, back to back as StoreReader holds
+    them, whatever its shard.  The sidecars are written on the GPU (hmse_band_tables_write)."""
+    _check_layers(cfg)
+    shards = _check_store(store)
+    N = len(shards)
+    sos, so_g, seg_base = shard_segments(store, cfg, seg_off)
+    n_seg = int(seg_base[-1])
+    drop = sorted({int(d) for d in drop})
+    if drop and (drop[0] < 0 or drop[-1] >= n_seg):
+        raise ValueError(f"gc: segment index out of range (the store has {n_seg} segments)")
+    use_l4 = bool(cfg.layers & LAYER_L4)
+    if use_l4 and band_tables is not None and len(band_tables) != N:
+        raise ValueError(f"gc: one band-table sidecar per shard ({N}), got {len(band_tables)}")
+    nc_l = [len(m.chunk_map) for m in shards]
+    nu_l = [len(m.index) for m in shards]
+    cbase = np.cumsum([0] + nc_l).astype(np.int64)
+    sbase = np.cumsum([0] + nu_l).astype(np.int64)
+    nc, nu = int(cbase[-1]), int(sbase[-1])
+    own_l = []
+    for i, m in enumerate(shards):
+        own = np.nonzero(m.chunk_map["kind"] != KIND_POINTER)[0]
+        if len(own) != nu_l[i] or not np.array_equal(m.chunk_map["slot"][own], np.arange(nu_l[i])) or (m.chunk_map["shard"][own] != i).any():
+            raise ValueError(f"gc: shard {i}'s index and chunk map disagree on its stored chunks")
+        if nu_l[i] and not m.index["sha256"].any():
+            raise ValueError("gc: the store carries no SHA-256 digests (L3)")
+        own_l.append(own + cbase[i])
+    if any((m.chunk_map["shard"] >= N).any() for m in shards):
+        raise ValueError("gc: a chunk map entry names a shard outside the store")
+    keys_side = sig_side = None
+    if use_l4 and band_tables is not None:
+        from . import bandtable
+        ks, ss = [], []
+        for i, bt in enumerate(band_tables):
+            k, sg = bandtable.read_signatures(bt)
+            if sg is None or sg.shape != (nu_l[i], cfg.n_hashes) or k.shape != (nu_l[i], cfg.bands):
+                raise ValueError(f"gc: band-table sidecar {i} does not belong to shard {i} of this store / configuration")
+            ks.append(k); ss.append(sg)
+        keys_side, sig_side = np.concatenate(ks), np.concatenate(ss)
+
+    import torch
+
+    from . import bandtable, ingest, manifest, ops, read
+    dev = torch.device(device)
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).copy()).to(dt).to(dev)
+    clock = _Clock(timings)
+    drop_mask = np.zeros(n_seg, np.uint8)
+    drop_mask[drop] = 1
+    stats = {"segments_dropped": len(drop), "chunks_before": nc, "stored_before": nu, "blob_bytes_before": int(sum(m.blob.size for m in shards)),
+             "bytes_decoded": 0}
+
+    # --- plan over the concatenated chunk map: global cuts, global slots, global segment table
+    cuts_np = np.concatenate([[0]] + [store_cuts(m)[1:] + int(so_g[seg_base[i]]) for i, m in enumerate(shards)]).astype(np.int64)
+    slot_np = np.concatenate([sbase[m.chunk_map["shard"].astype(np.int64)] + m.chunk_map["slot"].astype(np.int64) for m in shards])
+    sha_np = np.concatenate([m.index["sha256"] for m in shards]).reshape(nu, 32)
+    cuts_old = t(cuts_np, torch.int64)
+    plan = ops.gc_plan(cuts_old, t(slot_np.astype(np.int32), torch.int32), nu, t(so_g, torch.int64), t(drop_mask, torch.uint8), t(sha_np, torch.uint8))
+    n_new, u_new = plan["old_chunk"].numel(), plan["old_slot"].numel()
+    old_slot, new_slot_of_old = plan["old_slot"], plan["new_slot_of_old"]
+    # new chunk bases (surviving chunks per shard) and new slot bases (stored chunks per shard): one host sync
+    ncb = torch.searchsorted(plan["old_chunk"], t(cbase, torch.int64))
+    nub = torch.searchsorted(plan["uniq_ids"], ncb)
+    b = torch.cat([ncb, nub]).tolist()
+    new_cb, new_ub = b[:N + 1], b[N + 1:]
+    lens_new = (cuts_old[1:] - cuts_old[:-1])[plan["old_chunk"]]
+    clock.lap("plan")
+
+    rd = read.StoreReader(store, dev)                # every shard's blob in HBM, back to back; record headers parsed (global slots)
+    if not np.array_equal(rd.slot, slot_np):
+        raise ValueError("gc: the store's dictionaries do not precede their records (not the store of a one-shot sharded ingest)")
+    kind_old = t(rd.kind, torch.uint8)
+    raw_all = raw_off_all = None
+
+    def decode(slots: np.ndarray):
+        b = rd.base[slots]
+        base_sel = np.where(b >= 0, np.searchsorted(slots, np.maximum(b, 0)), -1)
+        raw, raw_off, _ = ops.l1_inflate(rd.blob, t(rd.stream_off[slots], torch.int64), t(rd.kind[slots], torch.uint8), t(base_sel, torch.int64),
+                                         t(rd.raw_len[slots], torch.int64), stream_len=t(rd.stream_len[slots], torch.int32))
+        if verify:
+            read.verify_digests(raw, raw_off, t(rd.sha[slots], torch.uint8))
+        stats["bytes_decoded"] += int(rd.raw_len[slots].sum())
+        return raw, raw_off
+
+    def lsh(sig, bases):
+        """Band keys and dictionaries (global slots, -1 none) of `sig`: one LSH over all rows (global L4) or one per shard."""
+        if global_l4:
+            return ops.l4_lsh(sig, cfg)
+        ks, bs = [], []
+        for i in range(N):
+            k, bb = ops.l4_lsh(sig[bases[i]: bases[i + 1]], cfg)
+            ks.append(k); bs.append(torch.where(bb >= 0, bb + bases[i], bb))
+        return torch.cat(ks), torch.cat(bs)
+
+    # --- L4: old signatures, the old dictionaries (recomputed in the store's scope), the new ones
+    sig_new = keys_new = base_new = None
+    if use_l4:
+        if sig_side is not None:
+            sig_old = t(sig_side.view(np.int32), torch.int32)
+        else:
+            raw_all, raw_off_all = decode(np.arange(nu, dtype=np.int64))
+            clock.lap("decode")
+            sig_old = ops.l4_minhash(raw_all, raw_off_all, cfg)
+            clock.lap("minhash")
+        keys_old, base_old = lsh(sig_old, [int(x) for x in sbase])
+        hdr_base = t(rd.base, torch.int64)
+        if not bool(((kind_old != KIND_DELTA) | (hdr_base == base_old)).all()):
+            raise ValueError(f"gc: a DELTA record's dictionary is not the LSH base of its chunk in the {'global' if global_l4 else 'shard-local'} "
+                             "scope under this configuration (the store was written with the other L4 scope, other LSH parameters or by a "
+                             "windowed stream)")
+        if keys_side is not None and not torch.equal(keys_old, t(keys_side.view(np.int32), torch.int32)):
+            raise ValueError("gc: the sidecars' band keys are not those of their signatures under this configuration")
+        sig_new = sig_old[old_slot]
+        keys_new, base_new = lsh(sig_new, new_ub)
+        base_new_old = torch.where(base_new >= 0, old_slot[base_new.clamp(min=0)], base_new)
+        old_base = base_old[old_slot]
+        reuse = old_base == base_new_old
+        clock.lap("lsh")
+    else:
+        base_new_old = old_base = torch.full((u_new,), -1, dtype=torch.int64, device=dev)
+        reuse = torch.ones(u_new, dtype=torch.bool, device=dev)
+
+    j_idx = torch.arange(u_new, dtype=torch.int64, device=dev)
+    own_old = t(np.concatenate(own_l) if own_l else np.zeros(0, np.int64), torch.int64)
+    promoted = plan["old_chunk"][plan["uniq_ids"]] != own_old[old_slot]
+    shard_old = torch.searchsorted(t(sbase, torch.int64), old_slot, right=True) - 1
+    shard_new = torch.searchsorted(t(np.asarray(new_ub, np.int64), torch.int64), j_idx, right=True) - 1
+    migrated = shard_old != shard_new
+    ob_new = torch.where(old_base >= 0, new_slot_of_old[old_base.clamp(min=0)], old_base)
+    base_gone = (old_base >= 0) & ((ob_new < 0) | (ob_new > j_idx))
+    redo = ~reuse
+    enc = redo.nonzero().flatten()
+    n_enc = int(enc.numel())
+
+    # --- L1: re-encode (one hmse_l1_inflate over the dictionary closure across shards, hmse_l1_deflate by chunk id)
+    src1 = None
+    kind_e = torch.zeros(0, dtype=torch.uint8, device=dev)
+    off_e = torch.zeros(1, dtype=torch.int64, device=dev)
+    if n_enc:
+        slots_e = old_slot[enc]
+        bases_e = base_new_old[enc]
+        if raw_all is not None:
+            data, dcuts = raw_all, raw_off_all
+            cid, bid = slots_e, bases_e
+        else:
+            se, be = slots_e.cpu().numpy(), bases_e.cpu().numpy()
+            need = rd.closure(np.concatenate([se, be[be >= 0]]))
+            data, dcuts = decode(need)
+            clock.lap("decode")
+            need_d = t(need, torch.int64)
+            cid = torch.searchsorted(need_d, slots_e)
+            bid = torch.where(bases_e >= 0, torch.searchsorted(need_d, bases_e.clamp(min=0)), bases_e)
+        src1, off_e, kind_e = ops.l1_deflate(data, dcuts, cfg, cid, bid, base_is_chunk_id=True)
+        del data, dcuts
+        clock.lap("reencode")
+    raw_all = raw_off_all = None
+
+    # --- gather: every shard's dense streams back to back (one launch), each shard's a slice
+    rec_e = torch.full((u_new,), n_enc, dtype=torch.int64, device=dev)
+    rec_e[enc] = torch.arange(n_enc, dtype=torch.int64, device=dev)
+    z64 = torch.zeros(1, dtype=torch.int64, device=dev)
+    e_off, e_len = torch.cat([off_e[:-1], z64]), torch.cat([off_e[1:] - off_e[:-1], z64])
+    e_kind = torch.cat([kind_e, torch.zeros(1, dtype=torch.uint8, device=dev)])
+    s_off_old, s_len_old = t(rd.stream_off, torch.int64), t(rd.stream_len, torch.int64)
+    src_off = torch.where(redo, e_off[rec_e], s_off_old[old_slot])
+    s_len = torch.where(redo, e_len[rec_e], s_len_old[old_slot])
+    kind_new = torch.where(redo, e_kind[rec_e], kind_old[old_slot])
+    stream_off = torch.zeros(u_new + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(s_len, 0, out=stream_off[1:])
+    streams = ops.record_gather(rd.blob, src1, src_off, redo.to(torch.uint8), stream_off)
+    clock.lap("gather", nbytes=2 * int(streams.numel()))
+    del rd, src1
+
+    # --- pack: N ShardResults of the fresh sharded ingest, through the unchanged packing code
+    parts = []
+    for i in range(N):
+        a, e, ua, ue = new_cb[i], new_cb[i + 1], new_ub[i], new_ub[i + 1]
+        cuts_i = torch.zeros(e - a + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(lens_new[a:e], 0, out=cuts_i[1:])
+        so_i = stream_off[ua: ue + 1] - stream_off[ua]
+        base_i = bg = None
+        if use_l4:
+            bg = base_new[ua:ue]
+            base_i = torch.where((bg >= ua) & (bg < ue), bg - ua, torch.full_like(bg, -1))
+        res = ingest.ShardResult(int(lens_new[a:e].sum().item()) if e > a else 0, cuts_i, plan["digests"][a:e], a, n_new, plan["first_occ"][a:e],
+                                 plan["refcount"][a:e], plan["uniq_ids"][ua:ue] - a, sig_new[ua:ue] if use_l4 else None,
+                                 keys_new[ua:ue] if use_l4 else None, base_i, streams[int(stream_off[ua]): int(stream_off[ue])], so_i,
+                                 kind_new[ua:ue], shard_bases=new_cb[:N])
+        if use_l4 and global_l4:
+            res.base_global, res.u_base, res.u_bases = bg, ua, new_ub[:N]
+        parts.append(manifest.build_manifest(res, i, N))
+    out = manifest.merge_manifests(parts)
+    clock.lap("pack")
+    sides = None
+    if use_l4:
+        sides = [bandtable.write_band_tables_device(keys_new[new_ub[i]: new_ub[i + 1]], cfg.band_bits, signatures=sig_new[new_ub[i]: new_ub[i + 1]])
+                 for i in range(N)]
+        clock.lap("sidecar")
+    changed = redo & (kind_new != kind_old[old_slot])
+    stats.update(_counts(n_new, u_new, u_new - n_enc, int((redo & promoted).sum()), int((redo & ~promoted & base_gone).sum()),
+                         int((redo & ~promoted & ~base_gone).sum()), int(promoted.sum()), int(changed.sum())))
+    stats["blob_bytes_after"] = int(sum(m.blob.size for m in out.shards))
+    stats["records_migrated"] = int(migrated.sum())
+    stats["per_shard"] = [{"chunks_after": new_cb[i + 1] - new_cb[i], "stored_after": new_ub[i + 1] - new_ub[i]} for i in range(N)]
+    return out, sides, stats
 
 
 def _counts(n_new, u_new, reused, r_prom, r_gone, r_changed, promoted, kind_changed) -> dict:

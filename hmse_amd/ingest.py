@@ -238,8 +238,11 @@ def ingest_shards_local(shards: list, cfg: IngestConfig, global_l4: bool = False
     pre = []
     for i, d in enumerate(shards):
         so = seg_offs[i] if seg_offs is not None else None
-        cuts = ops.l2_cdc(d, cfg, so) if cfg.layers & LAYER_L2 else \
-            fixed_cuts(d.numel(), cfg, so if so is not None else ops.segment_offsets(d.numel(), cfg.seg_size, d.device))
+        if d.numel() == 0:          # a zero-byte shard (e.g. one that garbage collection emptied): no chunk, one empty segment
+            cuts = torch.zeros(1, dtype=torch.int64, device=d.device)
+        else:
+            cuts = ops.l2_cdc(d, cfg, so) if cfg.layers & LAYER_L2 else \
+                fixed_cuts(d.numel(), cfg, so if so is not None else ops.segment_offsets(d.numel(), cfg.seg_size, d.device))
         pre.append((cuts, ops.l3_sha256(d, cuts) if cfg.layers & LAYER_L3 else None))
     if not cfg.layers & LAYER_L3:
         return [ingest_shard(d, cfg, pre=p) for d, p in zip(shards, pre)]

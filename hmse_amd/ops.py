@@ -561,3 +561,37 @@ def stream_piece_encode_g(data, piece_bytes, cap_bytes, cfg, state, gstate, cuts
     rc = _lib.hip_lib().hmse_stream_piece_encode_g(_ptr(data), data.numel(), int(piece_bytes), int(cap_bytes), C.byref(c), _ptr(state), _ptr(gstate),
                                                   _ptr(cuts_all), _ptr(kind_all), _ptr(stream_off_all), _ptr(out), out.numel(), ws.data_ptr(), ws.numel(), _stream())
     _check(rc, "hmse_stream_piece_encode_g")
+
+
+def band_tables_write(keys: torch.Tensor, sig: torch.Tensor | None, band_bits: int) -> torch.Tensor:
+    """hmse_band_tables_write: the band-table sidecar of `keys` (int32 [n, bands], uint32 bits) and, when given, the signatures
+    (int32 [n, n_hashes]) -> a device uint8 tensor, byte for byte bandtable.write_band_tables().  One host sync (the size)."""
+    _require_gpu(keys, "keys")
+    if keys.dim() != 2 or keys.dtype != torch.int32:
+        raise HmseError(-1, "band_tables_write: keys must be int32 [n, bands]")
+    n, bands = keys.shape
+    nh = 0
+    if sig is not None:
+        _require_gpu(sig, "sig")
+        if sig.dim() != 2 or sig.dtype != torch.int32 or sig.shape[0] != n:
+            raise HmseError(-1, "band_tables_write: sig must be int32 [n, n_hashes]")
+        nh = int(sig.shape[1])
+    if n >= 1 << 24:
+        raise ValueError("3-byte chunk ids hold at most 16 777 215 stored chunks (README.md:1943)")
+    if not 1 <= band_bits <= 16:
+        raise ValueError("band_hash is a u16")
+    dev = keys.device
+    lib = _lib.hip_lib()
+    cap = int(lib.hmse_band_tables_bound(n, bands, band_bits, nh))
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    meta = torch.zeros(2, dtype=torch.int64, device=dev)      # [out_bytes, status]
+    ws = _ws(lib.hmse_band_tables_workspace_bytes(n), dev)
+    rc = lib.hmse_band_tables_write(_ptr(keys) if n else None, n, bands, band_bits, _ptr(sig) if n and nh else None, nh, out.data_ptr(), cap,
+                                    meta.data_ptr(), meta.data_ptr() + 8, ws.data_ptr(), ws.numel(), _stream())
+    _check(rc, "hmse_band_tables_write")
+    size, st = (int(v) for v in meta.tolist())
+    if st & 0xFFFFFFFF:
+        raise HmseError(-2, f"hmse_band_tables_write device status {st & 0xFFFFFFFF:#x}")
+    if size > cap:
+        raise HmseError(-2, f"hmse_band_tables_write: {size} bytes written into {cap}")
+    return out[:size]

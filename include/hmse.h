@@ -467,6 +467,23 @@ int hmse_record_gather(const uint8_t* src0, uint64_t src0_bytes, const uint8_t* 
                        uint32_t* status, void* stream);
 
 /*
+ * L4 band-table sidecar (hmse_amd/bandtable.py write_band_tables, byte for byte): file header, per band the header count, the
+ * {band_hash u16, count u16} bucket headers in ascending band_hash order (a bucket of more than 65535 ids continues in further
+ * headers) and the 3-byte ids, ascending inside a bucket; with n_hashes > 0 the "HMSESIGS" section (band keys, signatures).
+ *   band_keys DEVICE u32[n][bands]; sig DEVICE u32[n][n_hashes] (may be NULL when n == 0 or n_hashes == 0)
+ *   out       DEVICE u8[out_cap], out_cap >= hmse_band_tables_bound(n, bands, band_bits, n_hashes)
+ *   out_bytes DEVICE u64[1] out: the exact size written
+ *   status    DEVICE u32[1]: bit0 = n >= 2^24 (3-byte ids), bit1 = band_bits outside 1..16, bit2 = out_cap too small
+ *   ws        hmse_band_tables_workspace_bytes(n) bytes
+ * Buckets are built by a stable LSD radix sort per band: the bytes do not depend on the order of any atomic operation.
+ */
+uint64_t hmse_band_tables_bound(uint64_t n, uint32_t bands, uint32_t band_bits, uint32_t n_hashes);
+size_t hmse_band_tables_workspace_bytes(uint64_t n);
+int hmse_band_tables_write(const uint32_t* band_keys, uint64_t n, uint32_t bands, uint32_t band_bits, const uint32_t* sig,
+                           uint32_t n_hashes, uint8_t* out, uint64_t out_cap, uint64_t* out_bytes, uint32_t* status, void* ws,
+                           size_t ws_bytes, void* stream);
+
+/*
  * Diagnostics (bench.py's roofline leg): when enabled, every entry point brackets its DOMINANT
  * kernel launch with a HIP event pair on the caller's stream.  hmse_profile_read() waits for the
  * recorded events (a host sync — never call it inside a capture), adds their durations to the
