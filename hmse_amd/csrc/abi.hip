@@ -10,6 +10,8 @@ size_t hmse_l1_deflate_workspace_bytes_impl(uint64_t n_chunks, const hmse_cfg* c
 size_t hmse_l1_inflate_workspace_bytes_impl(uint64_t n_chunks);
 size_t hmse_manifest_pack_workspace_bytes_impl(uint64_t n_chunks);
 size_t hmse_gc_plan_workspace_bytes_impl(uint64_t n_chunks);
+size_t hmse_l4_index_workspace_bytes_impl(uint64_t n);
+size_t hmse_l4_query_workspace_bytes_impl(uint64_t n_q, const hmse_cfg* cfg);
 
 extern "C" void hmse_cfg_default(hmse_cfg* c) {
   memset(c, 0, sizeof *c);
@@ -95,6 +97,8 @@ extern "C" size_t hmse_workspace_bytes(int stage, uint64_t n, const hmse_cfg* cf
     case HMSE_STAGE_READ_ASSEMBLE: return 256;
     case HMSE_STAGE_MANIFEST_PACK: return hmse_manifest_pack_workspace_bytes_impl(n);
     case HMSE_STAGE_GC_PLAN: return hmse_gc_plan_workspace_bytes_impl(n);
+    case HMSE_STAGE_L4_INDEX: return hmse_l4_index_workspace_bytes_impl(n);
+    case HMSE_STAGE_L4_QUERY: return hmse_l4_query_workspace_bytes_impl(n, cfg);
     default: return 0;
   }
 }

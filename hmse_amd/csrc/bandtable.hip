@@ -313,3 +313,58 @@ extern "C" int hmse_band_tables_write(const uint32_t* band_keys, uint64_t n, uin
   HMSE_LAUNCH_CHECK();
   return HMSE_OK;
 }
+
+// ---- near-duplicate index (hmse_l4_index_build, include/hmse.h): per band the stored ids sorted stably by the whole 32-bit key —
+// the kernels above with mask 0xFFFFFFFF and four 8-bit passes.
+size_t hmse_l4_index_workspace_bytes_impl(uint64_t n) {
+  const uint64_t nt = bt_blocks(n);
+  // key/id ping-pong partner (2 x n), histogram (256 per tile), block sums, meta
+  return 2 * hmse_align_up(4 * (n + 1), 256) + hmse_align_up(4 * 256 * nt, 256) + hmse_align_up(4 * (bt_blocks(256 * nt) + 1), 256) +
+         hmse_align_up(8 * BT_META, 256) + 256;
+}
+
+// ids [0, n) sorted stably by keys[i * stride + col] -> (out_keys, out_ids); an even pass count leaves the result there
+static int bt_sort_u32(const uint32_t* keys, uint64_t n, uint32_t stride, uint32_t col, uint32_t* out_keys, uint32_t* out_ids, void* ws,
+                       size_t ws_bytes, hipStream_t stream) {
+  if (n == 0) return HMSE_OK;
+  const uint64_t nt = bt_blocks(n);
+  WsCarver c(ws, ws_bytes);
+  uint32_t* bkt = c.take<uint32_t>(n + 1);
+  uint32_t* ids = c.take<uint32_t>(n + 1);
+  uint32_t* hist = c.take<uint32_t>(256 * nt);
+  uint32_t* bsum = c.take<uint32_t>(bt_blocks(256 * nt) + 1);
+  uint64_t* meta = c.take<uint64_t>(BT_META);
+  if (!c.ok()) return HMSE_ENOSPC;
+  bt_load_kernel<<<dim3((uint32_t)nt), dim3(BT_NT), 0, stream>>>(keys, n, stride, col, 0xFFFFFFFFu, out_keys, out_ids);
+  HMSE_LAUNCH_CHECK();
+  uint32_t *bi = out_keys, *ii = out_ids, *bo = bkt, *io = ids;
+  for (int p = 0; p < 4; p++) {
+    bt_hist_kernel<<<dim3((uint32_t)nt), dim3(BT_NT), 0, stream>>>(bi, n, 8u * p, nt, hist);
+    HMSE_LAUNCH_CHECK();
+    int rc = bt_scan(hist, 256 * nt, bsum, meta + BT_HIST, stream);
+    if (rc != HMSE_OK) return rc;
+    bt_scatter_kernel<<<dim3((uint32_t)nt), dim3(BT_NT), 0, stream>>>(bi, ii, n, 8u * p, nt, hist, bo, io);
+    HMSE_LAUNCH_CHECK();
+    uint32_t* tb = bi; bi = bo; bo = tb;
+    uint32_t* ti = ii; ii = io; io = ti;
+  }
+  return HMSE_OK;
+}
+
+extern "C" int hmse_l4_index_build(const uint32_t* keys, uint64_t n, uint32_t bands, uint32_t* sorted_keys, uint32_t* sorted_ids,
+                                   uint32_t* status, void* ws, size_t ws_bytes, void* stream_) {
+  if (!status || bands == 0 || bands > 16 || (bands & (bands - 1))) return HMSE_EINVAL;
+  if (n >= (1ull << 32)) return HMSE_EINVAL;
+  if (n && (!keys || !sorted_keys || !sorted_ids)) return HMSE_EINVAL;
+  if (n && (!ws || ws_bytes < hmse_l4_index_workspace_bytes_impl(n))) return HMSE_ENOSPC;
+  hipStream_t stream = (hipStream_t)stream_;
+  (void)hipGetLastError();
+  HMSE_FILL(status, 0, 4, stream);
+  PROF_BEGIN(HMSE_STAGE_L4_INDEX, stream);
+  for (uint32_t b = 0; b < bands && n; b++) {
+    int rc = bt_sort_u32(keys, n, bands, b, sorted_keys + (uint64_t)b * n, sorted_ids + (uint64_t)b * n, ws, ws_bytes, stream);
+    if (rc != HMSE_OK) return rc;
+  }
+  PROF_END(HMSE_STAGE_L4_INDEX, stream);
+  return HMSE_OK;
+}

@@ -17,6 +17,8 @@ from .config import IngestConfig
 STAGE_L2, STAGE_SHA, STAGE_DEDUP, STAGE_MINHASH, STAGE_LSH, STAGE_DEFLATE = 2, 3, 4, 5, 6, 7
 STAGE_INFLATE, STAGE_ASSEMBLE, STAGE_MANIFEST = 16, 17, 18
 STAGE_GC_PLAN, STAGE_RECORD_GATHER = 24, 25
+STAGE_L4_INDEX, STAGE_L4_QUERY = 26, 27
+QUERY_EXCLUDE_SELF = 1
 
 
 class HmseError(RuntimeError):
@@ -595,3 +597,62 @@ def band_tables_write(keys: torch.Tensor, sig: torch.Tensor | None, band_bits: i
     if size > cap:
         raise HmseError(-2, f"hmse_band_tables_write: {size} bytes written into {cap}")
     return out[:size]
+
+
+def search_cfg(cfg: IngestConfig, bands: int) -> IngestConfig:
+    """`cfg` with the search banding bands x (128 / bands); ValueError unless hmse_cfg_validate accepts it (bands in 1, 2, 4, 8, 16)."""
+    if int(bands) not in (1, 2, 4, 8, 16) or cfg.n_hashes != 128:
+        raise ValueError(f"a search banding is bands x rows = 128 with bands in (1, 2, 4, 8, 16), got bands={bands} (n_hashes {cfg.n_hashes})")
+    sc = cfg.with_(bands=int(bands), rows=128 // int(bands))
+    c = sc.to_c()
+    if _lib.hip_lib().hmse_cfg_validate(C.byref(c)) != 0:
+        raise ValueError(f"configuration {sc} is not supported by the device path")
+    return sc
+
+
+def l4_index_build(keys: torch.Tensor):
+    """hmse_l4_index_build: band keys int32 [n, bands] (uint32 bits) -> (sorted_keys, sorted_ids), int32 [bands, n] each: per band the
+    ids sorted stably by their key in uint32 order."""
+    _require_gpu(keys, "keys")
+    if keys.dim() != 2 or keys.dtype != torch.int32:
+        raise HmseError(-1, "l4_index_build: keys must be int32 [n, bands]")
+    n, bands = keys.shape
+    dev = keys.device
+    sk = torch.empty((bands, n), dtype=torch.int32, device=dev)
+    si = torch.empty((bands, n), dtype=torch.int32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = _ws(workspace_bytes(STAGE_L4_INDEX, n, search_cfg(IngestConfig(), bands)) if bands in (1, 2, 4, 8, 16) else 256, dev)
+    rc = _lib.hip_lib().hmse_l4_index_build(_ptr(keys) if n else None, n, bands, sk.data_ptr() if n else None, si.data_ptr() if n else None,
+                                            status.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    _check(rc, "hmse_l4_index_build")
+    return sk, si
+
+
+def l4_query(sig_q: torch.Tensor, keys_q: torch.Tensor, sig_s: torch.Tensor, sorted_keys: torch.Tensor, sorted_ids: torch.Tensor,
+             cfg: IngestConfig, top_k: int = 8, min_score: int = 0, exclude_self: bool = False):
+    """hmse_l4_query under the banding of `cfg` -> (ids int64 [q, top_k] (-1 padding), scores int32 [q, top_k] (0 padding),
+    n_hits int32 [q], n_candidates int64 [q]).  One host sync (the status word)."""
+    for t, name in ((sig_q, "sig_q"), (keys_q, "keys_q"), (sig_s, "sig_s"), (sorted_keys, "sorted_keys"), (sorted_ids, "sorted_ids")):
+        _require_gpu(t, name)
+    n_q, n_s = sig_q.shape[0], sig_s.shape[0]
+    if sig_q.shape[1:] != (128,) or sig_s.shape[1:] != (128,) or keys_q.shape != (n_q, cfg.bands) or \
+            sorted_keys.shape != (cfg.bands, n_s) or sorted_ids.shape != (cfg.bands, n_s):
+        raise HmseError(-1, "l4_query: shapes of the signatures, keys and index do not agree with each other or with the banding")
+    dev = sig_q.device
+    ids = torch.empty((n_q, int(top_k)), dtype=torch.int64, device=dev)
+    scores = torch.empty((n_q, int(top_k)), dtype=torch.int32, device=dev)
+    n_hits = torch.empty(n_q, dtype=torch.int32, device=dev)
+    n_cand = torch.empty(n_q, dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    c = cfg.to_c()
+    ws = _ws(workspace_bytes(STAGE_L4_QUERY, n_q, cfg), dev)
+    q = lambda t: _ptr(t) if n_q else None
+    s = lambda t: _ptr(t) if n_s else None
+    rc = _lib.hip_lib().hmse_l4_query(q(sig_q), q(keys_q), n_q, s(sig_s), n_s, s(sorted_keys), s(sorted_ids), C.byref(c), int(top_k),
+                                      int(min_score), QUERY_EXCLUDE_SELF if exclude_self else 0, q(ids), q(scores), q(n_hits), q(n_cand),
+                                      status.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    _check(rc, "hmse_l4_query")
+    st = int(status.item())
+    if st:
+        raise HmseError(-1, f"hmse_l4_query device status {st:#x}: an index entry names an id outside the stored signatures")
+    return ids, scores, n_hits, n_cand

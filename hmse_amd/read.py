@@ -207,6 +207,16 @@ def dependency_order(base: np.ndarray):
     return order, new_of_old
 
 
+def chunk_slots(shards: list):
+    """The chunk map of a merged store's shards in (shard, local) order -> (global stored slot of every chunk, int64 — a POINTER's
+    entry names its target's shard and slot, so the slot is `shard's first slot + slot` —, the chunks' raw lengths, int64)."""
+    if not shards:
+        return np.zeros(0, np.int64), np.zeros(0, np.int64)
+    sb = np.cumsum([0] + [len(m.index) for m in shards])
+    slot = np.concatenate([sb[m.chunk_map["shard"].astype(np.int64)] + m.chunk_map["slot"].astype(np.int64) for m in shards])
+    return slot, np.concatenate([m.chunk_map["raw_length"].astype(np.int64) for m in shards])
+
+
 def read_store(store: Store, device, verify: bool = True) -> torch.Tensor:
     """A sharded store (one Manifest per shard, cross-shard pointers resolved by manifest.merge_manifests) -> the
     original corpus in global chunk order, decoded on `device`: the records of all shards are inflated in one call, then
@@ -244,9 +254,7 @@ def read_store(store: Store, device, verify: bool = True) -> torch.Tensor:
                                                  stream_len=t(o(cat("stream_len")), torch.int32))
     else:
         raw_all = torch.empty(0, dtype=torch.uint8, device=device); raw_off_all = torch.zeros(1, dtype=torch.int64, device=device)
-    slot_g = np.concatenate([sb[m.chunk_map["shard"].astype(np.int64)] + m.chunk_map["slot"].astype(np.int64) for m in store.shards]) \
-        if store.shards else np.zeros(0, np.int64)
-    lens = np.concatenate([m.chunk_map["raw_length"].astype(np.int64) for m in store.shards]) if store.shards else np.zeros(0, np.int64)
+    slot_g, lens = chunk_slots(store.shards)
     from .manifest import stream_order
     perm = stream_order(store.shards)          # a multi-rank stream's store: the original bytes are the chunks in stream order
     if perm is not None:
@@ -310,9 +318,7 @@ class StoreReader:
             self.kind, self.stream_off, self.stream_len, self.raw_len = self.kind[order], self.stream_off[order], self.stream_len[order], self.raw_len[order]
         blobs = [t(m.blob, torch.uint8) for m in shards if m.blob.size]
         self.blob = blobs[0] if len(blobs) == 1 else torch.cat(blobs) if blobs else torch.zeros(1, dtype=torch.uint8, device=device)
-        self.slot = np.concatenate([sb[m.chunk_map["shard"].astype(np.int64)] + m.chunk_map["slot"].astype(np.int64) for m in shards]) \
-            if shards else np.zeros(0, np.int64)
-        lens = np.concatenate([m.chunk_map["raw_length"].astype(np.int64) for m in shards]) if shards else np.zeros(0, np.int64)
+        self.slot, lens = chunk_slots(shards)
         from .manifest import stream_order
         perm = stream_order(shards)             # a multi-rank stream's store: requests address the stream, whose chunks interleave the shards
         if perm is not None:

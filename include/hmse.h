@@ -53,7 +53,10 @@ enum {
   HMSE_STAGE_MANIFEST_PACK = 18,
   /* garbage collection of dropped segments (hmse_gc_plan; hmse_record_gather's profiling slot) */
   HMSE_STAGE_GC_PLAN       = 24,
-  HMSE_STAGE_RECORD_GATHER = 25
+  HMSE_STAGE_RECORD_GATHER = 25,
+  /* near-duplicate search over the stored chunks' signatures (hmse_l4_index_build: n = stored chunks; hmse_l4_query: n = queries) */
+  HMSE_STAGE_L4_INDEX      = 26,
+  HMSE_STAGE_L4_QUERY      = 27
 };
 
 /* layer-enable mask == the reference's ablation matrix / degradation modes
@@ -482,6 +485,44 @@ size_t hmse_band_tables_workspace_bytes(uint64_t n);
 int hmse_band_tables_write(const uint32_t* band_keys, uint64_t n, uint32_t bands, uint32_t band_bits, const uint32_t* sig,
                            uint32_t n_hashes, uint8_t* out, uint64_t out_cap, uint64_t* out_bytes, uint32_t* status, void* ws,
                            size_t ws_bytes, void* stream);
+
+/*
+ * Near-duplicate search (hmse_amd/similarity.py) over the MinHash signatures of the stored chunks.  A search banding is any cfg
+ * that hmse_cfg_validate accepts (bands x rows == 128, bands in {1, 2, 4, 8, 16}); band b of a signature is hashes
+ * [b rows, (b+1) rows).  Stored ids and query ids are row numbers of sig_s and sig_q.
+ *
+ * Index: per band, the stored ids sorted stably by their 32-bit band key (ids ascending inside equal keys), by the LSD radix sort
+ * of hmse_band_tables_write (four 8-bit passes).
+ *   keys        DEVICE u32[n][bands] the stored chunks' band keys under the search banding (hmse_l4_lsh)
+ *   sorted_keys DEVICE u32[bands][n], sorted_ids DEVICE u32[bands][n] out
+ *   status      DEVICE u32[1] out: 0 (no device-side failure exists; kept for the calling convention)
+ *   ws          hmse_workspace_bytes(HMSE_STAGE_L4_INDEX, n, cfg) bytes
+ * HMSE_EINVAL before any launch: bands not a power of two <= 16, n >= 2^32, a NULL pointer (keys / sorted_* may be NULL when n == 0).
+ */
+int hmse_l4_index_build(const uint32_t* keys, uint64_t n, uint32_t bands, uint32_t* sorted_keys, uint32_t* sorted_ids,
+                        uint32_t* status, void* ws, size_t ws_bytes, void* stream);
+
+/*
+ * Query: stored id c is a CANDIDATE of query i iff some band of sig_q[i] equals the same band of sig_s[c], word by word (a band
+ * key only routes the search: equal keys with different rows are no candidate).  score(i, c) = number of equal hashes (of 128;
+ * the Jaccard estimate is score / 128).  Result of query i: its candidates with score >= min_score, by score descending, then
+ * id ascending, the first top_k.
+ *   sig_q   DEVICE u32[n_q][128];  keys_q DEVICE u32[n_q][bands] (hmse_l4_lsh under cfg)
+ *   sig_s   DEVICE u32[n_s][128];  sorted_keys / sorted_ids from hmse_l4_index_build under the same banding
+ *   cfg     the search banding (bands, rows)
+ *   top_k   1..64;  min_score 0..128;  flags HMSE_QUERY_EXCLUDE_SELF: stored id i is no candidate of query i (self-join, sig_q == sig_s)
+ *   out_ids DEVICE i64[n_q][top_k] (-1 padding);  out_scores DEVICE i32[n_q][top_k] (0 padding)
+ *   n_hits  DEVICE u32[n_q] ids returned;  n_candidates DEVICE u64[n_q] candidates before min_score and top_k
+ *   status  DEVICE u32[1] out: bit0 = an index entry names an id >= n_s (it is skipped)
+ *   ws      hmse_workspace_bytes(HMSE_STAGE_L4_QUERY, n_q, cfg) bytes
+ * HMSE_EINVAL before any launch: top_k or min_score out of range, an unsupported banding, unknown flags, n_q or n_s >= 2^32,
+ * a NULL pointer (the query-side pointers may be NULL when n_q == 0, the stored-side ones when n_s == 0).
+ */
+enum { HMSE_QUERY_EXCLUDE_SELF = 1u };
+int hmse_l4_query(const uint32_t* sig_q, const uint32_t* keys_q, uint64_t n_q, const uint32_t* sig_s, uint64_t n_s,
+                  const uint32_t* sorted_keys, const uint32_t* sorted_ids, const hmse_cfg* cfg, uint32_t top_k, uint32_t min_score,
+                  uint32_t flags, int64_t* out_ids, int32_t* out_scores, uint32_t* n_hits, uint64_t* n_candidates, uint32_t* status,
+                  void* ws, size_t ws_bytes, void* stream);
 
 /*
  * Diagnostics (bench.py's roofline leg): when enabled, every entry point brackets its DOMINANT
