@@ -12,6 +12,7 @@ size_t hmse_manifest_pack_workspace_bytes_impl(uint64_t n_chunks);
 size_t hmse_gc_plan_workspace_bytes_impl(uint64_t n_chunks);
 size_t hmse_l4_index_workspace_bytes_impl(uint64_t n);
 size_t hmse_l4_query_workspace_bytes_impl(uint64_t n_q, const hmse_cfg* cfg);
+size_t hmse_scrub_attribute_workspace_bytes_impl(uint64_t n_records, uint64_t n_chunks);
 
 extern "C" void hmse_cfg_default(hmse_cfg* c) {
   memset(c, 0, sizeof *c);
@@ -99,6 +100,8 @@ extern "C" size_t hmse_workspace_bytes(int stage, uint64_t n, const hmse_cfg* cf
     case HMSE_STAGE_GC_PLAN: return hmse_gc_plan_workspace_bytes_impl(n);
     case HMSE_STAGE_L4_INDEX: return hmse_l4_index_workspace_bytes_impl(n);
     case HMSE_STAGE_L4_QUERY: return hmse_l4_query_workspace_bytes_impl(n, cfg);
+    case HMSE_STAGE_SCRUB_RECORDS: return 0;      /* takes no workspace */
+    case HMSE_STAGE_SCRUB_ATTRIBUTE: return hmse_scrub_attribute_workspace_bytes_impl(n, n);
     default: return 0;
   }
 }

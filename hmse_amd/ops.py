@@ -18,6 +18,7 @@ STAGE_L2, STAGE_SHA, STAGE_DEDUP, STAGE_MINHASH, STAGE_LSH, STAGE_DEFLATE = 2, 3
 STAGE_INFLATE, STAGE_ASSEMBLE, STAGE_MANIFEST = 16, 17, 18
 STAGE_GC_PLAN, STAGE_RECORD_GATHER = 24, 25
 STAGE_L4_INDEX, STAGE_L4_QUERY = 26, 27
+STAGE_SCRUB_RECORDS, STAGE_SCRUB_ATTRIBUTE = 28, 29
 QUERY_EXCLUDE_SELF = 1
 
 
@@ -656,3 +657,54 @@ def l4_query(sig_q: torch.Tensor, keys_q: torch.Tensor, sig_s: torch.Tensor, sor
     if st:
         raise HmseError(-1, f"hmse_l4_query device status {st:#x}: an index entry names an id outside the stored signatures")
     return ids, scores, n_hits, n_cand
+
+
+def scrub_records(blob: torch.Tensor, rec_shard: torch.Tensor, shard_blob: torch.Tensor, shard_slot: torch.Tensor, lba_unit: torch.Tensor,
+                  lba: torch.Tensor, rec_len: torch.Tensor, kind: torch.Tensor, remote: torch.Tensor, sorted_lba: torch.Tensor,
+                  sorted_slot: torch.Tensor, steps: int, meta: torch.Tensor):
+    """hmse_scrub_records: per record (global slot) its STRUCTURE / HEADER flags and resolved dictionary, plus the non-zero padding
+    bytes of the blobs.  u32 arrays travel as int32.  Returns (status uint8[n], dict int64[n], padding int64[1]) on the device."""
+    tensors = (blob, rec_shard, shard_blob, shard_slot, lba_unit, lba, rec_len, kind, remote, sorted_lba, sorted_slot, meta)
+    for t, nm in zip(tensors, ("blob", "rec_shard", "shard_blob", "shard_slot", "lba_unit", "lba", "rec_len", "kind", "remote", "sorted_lba",
+                               "sorted_slot", "meta")):
+        _require_gpu(t, nm)
+    dev = blob.device
+    n = lba.numel()
+    n_shards = lba_unit.numel()
+    if any(t.numel() != n for t in (rec_shard, rec_len, kind, remote, sorted_lba, sorted_slot, meta)) or shard_blob.numel() != n_shards + 1 \
+            or shard_slot.numel() != n_shards + 1:
+        raise HmseError(-1, "scrub_records: per-record / per-shard arrays do not match")
+    status = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+    dict_ = torch.full((max(n, 1),), -1, dtype=torch.int64, device=dev)
+    pad = torch.zeros(1, dtype=torch.int64, device=dev)
+    if n_shards == 0:
+        return status[:0], dict_[:0], pad
+    p = lambda t: _ptr(t) if t.numel() else None
+    rc = _lib.hip_lib().hmse_scrub_records(_ptr(blob), blob.numel(), n, n_shards, p(rec_shard), p(shard_blob), p(shard_slot), p(lba_unit),
+                                           p(lba), p(rec_len), p(kind), p(remote), p(sorted_lba), p(sorted_slot), int(steps), p(meta), _ptr(status),
+                                           _ptr(dict_), _ptr(pad), _stream())
+    _check(rc, "hmse_scrub_records")
+    return status[:n], dict_[:n], pad
+
+
+def scrub_attribute(status: torch.Tensor, dict_: torch.Tensor, ok: torch.Tensor, got: torch.Tensor, want: torch.Tensor, check_digest: bool,
+                    chunk_slot: torch.Tensor, cuts: torch.Tensor, max_depth_log2: int) -> dict:
+    """hmse_scrub_attribute: final record flags and roots, chunk roots, per-root losses and the damaged ranges.  Returns device
+    tensors {status, root, chunk_root, root_records, root_chunks, root_bytes, ranges (u64[2 (n_chunks / 2 + 1)]), counts (u64[8])}."""
+    for t, nm in ((status, "status"), (dict_, "dict"), (ok, "ok"), (got, "got"), (want, "want"), (chunk_slot, "chunk_slot"), (cuts, "cuts")):
+        _require_gpu(t, nm)
+    dev = cuts.device
+    n, nc = status.numel(), chunk_slot.numel()
+    if dict_.numel() != n or ok.numel() != n or cuts.numel() != nc + 1 or (check_digest and (got.shape != (n, 32) or want.shape != (n, 32))):
+        raise HmseError(-1, "scrub_attribute: per-record / per-chunk arrays do not match")
+    e = lambda k, dt=torch.int64: torch.zeros(max(k, 1), dtype=dt, device=dev)
+    out = {"status": e(n, torch.uint8), "root": e(n), "chunk_root": e(nc), "root_records": e(n), "root_chunks": e(n), "root_bytes": e(n),
+           "ranges": e(2 * (nc // 2 + 1)), "counts": e(8)}
+    ws = _ws(workspace_bytes(STAGE_SCRUB_ATTRIBUTE, max(n, nc), IngestConfig()), dev)
+    p = lambda t, keep=True: _ptr(t) if keep and t.numel() else None
+    rc = _lib.hip_lib().hmse_scrub_attribute(n, p(status), p(dict_), p(ok), p(got, check_digest), p(want, check_digest), 1 if check_digest else 0,
+                                             int(max_depth_log2), nc, p(chunk_slot), _ptr(cuts), _ptr(out["status"]), _ptr(out["root"]),
+                                             _ptr(out["chunk_root"]), _ptr(out["root_records"]), _ptr(out["root_chunks"]), _ptr(out["root_bytes"]),
+                                             _ptr(out["ranges"]), _ptr(out["counts"]), ws.data_ptr(), ws.numel(), _stream())
+    _check(rc, "hmse_scrub_attribute")
+    return out

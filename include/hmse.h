@@ -56,7 +56,10 @@ enum {
   HMSE_STAGE_RECORD_GATHER = 25,
   /* near-duplicate search over the stored chunks' signatures (hmse_l4_index_build: n = stored chunks; hmse_l4_query: n = queries) */
   HMSE_STAGE_L4_INDEX      = 26,
-  HMSE_STAGE_L4_QUERY      = 27
+  HMSE_STAGE_L4_QUERY      = 27,
+  /* scrub of a store (hmse_scrub_records: no workspace, 0 bytes; hmse_scrub_attribute: n = max(records, chunks)) */
+  HMSE_STAGE_SCRUB_RECORDS   = 28,
+  HMSE_STAGE_SCRUB_ATTRIBUTE = 29
 };
 
 /* layer-enable mask == the reference's ablation matrix / degradation modes
@@ -523,6 +526,65 @@ int hmse_l4_query(const uint32_t* sig_q, const uint32_t* keys_q, uint64_t n_q, c
                   const uint32_t* sorted_keys, const uint32_t* sorted_ids, const hmse_cfg* cfg, uint32_t top_k, uint32_t min_score,
                   uint32_t flags, int64_t* out_ids, int32_t* out_scores, uint32_t* n_hits, uint64_t* n_candidates, uint32_t* status,
                   void* ws, size_t ws_bytes, void* stream);
+
+/*
+ * Scrub (hmse_amd/scrub.py): which records of a store are intact, and how far each damaged one reaches.  Records are numbered by
+ * their GLOBAL slot: shard order, then index slot order.  Per-record flags (0 = good):
+ *   STRUCTURE   the record is not inside its shard's blob, a DELTA record is shorter than its 8-byte header, its base_lba is not
+ *               the LBA of an index entry of the shard its dictionary must be on (its own; remote_bases': exactly that entry),
+ *               or a local dictionary does not come before it.  No dictionary is attributed.
+ *   STREAM      structure fine, dictionary good, the decoder rejects the record (hmse_l1_inflate ok == 0)
+ *   DIGEST      the record decodes, its SHA-256 is not the ChunkIndex sha256
+ *   DICTIONARY  the record's dictionary is damaged (its own state is unknown)
+ *   HEADER      base_length is not the dictionary's index length or delta_length is not the record length - 8 (loses nothing)
+ *   METADATA    an inconsistency of the (trusted but checked) metadata touches the record
+ */
+enum {
+  HMSE_SCRUB_STRUCTURE = 1u, HMSE_SCRUB_STREAM = 2u, HMSE_SCRUB_DIGEST = 4u, HMSE_SCRUB_DICTIONARY = 8u,
+  HMSE_SCRUB_HEADER = 16u, HMSE_SCRUB_METADATA = 32u
+};
+
+/*
+ * Scrub, records pass: one thread per record.  STRUCTURE / HEADER flags, the resolved dictionary, the non-zero padding bytes.
+ *   blob        DEVICE u8[blob_bytes]: the shards' blobs back to back;  shard_blob DEVICE u64[n_shards+1] their offsets in it
+ *   shard_slot  DEVICE u64[n_shards+1]: global slot of every shard's slot 0;  rec_shard DEVICE u32[n]: shard of every record
+ *   lba_unit    DEVICE u32[n_shards];  lba DEVICE u32[n], rec_len DEVICE u32[n]: the ChunkIndex lba / length of every record
+ *   kind        DEVICE u8[n] HMSE_KIND_* of every record (from the chunk map)
+ *   remote      DEVICE i64[n]: -1, or the global slot remote_bases names as the record's dictionary
+ *   sorted_lba  DEVICE u32[n], sorted_slot DEVICE u32[n]: per shard (the same segments as the slots) its LBAs ascending and the
+ *               local slot of each;  steps = iterations of the binary search (bit length of the largest shard's record count)
+ *   meta        DEVICE u8[n] flags found on the host (METADATA), OR-ed into status
+ *   status      DEVICE u8[n] out;  dict DEVICE i64[n] out: global slot of the dictionary, -1 none / unresolved
+ *   padding     DEVICE u64[1] out: non-zero bytes outside every record, the whole blob of a shard without records included (the
+ *               packer writes zeros)
+ * Shard bounds are clamped to blob_bytes.  Every value read from the blob is only compared, never used as an index.  No workspace
+ * (hmse_workspace_bytes(HMSE_STAGE_SCRUB_RECORDS, ...) is 0).  n may be 0 with blob_bytes > 0: only the padding is counted.
+ */
+int hmse_scrub_records(const uint8_t* blob, uint64_t blob_bytes, uint64_t n, uint32_t n_shards, const uint32_t* rec_shard,
+                       const uint64_t* shard_blob, const uint64_t* shard_slot, const uint32_t* lba_unit, const uint32_t* lba,
+                       const uint32_t* rec_len, const uint8_t* kind, const int64_t* remote, const uint32_t* sorted_lba,
+                       const uint32_t* sorted_slot, uint32_t steps, const uint8_t* meta, uint8_t* status, int64_t* dict,
+                       uint64_t* padding, void* stream);
+
+/*
+ * Scrub, attribution: from the records pass's status / dict, the decoder's ok flags and the digests of the decoded records ->
+ * final flags and roots.  root(k) = the furthest ancestor on k's dictionary chain (k included) whose own state is faulty, found by
+ * pointer doubling in max_depth_log2 + 1 rounds (the caller cuts cycles and longer chains as METADATA); -1 for a good record.
+ *   ok          DEVICE u8[n] (hmse_l1_inflate, in slot order);  got_sha / want_sha DEVICE u8[n][32] (check_digest == 0: no DIGEST)
+ *   chunk_slot  DEVICE i64[n_chunks]: global slot of every chunk in corpus (stream) order, -1 = an inconsistent map entry
+ *   cuts        DEVICE u64[n_chunks+1]: byte offset of every chunk
+ *   status_out  DEVICE u8[n]; root DEVICE i64[n]; chunk_root DEVICE i64[n_chunks] (-1 good, -2 map entry inconsistent)
+ *   root_records / root_chunks / root_bytes DEVICE u64[n]: per root (index = its slot) records, chunks and bytes lost
+ *   ranges      DEVICE u64[2 (n_chunks / 2 + 1)]: the maximal runs of damaged chunks, (offset, length) pairs
+ *   counts      DEVICE u64[8] out: ranges, damaged records, damaged chunks, damaged bytes, METADATA chunks, METADATA bytes,
+ *               HEADER records, 0
+ *   ws          hmse_workspace_bytes(HMSE_STAGE_SCRUB_ATTRIBUTE, max(n, n_chunks), cfg)
+ */
+int hmse_scrub_attribute(uint64_t n, const uint8_t* status, const int64_t* dict, const uint8_t* ok, const uint8_t* got_sha,
+                         const uint8_t* want_sha, uint32_t check_digest, uint32_t max_depth_log2, uint64_t n_chunks,
+                         const int64_t* chunk_slot, const uint64_t* cuts, uint8_t* status_out, int64_t* root, int64_t* chunk_root,
+                         uint64_t* root_records, uint64_t* root_chunks, uint64_t* root_bytes, uint64_t* ranges, uint64_t* counts,
+                         void* ws, size_t ws_bytes, void* stream);
 
 /*
  * Diagnostics (bench.py's roofline leg): when enabled, every entry point brackets its DOMINANT
