@@ -425,11 +425,18 @@ static L2Ws l2_carve(void* ws, size_t ws_bytes, uint64_t n, uint32_t n_seg, cons
   const uint64_t n_tiles = (n + L2_TILE - 1) / L2_TILE;
   r.hdr = w.take<L2Header>(1);
   r.tinfo = w.take<TileInfo>(n_tiles + 1);
-  r.cand_cap = l2_cand_cap(n, cfg);
-  r.cand = w.take<uint32_t>(r.cand_cap);
   r.seg_cnt = w.take<uint32_t>((size_t)n_seg + 1);
   r.seg_base = w.take<uint64_t>((size_t)n_seg + 1);
   r.seg_cuts = w.take<uint64_t>(n / cfg->min_size + n_seg + 2);
+  // The candidate list comes last and takes whatever the caller's workspace has left beyond the provisioned size, up to one
+  // entry per byte (no input has more): dense inputs that overflow the default list fit a larger workspace.
+  r.cand_cap = l2_cand_cap(n, cfg);
+  if (ws && ws_bytes > w.off) {
+    uint64_t fit = (uint64_t)(ws_bytes - w.off) / 256 * (256 / sizeof(uint32_t));   // whole 256-byte units: the carver rounds up
+    if (fit > n) fit = n;
+    if (fit > r.cand_cap) r.cand_cap = fit;
+  }
+  r.cand = w.take<uint32_t>(r.cand_cap);
   r.bytes = w.off;
   r.ok = w.ok();
   return r;

@@ -80,11 +80,17 @@ def l2_cdc(data: torch.Tensor, cfg: IngestConfig, seg_off: torch.Tensor | None =
     meta = torch.zeros(2, dtype=torch.int64, device=dev)  # [n_cuts, status]
     # exact workspace for this segmentation: the generic sizing assumes ceil(n/seg_size) segments
     ws_bytes = workspace_bytes(STAGE_L2, n, cfg) + 24 * max(0, n_seg - n // cfg.seg_size) + 4096
-    ws = _ws(ws_bytes, dev)
-    rc = lib.hmse_l2_cdc(_ptr(data), n, _ptr(seg_off), n_seg, C.byref(c), _ptr(cuts), cap, meta.data_ptr(),
-                         meta.data_ptr() + 8, ws.data_ptr(), ws.numel(), _stream())
-    _check(rc, "hmse_l2_cdc")
-    n_cuts, status = (int(v) for v in meta.tolist())
+    # The provisioned candidate list holds 8x the expected density.  Bytes that are denser still (status bit 0) are legitimate
+    # input: run once more with a list of one entry per byte, which nothing can overflow (include/hmse.h).
+    for extra in (0, 4 * n + 256):
+        ws = _ws(ws_bytes + extra, dev)
+        rc = lib.hmse_l2_cdc(_ptr(data), n, _ptr(seg_off), n_seg, C.byref(c), _ptr(cuts), cap, meta.data_ptr(),
+                             meta.data_ptr() + 8, ws.data_ptr(), ws.numel(), _stream())
+        _check(rc, "hmse_l2_cdc")
+        n_cuts, status = (int(v) for v in meta.tolist())
+        if not (status & 1):
+            break
+        del ws
     if status & 0xFFFFFFFF:
         raise HmseError(-2, f"hmse_l2_cdc device status {status & 0xFFFFFFFF:#x}")
     return cuts[: n_cuts + 1]

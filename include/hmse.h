@@ -128,6 +128,13 @@ size_t hmse_workspace_bytes(int stage, uint64_t n, const hmse_cfg* cfg);
  *            written and n_cuts still receives the required count.
  *   status   DEVICE u32[1]: 0 ok, bit0 = candidate workspace overflow,
  *            bit1 = cuts_cap overflow
+ *   ws       hmse_workspace_bytes(HMSE_STAGE_L2_CDC, n, cfg) provisions a candidate list of 8x the expected density of
+ *            easy-mask hits plus 65536 entries.  The list is sized from ws_bytes: whatever the caller passes beyond
+ *            that goes to it, up to one entry per byte.  Ordinary bytes can be denser than provisioned (a run of two
+ *            alternating bytes whose window hash passes the easy mask makes every second position a candidate): the
+ *            call then reports bit0 and its cuts are not to be used; the same call with
+ *            hmse_workspace_bytes(...) + 4 * n + 256 bytes cannot overflow and gives the cuts (hmse_amd/ops.py::l2_cdc
+ *            does exactly this, once).  The default size does not grow.
  */
 int hmse_l2_cdc(const uint8_t* data, uint64_t n, const uint64_t* seg_off, uint32_t n_seg,
                 const hmse_cfg* cfg, uint64_t* cuts, uint64_t cuts_cap, uint64_t* n_cuts,
@@ -214,7 +221,10 @@ int hmse_l4_lsh_update(const uint32_t* sig_all, uint64_t n_old, uint64_t n_new, 
  *   out       DEVICE u8[out_cap]; chunk k's stream is out[out_off[k] .. out_off[k+1])
  *   out_off   DEVICE u64[n_sel+1]
  *   kind      DEVICE u8[n_sel]: HMSE_KIND_FULL or HMSE_KIND_DELTA
- *   status    DEVICE u32[1]: bit0 = out_cap overflow (out_off still exact), bit1 = workspace too small
+ *   status    DEVICE u32[1]: bit0 = out_cap overflow (out_off still exact), bit1 = workspace too small,
+ *             bit2 = a selected chunk is longer than 32768 bytes and was not encoded: it gets an EMPTY record
+ *             (out_off[k+1] == out_off[k], kind FULL) while every other chunk's record is complete and exact,
+ *             bit3 = a chunk was never encoded (internal error)
  *   ws        hmse_workspace_bytes(HMSE_STAGE_L1_DEFLATE, n_sel, cfg) is the FIXED part; after it the call needs
  *             one record per chunk: hmse_l1_deflate_record_bytes(len) bytes (about 4*len + 1.4 KiB: histograms and a
  *             token list sized for the all-literal case, which the FULL stream later overwrites), or
@@ -287,7 +297,8 @@ int hmse_read_assemble(const uint64_t* cuts, uint64_t n_chunks, const uint64_t* 
  * L3 lookup/insert -> L4 probe -> delta or full).  The batch's bytes are already at data[state[0] .. + batch_bytes); every
  * stage takes its ranges from `state` (DEVICE u64[16]: [0] byte offset, [1] chunks so far, [2] chunks of this batch (out),
  * [3] stored chunks so far, [4] stored chunks of this batch (out), [5] stream bytes so far, [6] stream bytes of this batch
- * (out), [7] sticky status: bit0 chunk capacity, bit1 stored-chunk capacity, bit2 L2 status, bit3 malformed exchange row,
+ * (out), [7] sticky status: bit0 chunk capacity, bit1 stored-chunk capacity, bit2 L2 status (the chain cannot run a batch twice: a batch with more cut candidates than its fixed list holds — see hmse_l2_cdc — is
+ * refused here, no cut of it is published; such bytes go through hmse_l2_cdc with the larger workspace), bit3 malformed exchange row,
  * bit4 workspace not initialised (hmse_stream_workspace_init), bit5 state block inconsistent (one rank and [8] != [1]: e.g. a stream resumed with the
  * version-1 state layout, whose [8] is 0), bits 8.. DEFLATE status; [8] chunks of ALL ranks so far (== [1] for one rank), [9] chunks of all ranks in this batch (out),
  * [10] global index of this rank's first chunk of the batch (out)), grids and workspace are sized for batch_bytes / min_size
