@@ -62,8 +62,10 @@ def write_band_tables_device(band_keys, band_bits: int = 16, signatures=None) ->
     return ops.band_tables_write(band_keys.contiguous(), None if signatures is None else signatures.contiguous(), band_bits).cpu().numpy().tobytes()
 
 
-def read_signatures(buf: bytes):
-    """-> (band keys u32[n][bands], signatures u32[n][n_hashes] or None) from the trailing section of write_band_tables()."""
+def split_sidecar(buf: bytes):
+    """One walk over write_band_tables()'s layout -> (the band-table section's bytes, band_bits, band keys u32[n][bands],
+    signatures u32[n][n_hashes]); keys and signatures are None without the trailing section.  A foreign or truncated buffer raises
+    AssertionError, struct.error or ValueError."""
     assert buf[:8] == MAGIC
     ver, bands, band_bits, id_bytes, n = struct.unpack_from("<IIIIQ", buf, 8)
     o = 8 + struct.calcsize("<IIIIQ")
@@ -71,12 +73,16 @@ def read_signatures(buf: bytes):
         (nh,) = struct.unpack_from("<Q", buf, o)
         o += 8 + 4 * nh + 3 * n
     if buf[o:o + 8] != b"HMSESIGS":
-        return None, None
+        return buf[:o], band_bits, None, None
     (nhash,) = struct.unpack_from("<I", buf, o + 8)
-    o += 12
-    keys = np.frombuffer(buf, "<u4", n * bands, o).reshape(n, bands); o += 4 * n * bands
-    sig = np.frombuffer(buf, "<u4", n * nhash, o).reshape(n, nhash)
-    return keys, sig
+    keys = np.frombuffer(buf, "<u4", n * bands, o + 12).reshape(n, bands)
+    sig = np.frombuffer(buf, "<u4", n * nhash, o + 12 + 4 * n * bands).reshape(n, nhash)
+    return buf[:o], band_bits, keys, sig
+
+
+def read_signatures(buf: bytes):
+    """-> (band keys u32[n][bands], signatures u32[n][n_hashes] or None) from the trailing section of write_band_tables()."""
+    return split_sidecar(buf)[2:]
 
 
 def read_band_tables(buf: bytes):

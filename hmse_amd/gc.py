@@ -1,9 +1,9 @@
-"""Garbage collection: drop segments from a one-shard store and collect its records on the GPU.
+"""Garbage collection: drop segments from a merged store of one or more shards and collect its records on the GPU.
 
 The ChunkIndex refcount is kept "for garbage collection" (README.md:1268, 1886); this module is what reads it back
 out of the chunk map.  The unit of deletion is the SEGMENT: L2 restarts its Gear hash at every segment start, so a segment
 boundary is always a cut, and the store that remains after dropping segments is defined exactly — it is, byte for byte, what
-`build_manifest(ingest_shard(R, cfg, seg_off=R_seg_off))` writes for the concatenation R of the surviving segments:
+a fresh ingest writes for the concatenation R of the surviving segments (`build_manifest(ingest_shard(R, cfg, seg_off=R_seg_off))`):
   * L2  the surviving segments keep their cuts;
   * L3  digests come from the old ChunkIndex; a slot's new first occurrence is its first SURVIVING reference (hmse_gc_plan), so a
         POINTER whose stored chunk was dropped is promoted to a stored chunk;
@@ -11,10 +11,11 @@ boundary is always a cut, and the store that remains after dropping segments is 
   * L1  the record of a (chunk, dictionary) pair is deterministic: it is reused when the pair is unchanged and re-encoded by
         hmse_l1_deflate otherwise; hmse_record_gather assembles the dense streams from both sources in one launch.
 The packing is the unchanged manifest.pack_manifest_device of a fresh ingest.
-A merged store of several shards (drop_sharded) has the same definition shard by shard — the store a fresh sharded ingest
-(ingest_shards_local) of every shard's surviving segments writes — with one plan over the concatenated chunk map, L4 in the store's
-scope (shard-local or global, remote dictionaries included) and stored chunks that move to the shard of their first surviving
-reference.  A multi-rank stream's store (pieces) and an unmerged part are refused.
+There is ONE body (_collect) for N >= 1 shards; a Manifest or a Store of one shard is its N = 1 case.  A store of several shards has
+the same definition shard by shard — the store a fresh sharded ingest (ingest_shards_local) of every shard's surviving segments
+writes — with one plan over the concatenated chunk map, L4 in the store's scope (shard-local or global, remote dictionaries
+included) and stored chunks that move to the shard of their first surviving reference.  A multi-rank stream's store (pieces) and
+an unmerged part are refused (manifest.merged_shards).
 """
 from __future__ import annotations
 
@@ -23,45 +24,14 @@ import time
 import numpy as np
 
 from .config import KIND_DELTA, KIND_POINTER, LAYER_L1, LAYER_L2, LAYER_L3, LAYER_L4, IngestConfig
-from .manifest import CHUNK_INDEX_DTYPE, MAP_DTYPE, POINTER_DTYPE, Manifest, Store
+from .manifest import Manifest, Store, merged_shards
 
 SUPPORTED_LAYERS = (LAYER_L1 | LAYER_L2 | LAYER_L3 | LAYER_L4, LAYER_L1 | LAYER_L2 | LAYER_L3)   # "full", "l1_cdc_dedupe"
 
 
-def _one_manifest(m) -> Manifest:
-    if isinstance(m, Store):
-        if len(m.shards) != 1:
-            raise ValueError(f"gc: a store of {len(m.shards)} shards goes through the sharded path (drop_segments of the Store)")
-        m = m.shards[0]
-    if m.n_shards != 1:
-        raise ValueError(f"gc: shard {m.shard} of {m.n_shards} is one part of a sharded store: merge_manifests() the parts and "
-                         "collect the merged Store")
-    if m.n_remote():
-        raise ValueError("gc: records of this manifest use dictionaries stored in other shards (remote_bases)")
-    if m.pieces is not None:
-        raise ValueError("gc: the manifest is one rank's part of a multi-rank stream (pieces)")
-    return m
-
-
 def _sharded(m) -> bool:
+    """A Store of several shards takes and returns per-shard lists; a Manifest or a Store of one shard the single items."""
     return isinstance(m, Store) and len(m.shards) > 1
-
-
-def _check_store(store: Store) -> list:
-    """The shards of a merged multi-shard store, checked before any device work: shard numbers, chunk bases, no stream pieces."""
-    shards = list(store.shards)
-    n = len(shards)
-    if any(m.pieces is not None for m in shards):
-        raise ValueError("gc: a multi-rank stream store (pieces: its shards' chunks interleave in stream order) is not collectable")
-    base = 0
-    for i, m in enumerate(shards):
-        if m.shard != i or m.n_shards != n:
-            raise ValueError(f"gc: the store's shard {i} is manifest shard {m.shard} of {m.n_shards}: not a merged store of {n} shards "
-                             "(merge_manifests)")
-        if m.chunk_base != base:
-            raise ValueError(f"gc: shard {i} starts at chunk {m.chunk_base}, not {base}: not a merged store (merge_manifests)")
-        base += len(m.chunk_map)
-    return shards
 
 
 def _check_layers(cfg: IngestConfig) -> None:
@@ -116,10 +86,13 @@ def segments_of_ranges(seg_off: np.ndarray, ranges) -> list:
 
 
 def shard_segments(store: Store, cfg: IngestConfig, seg_off=None):
-    """A merged multi-shard store's segment tables: (per shard its own table, checked against its cut list as store_seg_off does;
+    """A merged store's segment tables: (per shard its own table, checked against its cut list as store_seg_off does;
     the global table — the shards' tables shifted by the shard byte offsets, shard 0's segments first; the first global segment
     index of every shard, int64[n_shards + 1]).  `seg_off`: a list of per-shard local tables (None entries or None: cfg.seg_size)."""
-    shards = _check_store(store)
+    return _segment_tables(merged_shards(store, "gc"), cfg, seg_off)
+
+
+def _segment_tables(shards: list, cfg: IngestConfig, seg_off=None):
     if seg_off is not None and len(seg_off) != len(shards):
         raise ValueError(f"gc: seg_off must hold one segment table per shard ({len(shards)}), got {len(seg_off)}")
     sos = [store_seg_off(m, cfg, None if seg_off is None else seg_off[i]) for i, m in enumerate(shards)]
@@ -143,204 +116,51 @@ def drop_ranges(m, ranges, cfg: IngestConfig, device, band_tables=None, seg_off=
     """drop_segments() of the segments that the segment-aligned byte ranges [(offset, len), ...] cover (a sharded store: ranges of
     the original corpus, the shards concatenated in shard order)."""
     _check_layers(cfg)
-    if _sharded(m):
-        _, so_g, _ = shard_segments(m, cfg, seg_off)
-        return drop_segments(m, segments_of_ranges(so_g, ranges), cfg, device, band_tables=band_tables, seg_off=seg_off,
-                             global_l4=global_l4, verify=verify, timings=timings)
-    m = _one_manifest(m)
-    so = store_seg_off(m, cfg, seg_off)
-    return drop_segments(m, segments_of_ranges(so, ranges), cfg, device, band_tables=band_tables, seg_off=so, verify=verify, timings=timings)
+    sos, so_g, _ = _segment_tables(merged_shards(m, "gc"), cfg, seg_off if _sharded(m) else [seg_off])
+    return drop_segments(m, segments_of_ranges(so_g, ranges), cfg, device, band_tables=band_tables, seg_off=sos if _sharded(m) else sos[0],
+                         global_l4=global_l4, verify=verify, timings=timings)
 
 
 def drop_segments(m, drop, cfg: IngestConfig, device, band_tables=None, seg_off=None, global_l4: bool = False, verify: bool = True,
                   timings=None):
-    """Drop the segments `drop` (indices into the store's segment table: `seg_off`, or the fixed cfg.seg_size grid when None) from
-    a one-shard store and collect its records.  Returns (Manifest, sidecar bytes or None, stats):
-      * Manifest.to_bytes() equals that of build_manifest(ingest_shard(R, cfg, seg_off=R_seg_off)), R = the surviving segments;
-      * the sidecar equals StreamIngest.index_sidecar() after ingesting R (layer mask "full"; None for "l1_cdc_dedupe").
-    `band_tables` is the store's band-table sidecar (StreamIngest.index_sidecar()): with it only the records to re-encode and their
-    new dictionaries are decoded (one hmse_l1_inflate over their dictionary closure).  WITHOUT it the whole store is decoded and
-    every stored chunk goes through hmse_l4_minhash — the cost of a read of the store plus the MinHash stage of an ingest.
+    """Drop the segments `drop` from a merged store and collect its records.  `m`: a Manifest or a Store of one shard — `drop` holds
+    indices into its segment table (`seg_off`, or the fixed cfg.seg_size grid when None), `band_tables` is its band-table sidecar
+    (StreamIngest.index_sidecar()) and (Manifest, sidecar bytes or None, stats) comes back — or a Store of N > 1 shards: `drop`
+    holds GLOBAL segment indices (shard 0's segments first, each shard's as store_seg_off numbers them; a zero-byte shard keeps its
+    one empty segment), `band_tables` one sidecar per shard or None, `seg_off` per-shard local tables or None, `global_l4` names
+    the store's dictionary scope, and (Store, [N sidecars] or None, stats) comes back.  With R_i the surviving segments of shard i:
+      * to_bytes() equals that of merge_manifests([build_manifest(r, i, N) for r in ingest_shards_local([R_0..], cfg,
+        global_l4=global_l4, seg_offs=[..])]) — for one shard build_manifest(ingest_shard(R, cfg, seg_off=R_seg_off));
+      * sidecar i equals write_band_tables(r_i.band_keys, cfg.band_bits, signatures=r_i.sig) — for one shard
+        StreamIngest.index_sidecar() after ingesting R (layer mask "full"; None for "l1_cdc_dedupe").
+    WITH the sidecars only the records to re-encode and their new dictionaries are decoded (one hmse_l1_inflate over their
+    dictionary closure).  WITHOUT them the whole store is decoded and every stored chunk goes through hmse_l4_minhash — the cost of
+    a read of the store plus the MinHash stage of an ingest.
     The old record of a stored chunk is reused iff it was made with the dictionary the new LSH picks; the old dictionaries of FULL
     records (rule 7 fallbacks do not store one) are recomputed by hmse_l4_lsh over all old signatures, and every DELTA header must
-    agree with that recomputation — otherwise the store was not written under this cfg (a windowed stream, other LSH parameters)
-    and ValueError is raised rather than a store that differs from a fresh ingest.  `verify` checks the SHA-256 of every decoded
-    chunk.  Supported layer masks: "full" and "l1_cdc_dedupe"; one shard only (cross-shard GC is out of scope).
-    `timings` (a dict, diagnostics): filled with per-phase milliseconds (synchronising between phases).
-    A merged Store of more than one shard takes the sharded path (drop_sharded: one sidecar and one segment table per shard,
-    `global_l4` names the store's dictionary scope); `global_l4` means nothing to a one-shard store."""
-    if _sharded(m):
-        return drop_sharded(m, drop, cfg, device, band_tables, seg_off, global_l4, verify, timings)
-    m = _one_manifest(m)
+    agree with that recomputation — otherwise the store was not written under this cfg (a windowed stream, the other L4 scope,
+    other LSH parameters) and ValueError is raised rather than a store that differs from a fresh ingest.  `verify` checks the
+    SHA-256 of every decoded chunk.  Supported layer masks: "full" and "l1_cdc_dedupe".
+    `timings` (a dict, diagnostics): filled with per-phase milliseconds (synchronising between phases)."""
     _check_layers(cfg)
-    cuts_np = store_cuts(m)
-    so = store_seg_off(m, cfg, seg_off, cuts_np)
-    n_seg = len(so) - 1
-    drop = sorted({int(d) for d in drop})
-    if drop and (drop[0] < 0 or drop[-1] >= n_seg):
-        raise ValueError(f"gc: segment index out of range (the store has {n_seg} segments)")
-    nc, nu = len(m.chunk_map), len(m.index)
-    own = np.nonzero(m.chunk_map["kind"] != KIND_POINTER)[0]
-    if len(own) != nu or not np.array_equal(m.chunk_map["slot"][own], np.arange(nu)):
-        raise ValueError("gc: manifest index and chunk map disagree on the stored chunks")
-    if nu and not m.index["sha256"].any():
-        raise ValueError("gc: the store carries no SHA-256 digests (L3)")
-    use_l4 = bool(cfg.layers & LAYER_L4)
-    if use_l4 and band_tables is not None:
-        from . import bandtable
-        keys_side, sig_side = bandtable.read_signatures(band_tables)
-        if sig_side is None or sig_side.shape != (nu, cfg.n_hashes) or keys_side.shape != (nu, cfg.bands):
-            raise ValueError("gc: the band-table sidecar does not belong to this manifest / configuration")
-
-    import torch
-
-    from . import ingest, manifest, ops, read
-    dev = torch.device(device)
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).copy()).to(dt).to(dev)
-    clock = _Clock(timings)
-    drop_mask = np.zeros(n_seg, np.uint8)
-    drop_mask[drop] = 1
-    stats = {"segments_dropped": len(drop), "chunks_before": nc, "stored_before": nu, "blob_bytes_before": int(m.blob.size),
-             "bytes_decoded": 0}
-
-    # --- plan: survival, new chunk and slot numbering, L3 arrays (hmse_gc_plan)
-    cuts_old = t(cuts_np, torch.int64)
-    plan = ops.gc_plan(cuts_old, t(m.chunk_map["slot"].astype(np.int32), torch.int32), nu, t(so, torch.int64), t(drop_mask, torch.uint8),
-                       t(m.index["sha256"], torch.uint8).reshape(nu, 32))
-    n_new, u_new = plan["old_chunk"].numel(), plan["old_slot"].numel()
-    lens_old = cuts_old[1:] - cuts_old[:-1]
-    cuts_new = torch.zeros(n_new + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(lens_old[plan["old_chunk"]], 0, out=cuts_new[1:])
-    old_slot, new_slot_of_old = plan["old_slot"], plan["new_slot_of_old"]
-    clock.lap("plan")
-    if n_new == 0:
-        stats.update(_counts(0, 0, 0, 0, 0, 0, 0, 0))
-        empty = Manifest(1, np.zeros(0, CHUNK_INDEX_DTYPE), np.zeros(0, MAP_DTYPE), np.zeros(0, POINTER_DTYPE), np.zeros(0, np.uint8))
-        side = _sidecar(np.zeros((0, cfg.bands), np.int32), np.zeros((0, cfg.n_hashes), np.int32), cfg) if use_l4 else None
-        return empty, side, stats
-
-    rd = read.StoreReader(m, dev)                    # blob in HBM, record headers parsed (one shard: slot order, base < slot)
-    kind_old = t(rd.kind, torch.uint8)
-    raw_all = raw_off_all = None
-
-    def decode(slots: np.ndarray):
-        """One hmse_l1_inflate over `slots` (ascending, closed under dictionaries) -> (raw, raw_off)."""
-        b = rd.base[slots]
-        base_sel = np.where(b >= 0, np.searchsorted(slots, np.maximum(b, 0)), -1)
-        raw, raw_off, _ = ops.l1_inflate(rd.blob, t(rd.stream_off[slots], torch.int64), t(rd.kind[slots], torch.uint8), t(base_sel, torch.int64),
-                                         t(rd.raw_len[slots], torch.int64), stream_len=t(rd.stream_len[slots], torch.int32))
-        if verify:
-            read.verify_digests(raw, raw_off, t(rd.sha[slots], torch.uint8))
-        stats["bytes_decoded"] += int(rd.raw_len[slots].sum())
-        return raw, raw_off
-
-    # --- L4: signatures of the old stored chunks, the old dictionaries (recomputed), the new ones
-    sig_new = keys_new = base_new = None
-    if use_l4:
-        if band_tables is not None:
-            sig_old = t(sig_side.view(np.int32), torch.int32)
-        else:
-            raw_all, raw_off_all = decode(np.arange(nu, dtype=np.int64))
-            clock.lap("decode")
-            sig_old = ops.l4_minhash(raw_all, raw_off_all, cfg)
-            clock.lap("minhash")
-        keys_old, base_old = ops.l4_lsh(sig_old, cfg)
-        hdr_base = t(rd.base, torch.int64)
-        if not bool(((kind_old != KIND_DELTA) | (hdr_base == base_old)).all()):
-            raise ValueError("gc: a DELTA record's dictionary is not the LSH base of its chunk under this configuration "
-                             "(the store was written with other LSH parameters or by a windowed stream)")
-        if band_tables is not None and not torch.equal(keys_old, t(keys_side.view(np.int32), torch.int32)):
-            raise ValueError("gc: the sidecar's band keys are not those of its signatures under this configuration")
-        sig_new = sig_old[old_slot]
-        keys_new, base_new = ops.l4_lsh(sig_new, cfg)
-        base_new_old = torch.where(base_new >= 0, old_slot[base_new.clamp(min=0)], base_new)   # new dictionary as an old slot
-        old_base = base_old[old_slot]
-        reuse = old_base == base_new_old
-        clock.lap("lsh")
-    else:
-        base_new_old = old_base = torch.full((u_new,), -1, dtype=torch.int64, device=dev)
-        reuse = torch.ones(u_new, dtype=torch.bool, device=dev)
-
-    # --- why each stored chunk is re-encoded: promoted POINTER, old dictionary dropped or now behind it, dictionary changed
-    j_idx = torch.arange(u_new, dtype=torch.int64, device=dev)
-    own_old = t(own, torch.int64)
-    promoted = plan["old_chunk"][plan["uniq_ids"]] != own_old[old_slot]
-    ob_new = torch.where(old_base >= 0, new_slot_of_old[old_base.clamp(min=0)], old_base)
-    base_gone = (old_base >= 0) & ((ob_new < 0) | (ob_new > j_idx))
-    redo = ~reuse
-    enc = redo.nonzero().flatten()
-    n_enc = int(enc.numel())
-
-    # --- L1: re-encode what cannot be reused (hmse_l1_deflate, dictionaries by chunk id into the decoded closure)
-    src1 = None
-    kind_e = torch.zeros(0, dtype=torch.uint8, device=dev)
-    off_e = torch.zeros(1, dtype=torch.int64, device=dev)
-    if n_enc:
-        slots_e = old_slot[enc]
-        bases_e = base_new_old[enc]
-        if raw_all is not None:                     # the whole store is decoded already
-            data, dcuts = raw_all, raw_off_all
-            cid, bid = slots_e, bases_e
-        else:
-            se, be = slots_e.cpu().numpy(), bases_e.cpu().numpy()
-            need = rd.closure(np.concatenate([se, be[be >= 0]]))
-            data, dcuts = decode(need)
-            clock.lap("decode")
-            need_d = t(need, torch.int64)
-            cid = torch.searchsorted(need_d, slots_e)
-            bid = torch.where(bases_e >= 0, torch.searchsorted(need_d, bases_e.clamp(min=0)), bases_e)
-        src1, off_e, kind_e = ops.l1_deflate(data, dcuts, cfg, cid, bid, base_is_chunk_id=True)
-        del data, dcuts
-        clock.lap("reencode")
-    raw_all = raw_off_all = None
-
-    # --- gather: dense streams of the new store from the old blob (reused) and the DEFLATE output (re-encoded)
-    # per stored chunk: its re-encoded record's number, or n_enc (a spare zero entry) for a reused one — every index stays in range
-    rec_e = torch.full((u_new,), n_enc, dtype=torch.int64, device=dev)
-    rec_e[enc] = torch.arange(n_enc, dtype=torch.int64, device=dev)
-    z64 = torch.zeros(1, dtype=torch.int64, device=dev)
-    e_off, e_len = torch.cat([off_e[:-1], z64]), torch.cat([off_e[1:] - off_e[:-1], z64])
-    e_kind = torch.cat([kind_e, torch.zeros(1, dtype=torch.uint8, device=dev)])
-    s_off_old, s_len_old = t(rd.stream_off, torch.int64), t(rd.stream_len, torch.int64)
-    src_off = torch.where(redo, e_off[rec_e], s_off_old[old_slot])
-    s_len = torch.where(redo, e_len[rec_e], s_len_old[old_slot])
-    kind_new = torch.where(redo, e_kind[rec_e], kind_old[old_slot])
-    stream_off = torch.zeros(u_new + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(s_len, 0, out=stream_off[1:])
-    streams = ops.record_gather(rd.blob, src1, src_off, redo.to(torch.uint8), stream_off)
-    clock.lap("gather", nbytes=2 * int(streams.numel()))
-    del rd, src1
-
-    # --- pack: the ShardResult a fresh ingest of the remainder returns, through the unchanged packing code
-    res = ingest.ShardResult(int(cuts_new[-1].item()), cuts_new, plan["digests"], 0, n_new, plan["first_occ"], plan["refcount"],
-                             plan["uniq_ids"], sig_new, keys_new, base_new if use_l4 else None, streams, stream_off, kind_new)
-    out = manifest.build_manifest(res)
-    side = _sidecar(keys_new.cpu().numpy(), sig_new.cpu().numpy(), cfg) if use_l4 else None
-    clock.lap("pack")
-    changed = redo & (kind_new != kind_old[old_slot])
-    stats.update(_counts(n_new, u_new, u_new - n_enc, int((redo & promoted).sum()), int((redo & ~promoted & base_gone).sum()),
-                         int((redo & ~promoted & ~base_gone).sum()), int(promoted.sum()), int(changed.sum())))
-    stats["blob_bytes_after"] = int(out.blob.size)
-    return out, side, stats
+    shards = merged_shards(m, "gc")
+    if _sharded(m):
+        return _collect(shards, drop, cfg, device, band_tables, seg_off, global_l4, verify, timings)
+    # one shard: every dictionary is local, so there is no L4 scope to name — `global_l4` means nothing and is not passed on
+    out, sides, stats = _collect(shards, drop, cfg, device, None if band_tables is None else [band_tables], [seg_off], False, verify, timings)
+    return out.shards[0], None if sides is None else sides[0], stats
 
 
-def drop_sharded(store: Store, drop, cfg: IngestConfig, device, band_tables=None, seg_off=None, global_l4: bool = False,
-                 verify: bool = True, timings=None):
-    """drop_segments() of a merged store of N > 1 shards.  `drop`: GLOBAL segment indices (shard 0's segments first, each shard's
-    as store_seg_off numbers them; a zero-byte shard keeps its one empty segment).  `band_tables`: one sidecar per shard or None;
-    `seg_off`: per-shard local segment tables or None.  Returns (Store, [N sidecars] or None, stats): with R_i the surviving segments
-    of shard i, Store.to_bytes() equals merge_manifests([build_manifest(r, i, N) for r in ingest_shards_local([R_0..], cfg,
-    global_l4=global_l4, seg_offs=[..])]) and sidecar i equals write_band_tables(r_i.band_keys, cfg.band_bits, signatures=r_i.sig).
+def _collect(shards: list, drop, cfg: IngestConfig, device, band_tables, seg_off, global_l4: bool, verify: bool, timings):
+    """drop_segments() of the N >= 1 shards of a merged store -> (Store, [N sidecars] or None, stats).
     One hmse_gc_plan runs over the concatenated chunk map (global slot = slot base of the chunk map's shard + slot; the global chunk
     order (shard, local) is the order in which a sharded ingest picks first occurrences), so the plan's new chunk and slot numbers
     are the fresh run's global numbers; they are split per shard at the new chunk bases.  A stored chunk whose first surviving
     reference lies on another shard MIGRATES there.  L4 is recomputed per shard (shard-local) or over all shards (`global_l4`); a
     record is reused iff its dictionary (an old global slot) is unchanged — from the old blobs, back to back as StoreReader holds
     them, whatever its shard.  The sidecars are written on the GPU (hmse_band_tables_write)."""
-    _check_layers(cfg)
-    shards = _check_store(store)
     N = len(shards)
-    sos, so_g, seg_base = shard_segments(store, cfg, seg_off)
+    sos, so_g, seg_base = _segment_tables(shards, cfg, seg_off)
     n_seg = int(seg_base[-1])
     drop = sorted({int(d) for d in drop})
     if drop and (drop[0] < 0 or drop[-1] >= n_seg):
@@ -378,7 +198,7 @@ def drop_sharded(store: Store, drop, cfg: IngestConfig, device, band_tables=None
 
     from . import bandtable, ingest, manifest, ops, read
     dev = torch.device(device)
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).copy()).to(dt).to(dev)
+    t = lambda a, dt: read.to_device(a, dt, dev)
     clock = _Clock(timings)
     drop_mask = np.zeros(n_seg, np.uint8)
     drop_mask[drop] = 1
@@ -387,7 +207,7 @@ def drop_sharded(store: Store, drop, cfg: IngestConfig, device, band_tables=None
 
     # --- plan over the concatenated chunk map: global cuts, global slots, global segment table
     cuts_np = np.concatenate([[0]] + [store_cuts(m)[1:] + int(so_g[seg_base[i]]) for i, m in enumerate(shards)]).astype(np.int64)
-    slot_np = np.concatenate([sbase[m.chunk_map["shard"].astype(np.int64)] + m.chunk_map["slot"].astype(np.int64) for m in shards])
+    slot_np, _ = read.chunk_slots(shards)
     sha_np = np.concatenate([m.index["sha256"] for m in shards]).reshape(nu, 32)
     cuts_old = t(cuts_np, torch.int64)
     plan = ops.gc_plan(cuts_old, t(slot_np.astype(np.int32), torch.int32), nu, t(so_g, torch.int64), t(drop_mask, torch.uint8), t(sha_np, torch.uint8))
@@ -401,21 +221,16 @@ def drop_sharded(store: Store, drop, cfg: IngestConfig, device, band_tables=None
     lens_new = (cuts_old[1:] - cuts_old[:-1])[plan["old_chunk"]]
     clock.lap("plan")
 
-    rd = read.StoreReader(store, dev)                # every shard's blob in HBM, back to back; record headers parsed (global slots)
+    rd = read.StoreReader(Store(shards), dev)        # every shard's blob in HBM, back to back; record headers parsed (global slots)
     if not np.array_equal(rd.slot, slot_np):
         raise ValueError("gc: the store's dictionaries do not precede their records (not the store of a one-shot sharded ingest)")
     kind_old = t(rd.kind, torch.uint8)
     raw_all = raw_off_all = None
 
-    def decode(slots: np.ndarray):
-        b = rd.base[slots]
-        base_sel = np.where(b >= 0, np.searchsorted(slots, np.maximum(b, 0)), -1)
-        raw, raw_off, _ = ops.l1_inflate(rd.blob, t(rd.stream_off[slots], torch.int64), t(rd.kind[slots], torch.uint8), t(base_sel, torch.int64),
-                                         t(rd.raw_len[slots], torch.int64), stream_len=t(rd.stream_len[slots], torch.int32))
-        if verify:
-            read.verify_digests(raw, raw_off, t(rd.sha[slots], torch.uint8))
-        stats["bytes_decoded"] += int(rd.raw_len[slots].sum())
-        return raw, raw_off
+    def decode(slots=None):
+        """rd.decode() of the stored slots `slots` (ascending, closed under dictionaries; None: all), counted in the stats."""
+        stats["bytes_decoded"] += int((rd.raw_len if slots is None else rd.raw_len[slots]).sum())
+        return rd.decode(slots, verify)
 
     def lsh(sig, bases):
         """Band keys and dictionaries (global slots, -1 none) of `sig`: one LSH over all rows (global L4) or one per shard."""
@@ -433,7 +248,7 @@ def drop_sharded(store: Store, drop, cfg: IngestConfig, device, band_tables=None
         if sig_side is not None:
             sig_old = t(sig_side.view(np.int32), torch.int32)
         else:
-            raw_all, raw_off_all = decode(np.arange(nu, dtype=np.int64))
+            raw_all, raw_off_all = decode()
             clock.lap("decode")
             sig_old = ops.l4_minhash(raw_all, raw_off_all, cfg)
             clock.lap("minhash")
@@ -532,23 +347,13 @@ def drop_sharded(store: Store, drop, cfg: IngestConfig, device, band_tables=None
                  for i in range(N)]
         clock.lap("sidecar")
     changed = redo & (kind_new != kind_old[old_slot])
-    stats.update(_counts(n_new, u_new, u_new - n_enc, int((redo & promoted).sum()), int((redo & ~promoted & base_gone).sum()),
-                         int((redo & ~promoted & ~base_gone).sum()), int(promoted.sum()), int(changed.sum())))
-    stats["blob_bytes_after"] = int(sum(m.blob.size for m in out.shards))
-    stats["records_migrated"] = int(migrated.sum())
-    stats["per_shard"] = [{"chunks_after": new_cb[i + 1] - new_cb[i], "stored_after": new_ub[i + 1] - new_ub[i]} for i in range(N)]
+    r_prom, r_gone, r_changed = int((redo & promoted).sum()), int((redo & ~promoted & base_gone).sum()), int((redo & ~promoted & ~base_gone).sum())
+    stats.update({"chunks_after": n_new, "stored_after": u_new, "records_reused": u_new - n_enc, "records_reencoded": n_enc,
+                  "reencoded_promoted": r_prom, "reencoded_base_dropped_or_moved": r_gone, "reencoded_base_changed": r_changed,
+                  "promoted": int(promoted.sum()), "kind_changed": int(changed.sum()), "blob_bytes_after": int(sum(m.blob.size for m in out.shards)),
+                  "records_migrated": int(migrated.sum()),
+                  "per_shard": [{"chunks_after": new_cb[i + 1] - new_cb[i], "stored_after": new_ub[i + 1] - new_ub[i]} for i in range(N)]})
     return out, sides, stats
-
-
-def _counts(n_new, u_new, reused, r_prom, r_gone, r_changed, promoted, kind_changed) -> dict:
-    return {"chunks_after": n_new, "stored_after": u_new, "records_reused": reused, "records_reencoded": r_prom + r_gone + r_changed,
-            "reencoded_promoted": r_prom, "reencoded_base_dropped_or_moved": r_gone, "reencoded_base_changed": r_changed,
-            "promoted": promoted, "kind_changed": kind_changed, "blob_bytes_after": 0}
-
-
-def _sidecar(keys: np.ndarray, sig: np.ndarray, cfg: IngestConfig) -> bytes:
-    from . import bandtable
-    return bandtable.write_band_tables(keys, cfg.band_bits, signatures=sig)
 
 
 class _Clock:

@@ -226,6 +226,42 @@ def merge_manifests(parts: list) -> Store:
     return Store(out)
 
 
+def merged_shards(store, who: str, lenient: bool = False) -> list:
+    """The shards of a merged store — a lone Manifest is a store of one shard — or ValueError, prefixed by `who`: an unmerged part,
+    shards that are not numbered 0..N-1 of N, unresolved cross-shard pointers.  Readers of the (shard, local) chunk order also
+    refuse a multi-rank stream's store (pieces: its shards' chunks interleave in stream order), chunk bases that do not follow
+    from the chunk maps and a one-shard store with remote dictionaries; `lenient` (scrub, which reports such damage instead)
+    leaves those three alone."""
+    remote = f"{who}: records of this manifest use dictionaries stored in other shards (remote_bases): pass the merged Store"
+    if isinstance(store, Manifest):
+        if store.n_shards != 1:
+            raise ValueError(f"{who}: shard {store.shard} of {store.n_shards} is one part of a sharded store: merge_manifests() the parts "
+                             "and pass the merged Store")
+        if store.n_remote():
+            raise ValueError(remote)
+        shards = [store]
+    elif isinstance(store, Store):
+        shards = list(store.shards)
+    else:
+        raise ValueError(f"{who}: a Manifest or a Store, not {type(store).__name__}")
+    n, base = len(shards), 0
+    if not lenient:
+        if n == 1 and shards[0].n_remote():
+            raise ValueError(remote)
+        if any(m.pieces is not None for m in shards):
+            raise ValueError(f"{who}: a multi-rank stream's store (pieces: its shards' chunks interleave in stream order) is not supported")
+    for i, m in enumerate(shards):
+        if m.shard != i or m.n_shards != n:
+            raise ValueError(f"{who}: the store's shard {i} is manifest shard {m.shard} of {m.n_shards}: not a merged store of {n} shards "
+                             "(merge_manifests)")
+        if not lenient and m.chunk_base != base:
+            raise ValueError(f"{who}: shard {i} starts at chunk {m.chunk_base}, not {base}: not a merged store (merge_manifests)")
+        base += len(m.chunk_map)
+    if any(((m.pointers["flags"] & PTR_UNRESOLVED) != 0).any() for m in shards):
+        raise ValueError(f"{who}: the store has unresolved cross-shard pointers: merge_manifests() its shards first")
+    return shards
+
+
 def stream_order(shards: list) -> np.ndarray | None:
     """A store written by a multi-rank STREAM keeps its chunks per shard, but the original bytes are the chunks in stream
     order (batch, rank, local): the permutation from stream position to the (shard, local)-concatenated chunk list, or None for

@@ -6,6 +6,8 @@ hmse_amd/csrc/l1_inflate.hip and the L3 SHA-256 kernel (the reference's "100 % c
 """
 from __future__ import annotations
 
+import dataclasses
+
 import numpy as np
 import torch
 
@@ -217,91 +219,42 @@ def chunk_slots(shards: list):
     return slot, np.concatenate([m.chunk_map["raw_length"].astype(np.int64) for m in shards])
 
 
-def read_store(store: Store, device, verify: bool = True) -> torch.Tensor:
-    """A sharded store (one Manifest per shard, cross-shard pointers resolved by manifest.merge_manifests) -> the
-    original corpus in global chunk order, decoded on `device`: the records of all shards are inflated in one call, then
-    ONE assembly pass lays out every chunk from the slot its map entry names — its own shard's or, for a cross-shard
-    POINTER, another's (README.md:1635-1669)."""
-    from .manifest import PTR_UNRESOLVED
-    if any(((m.pointers["flags"] & PTR_UNRESOLVED) != 0).any() for m in store.shards):
-        raise ReadError("the store has unresolved cross-shard pointers: merge_manifests() its shards first")
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).copy()).to(dt).to(device)
-    # ONE inflate call over the records of all shards, in (shard, slot) order: a DELTA's dictionary is an earlier record of
-    # its own shard or — in a store ingested with global L4 — of an earlier shard (manifest.remote_bases)
-    sb = np.cumsum([0] + [len(m.index) for m in store.shards])
-    bb = np.cumsum([0] + [int(m.blob.size) for m in store.shards])
-    ps = [parse_manifest(m) for m in store.shards]
-    for m, p in zip(store.shards, ps):
-        if m.n_remote():
-            rb = m.remote_bases
-            lba = m.blob[(m.index["lba"][rb["slot"]].astype(np.int64) * m.lba_unit)[:, None] + np.arange(4)[None, :]].copy().view("<u4")[:, 0]
-            want = np.array([store.shards[int(r)].index["lba"][int(b)] for r, b in zip(rb["shard"], rb["base_slot"])], np.uint32)
-            if not np.array_equal(lba, want):
-                raise ReadError("the store has unresolved cross-shard DeltaChunk headers: merge_manifests() its shards first")
-    cat = lambda key, adj=None: np.concatenate([(p[key] if adj is None else adj(i, p)) for i, p in enumerate(ps)]) if ps else np.zeros(0, np.int64)
-    base_g = cat("base", lambda i, p: np.where(p["base"] >= 0, sb[p["base_shard"]] + p["base"], -1)).astype(np.int64)
-    dep = dependency_order(base_g)          # (a global-L4 stream's store: dictionaries on later-numbered shards)
-    o = (lambda a: a) if dep is None else (lambda a: a[dep[0]])
-    if dep is not None:
-        base_g = np.where(base_g >= 0, dep[1][np.maximum(base_g, 0)], -1)
-    if len(base_g):
-        blobs = [t(m.blob, torch.uint8) for m in store.shards if m.blob.size]
-        blob_all = blobs[0] if len(blobs) == 1 else torch.cat(blobs) if blobs else torch.zeros(1, dtype=torch.uint8, device=device)
-        del blobs
-        raw_all, raw_off_all, _ = ops.l1_inflate(blob_all,
-                                                 t(o(cat("stream_off", lambda i, p: p["stream_off"] + bb[i])), torch.int64),
-                                                 t(o(cat("kind")), torch.uint8), t(o(base_g), torch.int64), t(o(cat("raw_len")), torch.int64),
-                                                 stream_len=t(o(cat("stream_len")), torch.int32))
-    else:
-        raw_all = torch.empty(0, dtype=torch.uint8, device=device); raw_off_all = torch.zeros(1, dtype=torch.int64, device=device)
-    slot_g, lens = chunk_slots(store.shards)
-    from .manifest import stream_order
-    perm = stream_order(store.shards)          # a multi-rank stream's store: the original bytes are the chunks in stream order
-    if perm is not None:
-        slot_g, lens = slot_g[perm], lens[perm]
-    cuts = torch.zeros(len(lens) + 1, dtype=torch.int64, device=device)
-    torch.cumsum(t(lens, torch.int64), 0, out=cuts[1:])
-    data = ops.read_assemble(cuts, t(slot_g if dep is None else dep[1][slot_g], torch.int64), raw_off_all, raw_all)
-    if verify:
-        sha = np.concatenate([m.index["sha256"] for m in store.shards]) if store.shards else np.zeros((0, 32), np.uint8)
-        if len(sha) and sha.any():
-            verify_digests(data, cuts, t(sha[slot_g], torch.uint8))
-    return data
-
-
-def read_manifest(m: Manifest, device, verify: bool = True) -> torch.Tensor:
-    """Manifest bytes (hmse_amd/manifest.py record formats) -> original data, decoded on `device`."""
-    idx, cmap = m.index, m.chunk_map
-    u, n = len(idx), len(cmap)
-    if m.n_remote():
-        raise ReadError("records of this manifest use dictionaries stored in other shards: read_store() the merged store")
-    p = parse_manifest(m)
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).copy()).to(dt).to(device)
-    raw, raw_off, _ = ops.l1_inflate(t(m.blob, torch.uint8), t(p["stream_off"], torch.int64), t(p["kind"], torch.uint8), t(p["base"], torch.int64),
-                                     t(p["raw_len"], torch.int64), stream_len=t(p["stream_len"], torch.int32))
-    cuts = torch.zeros(n + 1, dtype=torch.int64, device=device)
-    torch.cumsum(t(p["raw_len"][cmap["slot"]], torch.int64), 0, out=cuts[1:])
-    data = ops.read_assemble(cuts, t(cmap["slot"].astype(np.int64), torch.int64), raw_off, raw)
-    if verify and u and idx["sha256"].any():
-        verify_digests(data, cuts, t(idx["sha256"][cmap["slot"]], torch.uint8))
-    return data
+def to_device(a, dt, device) -> torch.Tensor:
+    """A host array as a tensor of dtype `dt` on `device` (a read-only view, e.g. np.frombuffer over a file's bytes, is copied first)."""
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dt).to(device)
 
 
 class StoreReader:
-    """Request-driven read (README.md:1444-1448 "Read Request (offset, len)" -> chunk map; 1621-1675 the three branches per
-    requested chunk; gate README.md:1329 "1000 random articles"): a store (or one manifest) is opened ONCE — blobs to HBM, record
-    headers parsed — and then serves byte ranges of the original corpus: chunk map -> the touched chunks -> their stored slots
-    (a POINTER names its target's) -> the transitive closure over DELTA dictionaries -> ONE hmse_l1_inflate over that subset
-    (dictionaries renumbered so that base < k) -> only the requested bytes are laid out -> SHA-256 of every touched chunk.
-    Nothing outside the closure is decoded."""
+    """A store (or one manifest) opened ONCE — record headers parsed, records numbered globally in (shard, slot) order and, where a
+    dictionary sits behind its dependant (a multi-rank global-L4 stream's store), re-ordered by dictionary depth, blobs in HBM back
+    to back — for every consumer of a written store: the full read (read_store, read_manifest), garbage collection, a stream's
+    resume, and the request-driven read (README.md:1444-1448 "Read Request (offset, len)" -> chunk map; 1621-1675 the three branches
+    per requested chunk; gate README.md:1329 "1000 random articles"): byte ranges of the original corpus -> the touched chunks ->
+    their stored slots (a POINTER names its target's) -> the transitive closure over DELTA dictionaries -> ONE hmse_l1_inflate over
+    that subset (dictionaries renumbered so that base < k) -> only the requested bytes are laid out -> SHA-256 of every touched
+    chunk.  Nothing outside the closure is decoded."""
 
     def __init__(self, store, device):
-        from .manifest import PTR_UNRESOLVED
-        shards = store.shards if isinstance(store, Store) else [store]
+        from .manifest import PTR_UNRESOLVED, stream_order
+        if isinstance(store, Store):
+            shards = store.shards
+        else:                                   # a lone manifest is numbered as shard 0 of 1, whatever part of a run it was
+            if store.n_remote():
+                raise ReadError("records of this manifest use dictionaries stored in other shards: read_store() the merged store")
+            cmap = store.chunk_map.copy()
+            cmap["shard"] = 0
+            shards = [dataclasses.replace(store, chunk_map=cmap, shard=0, n_shards=1)]
         if any(((m.pointers["flags"] & PTR_UNRESOLVED) != 0).any() for m in shards):
             raise ReadError("the store has unresolved cross-shard pointers: merge_manifests() its shards first")
+        for m in shards:
+            if m.n_remote():                    # global L4: the merge wrote the dictionary's LBA into every header the table lists
+                rb = m.remote_bases
+                lba = m.blob[(m.index["lba"][rb["slot"]].astype(np.int64) * m.lba_unit)[:, None] + np.arange(4)[None, :]].copy().view("<u4")[:, 0]
+                want = np.array([shards[int(r)].index["lba"][int(b)] for r, b in zip(rb["shard"], rb["base_slot"])], np.uint32)
+                if not np.array_equal(lba, want):
+                    raise ReadError("the store has unresolved cross-shard DeltaChunk headers: merge_manifests() its shards first")
         self.dev = device
-        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).copy()).to(dt).to(device)
         sb = np.cumsum([0] + [len(m.index) for m in shards])
         bb = np.cumsum([0] + [int(m.blob.size) for m in shards])
         ps = [parse_manifest(m) for m in shards]
@@ -316,10 +269,9 @@ class StoreReader:
             order, new_of_old = dep
             self.base = np.where(self.base >= 0, new_of_old[np.maximum(self.base, 0)], -1)[order]
             self.kind, self.stream_off, self.stream_len, self.raw_len = self.kind[order], self.stream_off[order], self.stream_len[order], self.raw_len[order]
-        blobs = [t(m.blob, torch.uint8) for m in shards if m.blob.size]
+        blobs = [to_device(m.blob, torch.uint8, device) for m in shards if m.blob.size]
         self.blob = blobs[0] if len(blobs) == 1 else torch.cat(blobs) if blobs else torch.zeros(1, dtype=torch.uint8, device=device)
         self.slot, lens = chunk_slots(shards)
-        from .manifest import stream_order
         perm = stream_order(shards)             # a multi-rank stream's store: requests address the stream, whose chunks interleave the shards
         if perm is not None:
             self.slot, lens = self.slot[perm], lens[perm]
@@ -327,8 +279,12 @@ class StoreReader:
         self.sha = np.concatenate([m.index["sha256"] for m in shards]) if shards else np.zeros((0, 32), np.uint8)
         if dep is not None:
             self.slot, self.sha = new_of_old[self.slot], self.sha[order]
+        self.has_digests = bool(self.sha.any())      # a store written without L3 carries none: nothing to verify against
         self.n_bytes = int(self.cuts[-1])
         self.last = {}
+
+    def _t(self, a, dt) -> torch.Tensor:
+        return to_device(a, dt, self.dev)
 
     def closure(self, slots: np.ndarray) -> np.ndarray:
         """The stored slots needed to decode `slots`: themselves plus, transitively, the dictionaries of the DELTA records
@@ -343,9 +299,34 @@ class StoreReader:
                 need = np.union1d(need, frontier)
         return need
 
+    def decode(self, slots: np.ndarray | None = None, verify: bool = True):
+        """ONE hmse_l1_inflate over the stored slots `slots` — ascending and closed under dictionaries (closure()); None: every
+        record — -> (raw bytes back to back, raw_off int64[len + 1]).  Dictionaries are renumbered into the subset; `verify`
+        checks every decoded record's SHA-256 (where the store carries digests)."""
+        pick = (lambda a: a) if slots is None else (lambda a: a[slots])
+        base = pick(self.base)
+        if slots is not None:
+            base = np.where(base >= 0, np.searchsorted(slots, np.maximum(base, 0)), -1)
+        t = self._t
+        raw, raw_off, _ = ops.l1_inflate(self.blob, t(pick(self.stream_off), torch.int64), t(pick(self.kind), torch.uint8), t(base, torch.int64),
+                                         t(pick(self.raw_len), torch.int64), stream_len=t(pick(self.stream_len), torch.int32))
+        if verify and self.has_digests:
+            verify_digests(raw, raw_off, t(pick(self.sha), torch.uint8))
+        return raw, raw_off
+
+    def read_all(self, verify: bool = True) -> torch.Tensor:
+        """The original corpus (README.md:1635-1669): every record inflated in one call, then ONE assembly pass lays out every chunk
+        from the slot its map entry names — its own shard's or, for a cross-shard POINTER, another's."""
+        t = self._t
+        raw, raw_off = self.decode(verify=False)
+        cuts = t(self.cuts, torch.int64)
+        data = ops.read_assemble(cuts, t(self.slot, torch.int64), raw_off, raw)
+        if verify and self.has_digests:
+            verify_digests(data, cuts, t(self.sha[self.slot], torch.uint8))
+        return data
+
     def read_ranges(self, ranges, verify: bool = True) -> list:
         """[(offset, length), ...] -> one uint8 tensor on the device per request (views into one buffer)."""
-        dev = self.dev
         if not len(ranges):
             return []
         r = np.asarray(ranges, np.int64).reshape(-1, 2)
@@ -360,17 +341,14 @@ class StoreReader:
         chunks = np.nonzero(touched)[0]
         slots = self.slot[chunks]
         need = self.closure(slots)                                                   # ascending global slot ids
-        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt).to(dev)
-        b = self.base[need]
-        base_sel = np.where(b >= 0, np.searchsorted(need, np.maximum(b, 0)), -1)      # dictionaries renumbered into the subset
-        raw, raw_off, _ = ops.l1_inflate(self.blob, t(self.stream_off[need], torch.int64), t(self.kind[need], torch.uint8), t(base_sel, torch.int64),
-                                         t(self.raw_len[need], torch.int64), stream_len=t(self.stream_len[need], torch.int32))
+        t = self._t
+        raw, raw_off = self.decode(need, verify=False)
         # the touched chunks, back to back, from the slots that hold them (POINTER: the target's)
         clen = self.cuts[chunks + 1] - self.cuts[chunks]
         tcuts = np.concatenate([[0], np.cumsum(clen)]).astype(np.int64)
         tcuts_d = t(tcuts, torch.int64)
         buf = ops.read_assemble(tcuts_d, t(np.searchsorted(need, slots), torch.int64), raw_off, raw)
-        if verify and len(self.sha) and self.sha.any():
+        if verify and self.has_digests:
             verify_digests(buf, tcuts_d, t(self.sha[slots], torch.uint8))
         pos = np.searchsorted(chunks, lo)                                              # request -> its first chunk's place in buf
         start = tcuts[np.minimum(pos, len(tcuts) - 1)] + (r[:, 0] - self.cuts[np.minimum(lo, len(self.cuts) - 2)])
@@ -378,6 +356,17 @@ class StoreReader:
                      "dictionaries_pulled_in": int(len(need) - len(np.unique(slots))), "bytes_decoded": int(self.raw_len[need].sum()),
                      "bytes_requested": int(r[:, 1].sum())}
         return [buf[int(s): int(s) + int(n)] for s, n in zip(start, r[:, 1])]
+
+
+def read_store(store: Store, device, verify: bool = True) -> torch.Tensor:
+    """A sharded store (one Manifest per shard, cross-shard pointers resolved by manifest.merge_manifests) -> the original corpus
+    in global chunk order (a multi-rank stream's store: in stream order), decoded on `device`."""
+    return StoreReader(store, device).read_all(verify)
+
+
+def read_manifest(m: Manifest, device, verify: bool = True) -> torch.Tensor:
+    """Manifest bytes (hmse_amd/manifest.py record formats) -> original data, decoded on `device`."""
+    return StoreReader(m, device).read_all(verify)
 
 
 def read_ranges(store, ranges, device, verify: bool = True) -> list:

@@ -24,7 +24,8 @@ import torch
 
 from . import ops
 from .config import KIND_DELTA, KIND_FULL, KIND_POINTER, IngestConfig
-from .manifest import PTR_UNRESOLVED, Manifest, Store
+from .manifest import Manifest, Store, merged_shards
+from .read import MAX_DELTA_DEPTH_LOG2, dependency_order, to_device as _t
 
 STRUCTURE, STREAM, DIGEST, DICTIONARY, HEADER, METADATA = 1, 2, 4, 8, 16, 32
 DAMAGE = STRUCTURE | STREAM | DIGEST | DICTIONARY | METADATA
@@ -92,21 +93,7 @@ class ScrubReport:
 
 # ---- metadata: trusted but checked -------------------------------------------------------------------------------------------
 def _shards(store) -> list:
-    if isinstance(store, Manifest):
-        if store.n_shards != 1:
-            raise ValueError(f"scrub: manifest shard {store.shard} of {store.n_shards} is one part of a sharded store: merge_manifests() the parts")
-        if store.n_remote():
-            raise ValueError("scrub: records of this manifest use dictionaries stored in other shards: scrub the merged store")
-        shards = [store]
-    elif isinstance(store, Store):
-        shards = list(store.shards)
-    else:
-        raise ValueError(f"scrub: a Manifest or a Store, not {type(store).__name__}")
-    for i, m in enumerate(shards):
-        if m.shard != i or m.n_shards != len(shards):
-            raise ValueError(f"scrub: the store's shard {i} is manifest shard {m.shard} of {m.n_shards}: not a merged store (merge_manifests)")
-    if any(((m.pointers["flags"] & PTR_UNRESOLVED) != 0).any() for m in shards):
-        raise ValueError("scrub: the store has unresolved cross-shard pointers: merge_manifests() its shards first")
+    shards = merged_shards(store, "scrub", lenient=True)
     if any(m.pieces is not None for m in shards) and not all(m.pieces is not None for m in shards):
         raise ValueError("scrub: only some shards carry stream pieces")
     return shards
@@ -249,11 +236,6 @@ def cut_deep(parent: np.ndarray, max_log2: int) -> np.ndarray:
 
 
 # ---- the device pass ------------------------------------------------------------------------------------------------------------
-def _t(a, dt, device):
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dt).to(device)
-
-
 def _records_pass(blob, p: _Plan, device):
     t = lambda a, dt: _t(a, dt, device)
     steps = int(max(np.diff(p.shard_slot).max(initial=0), 0)).bit_length()
@@ -276,7 +258,6 @@ class _Pass:
 
 def _scrub_pass(store, device, cfg=None, band_tables=None, timings=None) -> _Pass:
     from .gc import _Clock
-    from .read import MAX_DELTA_DEPTH_LOG2
     clock = _Clock(timings)
     p = plan(store)
     clock.lap("plan")
@@ -297,7 +278,6 @@ def _scrub_pass(store, device, cfg=None, band_tables=None, timings=None) -> _Pas
         status = t(st_h, torch.uint8)
         bad |= cyc
         parent = np.where(bad, -1, d_h)
-    from .read import dependency_order
     dep = dependency_order(parent)
     order = np.arange(n) if dep is None else dep[0]
     pos = np.arange(n) if dep is None else dep[1]
@@ -354,24 +334,12 @@ def _split_sidecar(buf: bytes):
     """-> (band-table section bytes, keys u32[n][bands], signatures u32[n][h], bands, band_bits) or None when unusable."""
     from . import bandtable
     try:
-        if buf[:8] != bandtable.MAGIC:
-            return None
-        ver, bands, band_bits, id_bytes, nid = struct.unpack_from("<IIIIQ", buf, 8)
-        o = 8 + struct.calcsize("<IIIIQ")
-        for _ in range(bands):
-            (nh,) = struct.unpack_from("<Q", buf, o)
-            o += 8 + 4 * nh + 3 * nid
-        if buf[o:o + 8] != b"HMSESIGS":
-            return None
-        (nhash,) = struct.unpack_from("<I", buf, o + 8)
-        want = o + 12 + 4 * nid * bands + 4 * nid * nhash
-        if len(buf) != want:
-            return None
-        keys = np.frombuffer(buf, "<u4", nid * bands, o + 12).reshape(nid, bands)
-        sig = np.frombuffer(buf, "<u4", nid * nhash, o + 12 + 4 * nid * bands).reshape(nid, nhash)
-        return buf[:o], keys, sig, bands, band_bits
-    except struct.error:
+        tables, band_bits, keys, sig = bandtable.split_sidecar(buf)
+    except (AssertionError, ValueError, struct.error):
         return None
+    if sig is None or len(buf) != len(tables) + 12 + keys.nbytes + sig.nbytes:
+        return None
+    return tables, keys, sig, keys.shape[1], band_bits
 
 
 def _check_sidecars(p: _Plan, band_tables, cfg: IngestConfig, rec_status, raw, raw_off, pos, dev) -> dict:

@@ -23,7 +23,7 @@ import torch
 
 from . import ops
 from .config import LAYER_L2, IngestConfig
-from .manifest import PTR_UNRESOLVED, Manifest, Store
+from .manifest import Store, merged_shards
 
 
 @dataclass
@@ -98,31 +98,12 @@ class SimilarityIndex:
         for a Store; the signatures come from its HMSESIGS section.  Without it the store is decoded on the GPU and every stored
         chunk signed by hmse_l4_minhash."""
         from . import bandtable, read
-        if isinstance(store, Manifest):
-            if store.pieces is not None:
-                raise ValueError("similarity: the manifest is one rank's part of a multi-rank stream (pieces)")
-            if store.n_shards != 1:
-                raise ValueError(f"similarity: shard {store.shard} of {store.n_shards} is one part of a sharded store: "
-                                 "merge_manifests() the parts and search the Store")
-            shards = [store]
-            sides = None if band_tables is None else [band_tables]
-        else:
-            shards = list(store.shards)
-            if any(m.pieces is not None for m in shards):
-                raise ValueError("similarity: a multi-rank stream store (pieces) is not searchable")
-            base = 0
-            for i, m in enumerate(shards):
-                if m.shard != i or m.n_shards != len(shards) or m.chunk_base != base:
-                    raise ValueError(f"similarity: the store's shard {i} is manifest shard {m.shard} of {m.n_shards} at chunk "
-                                     f"{m.chunk_base}: not a merged store (merge_manifests)")
-                base += len(m.chunk_map)
-            if isinstance(band_tables, (bytes, bytearray, memoryview)) and len(shards) == 1:
-                band_tables = [band_tables]
-            if band_tables is not None and len(band_tables) != len(shards):
-                raise ValueError(f"similarity: one band-table sidecar per shard ({len(shards)}), got {len(band_tables)}")
-            sides = band_tables
-        if any(((m.pointers["flags"] & PTR_UNRESOLVED) != 0).any() for m in shards):
-            raise ValueError("similarity: the store has unresolved cross-shard pointers: merge_manifests() its shards first")
+        shards = merged_shards(store, "similarity")
+        if isinstance(band_tables, (bytes, bytearray, memoryview)) and len(shards) == 1:
+            band_tables = [band_tables]
+        if band_tables is not None and len(band_tables) != len(shards):
+            raise ValueError(f"similarity: one band-table sidecar per shard ({len(shards)}), got {len(band_tables)}")
+        sides = band_tables
         slot, lens = read.chunk_slots(shards)
         u = sum(len(m.index) for m in shards)
         if len(slot) and (slot.max() >= u or (np.bincount(slot, minlength=u) == 0).any()):

@@ -119,19 +119,19 @@ class StreamIngest:
         from . import bandtable, read
         from .config import KIND_POINTER
         st = StreamIngest(cfg, capacity_bytes, device, max_chunks, graph=graph)
-        data = read.read_manifest(m, device, verify=verify)
+        rd = read.StoreReader(m, device)         # the manifest opened once: record headers parsed, the blob in HBM
+        data = rd.read_all(verify)
         n = data.numel()
         if n % cfg.seg_size:
             raise ValueError("the stored stream ends inside a segment: nothing can be appended to it")
         if n > st.data.numel():
             raise ValueError("stream capacity exceeded")
         st.data[:n] = data
-        p = read.parse_manifest(m)
-        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).copy()).to(dt).to(device)
+        t = lambda a, dt: read.to_device(a, dt, device)
         nc, nu = len(m.chunk_map), len(m.index)
         if nc > st.max_chunks or nu > st.max_unique:
             raise ValueError("stream index capacity exceeded")
-        torch.cumsum(t(p["raw_len"][m.chunk_map["slot"]], torch.int64), 0, out=st._cuts[1: nc + 1])
+        st._cuts[1: nc + 1] = t(rd.cuts[1:], torch.int64)
         st._digests[:nc] = t(m.index["sha256"][m.chunk_map["slot"]], torch.uint8)
         ops.l3_index_update(st._digests, 0, nc, st._first_occ, st._refcount, st._l3_table)
         own = np.nonzero(m.chunk_map["kind"] != KIND_POINTER)[0]
@@ -152,16 +152,16 @@ class StreamIngest:
         else:
             st._sig[:nu] = ops.l4_minhash(st.data[:n], st.cuts, cfg, st.uniq_ids)
             ops.l4_lsh_update(st._sig, 0, nu, cfg, st._band_keys, st._base, st._lsh_tables)
-        st._kind[:nu] = t(p["kind"], torch.uint8)
+        st._kind[:nu] = t(rd.kind, torch.uint8)
         # dense copy of the stored streams (the blob aligns records to lba_unit and prefixes DELTA records with a header)
-        s_len = t(p["stream_len"], torch.int64)
+        s_len = t(rd.stream_len, torch.int64)
         torch.cumsum(s_len, 0, out=st._stream_off[1: nu + 1])
         st.stream_bytes = int(st._stream_off[nu].item())
         src = torch.arange(st.stream_bytes, dtype=torch.int64, device=device) + \
-            torch.repeat_interleave(t(p["stream_off"], torch.int64) - st._stream_off[:nu], s_len)
-        st.stream_parts = [t(m.blob, torch.uint8)[src]]
+            torch.repeat_interleave(t(rd.stream_off, torch.int64) - st._stream_off[:nu], s_len)
+        st.stream_parts = [rd.blob[src]]
         # the records must agree with what this build derives from the loaded index
-        mb = t(p["base"], torch.int64)
+        mb = t(rd.base, torch.int64)
         if not bool(((st.kind != 2) | (mb == st.base)).all()):
             raise ValueError("a DELTA record's dictionary is not the LSH base of its chunk under this configuration")
         st.n_bytes = st.n_done = n

@@ -92,7 +92,7 @@ def test_drop_ranges_maps_aligned_ranges_to_segments(monkeypatch):
     assert gc.segments_of_ranges(so, [(SEG, 0), (20480, SEG), (20480, SEG)]) == [2]
     seen = {}
 
-    def fake(m, drop, cfg, device, band_tables=None, seg_off=None, verify=True, timings=None):
+    def fake(m, drop, cfg, device, band_tables=None, seg_off=None, global_l4=False, verify=True, timings=None):
         seen.update(drop=drop, seg_off=np.asarray(seg_off).tolist())
         return "ok"
     monkeypatch.setattr(gc, "drop_segments", fake)

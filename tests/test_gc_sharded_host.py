@@ -123,3 +123,34 @@ def test_refuses_a_shard_whose_map_disagrees_with_its_index():
     st.shards[2] = Manifest(1, m.index, cmap, m.pointers, m.blob, 2, 3, m.chunk_base)
     with pytest.raises(ValueError, match="disagree|outside"):
         gc.drop_segments(st, [0], _cfg(), DEV)
+
+
+def test_merged_shards_is_the_one_store_check():
+    """manifest.merged_shards: what GC and near-duplicate search refuse, what scrub (lenient) leaves to its report, and the prefix."""
+    import dataclasses
+    from hmse_amd.manifest import PTR_UNRESOLVED, REMOTE_BASE_DTYPE, merged_shards
+    st = _store()
+    lone = _shard(5, 0, 1, 0)
+    for lenient in (False, True):
+        assert merged_shards(st, "x", lenient) == st.shards and merged_shards(lone, "x", lenient) == [lone]
+        with pytest.raises(ValueError, match="^who: shard 2 of 3 is one part of a sharded store: merge_manifests"):
+            merged_shards(st.shards[2], "who", lenient)
+        with pytest.raises(ValueError, match="^who: a Manifest or a Store, not bytes"):
+            merged_shards(b"", "who", lenient)
+        with pytest.raises(ValueError, match="shard 1 is manifest shard 2 of 3: not a merged store of 3 shards"):
+            merged_shards(Store([st.shards[0], st.shards[2], st.shards[1]]), "x", lenient)
+        with pytest.raises(ValueError, match="remote_bases"):
+            merged_shards(dataclasses.replace(lone, remote_bases=np.zeros(1, REMOTE_BASE_DTYPE)), "x", lenient)
+        ptr = np.zeros(1, POINTER_DTYPE)
+        ptr["flags"] = PTR_UNRESOLVED
+        with pytest.raises(ValueError, match="^who: the store has unresolved cross-shard pointers"):
+            merged_shards(Store([st.shards[0], dataclasses.replace(st.shards[1], pointers=ptr), st.shards[2]]), "who", lenient)
+    # only the readers of the (shard, local) chunk order refuse these three
+    moved = Store([st.shards[0], st.shards[1], dataclasses.replace(st.shards[2], chunk_base=7)])
+    pc = np.zeros(1, PIECE_DTYPE)
+    streamed = Store([dataclasses.replace(m, pieces=pc) for m in st.shards])
+    remote = Store([dataclasses.replace(lone, remote_bases=np.zeros(1, REMOTE_BASE_DTYPE))])
+    for bad, what in ((moved, "starts at chunk 7, not 35"), (streamed, "pieces"), (remote, "remote_bases")):
+        with pytest.raises(ValueError, match=what):
+            merged_shards(bad, "x")
+        assert merged_shards(bad, "x", lenient=True) == bad.shards

@@ -131,6 +131,22 @@ def test_gc_drop_nothing_and_drop_everything(variants, dev):
     assert read.read_manifest(type(out).from_bytes(out.to_bytes()), dev).numel() == 0
 
 
+def test_one_shard_inputs_share_one_body(variants, dev):
+    """A Manifest, a Store of that one shard, and a Manifest with global_l4=True (every dictionary of one shard is local: the scope
+    names nothing) give the same Manifest, the same sidecar and the same stats."""
+    from hmse_amd import gc, manifest
+    data, cfg, m, side = variants
+    for sc in (side, None):
+        out, out_side, st = gc.drop_segments(m, [0, 1, 2, 3], cfg, dev, band_tables=sc)
+        assert isinstance(out, manifest.Manifest) and isinstance(out_side, bytes)
+        for o2, side2, st2 in (gc.drop_segments(manifest.Store([m]), [0, 1, 2, 3], cfg, dev, band_tables=sc),
+                               gc.drop_segments(m, [0, 1, 2, 3], cfg, dev, band_tables=sc, global_l4=True)):
+            assert isinstance(o2, manifest.Manifest) and o2.to_bytes() == out.to_bytes() and side2 == out_side
+            shared = set(st) & set(st2)
+            assert {"chunks_after", "stored_after", "records_reused", "records_reencoded", "bytes_decoded", "blob_bytes_after"} <= shared
+            assert all(st[k] == st2[k] for k in shared)
+
+
 def test_retention_window_then_resume(dev):
     """Write with StreamIngest, drop the first batch, resume from the collected store and its sidecar, push two more batches:
     the result equals a one-shot ingest of (remainder + new batches)."""

@@ -271,6 +271,19 @@ def test_global_l4_three_shards_equal_the_one_shard_run(dev):
     assert sum(m.n_remote() for m in store.shards) == n_remote_delta
     assert torch.equal(read.read_store(store, dev, verify=True), d)
     assert manifest.reconstruct(store) == data.tobytes()
+    # the header refusal on its own: every pointer stays resolved, one record listed in remote_bases loses its base_lba — the full
+    # read and the opener behind range reads and GC refuse the store alike
+    import dataclasses
+    i = next(i for i, m in enumerate(store.shards) if m.n_remote())
+    ms = store.shards[i]
+    blob = ms.blob.copy()
+    pos = int(ms.index["lba"][ms.remote_bases["slot"][0]]) * ms.lba_unit
+    blob[pos: pos + 4] = 0xFF
+    bad = manifest.Store([dataclasses.replace(ms, blob=blob) if j == i else m for j, m in enumerate(store.shards)])
+    with pytest.raises(read.ReadError, match="unresolved cross-shard DeltaChunk headers"):
+        read.read_store(bad, dev)
+    with pytest.raises(read.ReadError, match="unresolved cross-shard DeltaChunk headers"):
+        read.StoreReader(bad, dev)
 
 
 def test_distributed_ingest_world_size_1_runs_rccl(dev):

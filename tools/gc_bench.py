@@ -3,8 +3,8 @@
 Ingests the corpus into a one-shard store (default config: 4 MiB segments) and its band-table sidecar, then collects two cases —
 10 % of the segments dropped, spread out (every 10th), and the oldest 25 % dropped (retention) — each with and without the sidecar.
 Every run is checked by identity (manifest bytes == fresh ingest of the remainder, packed) and timed per phase (a device sync
-between phases): plan, decode, minhash, lsh, reencode, gather, pack; the gather KERNEL's GB/s (hmse_profile event pair around the
-launch) counts its bytes read + written.
+between phases): plan, decode, minhash, lsh, reencode, gather, pack (build_manifest), sidecar (hmse_band_tables_write); the gather
+KERNEL's GB/s (hmse_profile event pair around the launch) counts its bytes read + written.
 The fresh ingest is timed the same way (ingest_shard + build_manifest).  Prints one JSON line."""
 import ctypes as C
 import json

@@ -1,4 +1,4 @@
-"""Garbage collection of a SHARDED store (hmse_amd.gc sharded path) against a fresh sharded ingest of the same remainder.
+"""Garbage collection of a SHARDED store (hmse_amd.gc, N > 1 shards) against a fresh sharded ingest of the same remainder.
     python tools/gc_sharded_bench.py [store MiB (1024)] [shards (4)] [corpus (wikipedia)] [--shard-local]
 Ingests the corpus into an N-shard store with ingest_shards_local (default config: 4 MiB segments; global L4 unless --shard-local)
 and its per-shard band-table sidecars, then collects the two cases of tools/gc_bench.py — 10 % of the segments dropped, spread out

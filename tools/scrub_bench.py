@@ -4,8 +4,8 @@ Ingests wiki-synth(seed) with the default configuration (ingest_shard) into a on
 around it (best of 3 after a warm-up): read_store(verify=True); scrub of the clean store; scrub of a copy with `--damaged` records
 each hit by one flipped byte; salvage of that copy; repair of it from a replica whose damage is disjoint.  hmse_scrub_records and
 hmse_scrub_attribute are timed by the library's device events (hmse_profile_enable) over the clean scrubs.  Where the time goes: one
-more clean scrub with per-phase timings (scrub(timings=...), a device sync between phases), and read_store's steps for a one-shard
-store run one by one with the same syncs (read_store_phases, a diagnostic copy of its sequence).  Writes one JSON file and prints it."""
+more clean scrub with per-phase timings (scrub(timings=...), a device sync between phases), and read_store's steps run one by one
+with the same syncs (read_store_phases).  Writes one JSON file and prints it."""
 import argparse
 import json
 import os
@@ -32,24 +32,17 @@ def timed(fn, reps=3):
 
 
 def read_store_phases(store, dev) -> dict:
-    """read.read_store(verify=True)'s steps for a one-shard store, in its order and with its host copies, timed one by one."""
+    """read.read_store(verify=True)'s steps (StoreReader.read_all), in its order, timed one by one."""
     out = {}
     clock = gc._Clock(out)
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).copy()).to(dt).to(dev)
-    m = store.shards[0]
-    p = read.parse_manifest(m)
-    clock.lap("parse_manifest")
-    blob = t(m.blob, torch.uint8)
-    clock.lap("upload")
-    raw, raw_off, _ = ops.l1_inflate(blob, t(p["stream_off"], torch.int64), t(p["kind"], torch.uint8), t(p["base"], torch.int64),
-                                     t(p["raw_len"], torch.int64), stream_len=t(p["stream_len"], torch.int32))
+    rd = read.StoreReader(store, dev)
+    clock.lap("open")                                              # headers parsed, blob uploaded
+    raw, raw_off = rd.decode(verify=False)
     clock.lap("inflate")
-    slot_g, lens = read.chunk_slots([m])
-    cuts = torch.zeros(len(lens) + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(t(lens, torch.int64), 0, out=cuts[1:])
-    data = ops.read_assemble(cuts, t(slot_g, torch.int64), raw_off, raw)
+    cuts = read.to_device(rd.cuts, torch.int64, dev)
+    data = ops.read_assemble(cuts, read.to_device(rd.slot, torch.int64, dev), raw_off, raw)
     clock.lap("assemble")
-    read.verify_digests(data, cuts, t(m.index["sha256"][slot_g], torch.uint8))
+    read.verify_digests(data, cuts, read.to_device(rd.sha[rd.slot], torch.uint8, dev))
     clock.lap("sha256_verify")
     return out
 
