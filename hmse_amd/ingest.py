@@ -40,6 +40,11 @@ class ShardResult:
     base_global: torch.Tensor | None = None   # global L4: int64 [u] GLOBAL stored-chunk index of the dictionary, -1 none
     u_base: int = 0                    # global L4: global stored-chunk index of this shard's first stored chunk
     u_bases: list | None = None        # global L4: u_base of every shard
+    # a multi-rank STREAM's shard (stream_dist / stream_gl4): the ranks' chunks interleave in the global (stream) order
+    gidx: torch.Tensor | None = None   # int64 [n] global chunk index of every local chunk
+    ug: torch.Tensor | None = None     # global-L4 stream: int64 [u] GLOBAL stored index of every stored chunk (None: any other result)
+    remote_bases: object | None = None        # global-L4 stream: manifest.REMOTE_BASE_DTYPE rows (slot, owner rank, owner's slot), None if there are none
+    pieces: object | None = None              # stream_dist.store_results: manifest.PIECE_DTYPE rows, where the shard's chunks sit in the stream order
 
 
 def fixed_cuts(n: int, cfg: IngestConfig, seg_off: torch.Tensor) -> torch.Tensor:
@@ -293,7 +298,7 @@ def shard_stats(r: ShardResult) -> dict:
     lens = r.cuts[1:] - r.cuts[:-1]
     unique_bytes = int(lens[r.uniq_ids].sum().item()) if n_unique else 0
     stored = int(r.streams.numel()) if r.streams is not None else unique_bytes
-    bsel = r.base_global if getattr(r, "base_global", None) is not None else r.base
+    bsel = r.base_global if r.base_global is not None else r.base
     lsh_hits = int((bsel >= 0).sum().item()) if bsel is not None else 0
     return {"bytes": r.n_bytes, "chunks": n_chunks, "unique": n_unique, "pointer": n_chunks - n_unique, "delta": n_delta,
             "lsh_hits": lsh_hits, "unique_bytes": unique_bytes, "stored_bytes": stored}

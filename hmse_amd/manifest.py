@@ -125,7 +125,7 @@ def pack_manifest_device(res, shard: int = 0, n_shards: int = 1, any_target: boo
     index = torch.empty((u, 40), dtype=torch.uint8, device=dev)
     cmap = torch.empty((n, 8), dtype=torch.uint8, device=dev)
     ptrs = torch.empty((n_ptr, 8), dtype=torch.uint8, device=dev)
-    ops.manifest_pack(res, shard, n_shards, getattr(res, "shard_bases", None), rec_off, unit, ptr_index, blob, index, cmap, ptrs, any_target=any_target)
+    ops.manifest_pack(res, shard, n_shards, res.shard_bases, rec_off, unit, ptr_index, blob, index, cmap, ptrs, any_target=any_target)
     return unit, blob, index, cmap, ptrs
 
 
@@ -133,9 +133,9 @@ def remote_base_table(res) -> np.ndarray | None:
     """DELTA records of a global-L4 shard whose dictionary is stored on another shard: (slot, shard, that shard's slot).
     Their DeltaChunk headers are packed unresolved (base_lba 0xFFFFFFFF); merge_manifests() fills them in."""
     import torch
-    if hasattr(res, "remote_bases"):      # a global-L4 STREAM's shard: its stored chunks interleave with the other ranks' in the
-        return res.remote_bases           # global numbering, the owner table comes with the result (stream_dist.GlobalL4StreamIngest)
-    bg = getattr(res, "base_global", None)
+    if res.ug is not None:                # a global-L4 STREAM's shard: its stored chunks interleave with the other ranks' in the global
+        return res.remote_bases           # numbering, the owner table (None: no remote dictionary) comes with the result (stream_common.remote_base_rows)
+    bg = res.base_global
     if bg is None:
         return None
     remote = (bg >= 0) & (res.base < 0) & (res.kind == KIND_DELTA)
@@ -154,7 +154,7 @@ def build_manifest(res, shard: int = 0, n_shards: int = 1) -> Manifest:
     """pack_manifest_device() + one device -> host copy per array: the host receives four finished arrays and only has to
     write() them.  A chunk whose first occurrence lives on another shard (sharded ingest) becomes a POINTER
     with an unresolved pointer record; merge_manifests() resolves those once every shard's manifest exists."""
-    pieces = getattr(res, "pieces", None)           # a multi-rank stream's shard (stream_dist.store_results): stream-order table,
+    pieces = res.pieces                             # a multi-rank stream's shard (stream_dist.store_results): stream-order table,
     unit, blob, index, cmap, ptrs = pack_manifest_device(res, shard, n_shards, any_target=pieces is not None)   # targets on any shard
     host = lambda t, dt: np.frombuffer(t.cpu().numpy().tobytes(), dt)
     return Manifest(unit, host(index, CHUNK_INDEX_DTYPE), host(cmap, MAP_DTYPE), host(ptrs, POINTER_DTYPE), blob.cpu().numpy(),

@@ -28,7 +28,7 @@ def reconstruct_shard(res, verify: bool = True) -> torch.Tensor:
     lens = cuts[1:] - cuts[:-1]
     if res.streams is None:
         raise ReadError("reconstruct_shard needs the L1 layer's streams")
-    if getattr(res, "base_global", None) is not None and bool(((res.base_global >= 0) & (res.base < 0)).any()):
+    if res.base_global is not None and bool(((res.base_global >= 0) & (res.base < 0)).any()):
         raise ReadError("records of this shard use dictionaries stored on other shards: read.reconstruct_shards decodes all shards together")
     raw, raw_off, _ = ops.l1_inflate(res.streams, res.stream_off, res.kind, res.base, lens[res.uniq_ids])
     slot_of = torch.full((n_chunks,), -1, dtype=torch.int64, device=dev)
@@ -52,7 +52,7 @@ def reconstruct_shards(results: list, verify: bool = True) -> list:
     DELTA record's dictionary — named by its global stored-chunk index — is any earlier record; then every shard's chunks
     are laid out from the slots their first occurrences name.  Returns the shards' data tensors, in order."""
     dev = results[0].cuts.device
-    if all(getattr(r, "ug", None) is not None for r in results):
+    if all(r.ug is not None for r in results):
         return _reconstruct_stream_global_l4(results, verify)
     u_counts = [int(r.uniq_ids.numel()) for r in results]
     u_bases = [sum(u_counts[:i]) for i in range(len(results))]
@@ -72,8 +72,7 @@ def reconstruct_shards(results: list, verify: bool = True) -> list:
     n_global = results[0].n_global
     slot_of_global = torch.full((n_global,), -1, dtype=torch.int64, device=dev)
     for r, ub in zip(results, u_bases):
-        g = getattr(r, "gidx", None)
-        own = g[r.uniq_ids] if g is not None else r.chunk_base + r.uniq_ids
+        own = r.gidx[r.uniq_ids] if r.gidx is not None else r.chunk_base + r.uniq_ids
         slot_of_global[own] = torch.arange(ub, ub + r.uniq_ids.numel(), dtype=torch.int64, device=dev)
     out = []
     for r in results:

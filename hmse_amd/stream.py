@@ -18,6 +18,8 @@ import torch
 from . import ops
 from .config import LAYER_L1, LAYER_L2, LAYER_L3, LAYER_L4, IngestConfig
 from .ingest import ShardResult, shard_stats
+from .stream_common import (PhaseGraphs, SizeEntry, chain_status_error, default_max_chunks, default_stream_capacity, deflate_ws_bytes, issue_copy,
+                            max_stored)
 
 
 class StreamIngest:
@@ -57,8 +59,8 @@ class StreamIngest:
         # once for `max_chunks` (default: twice the expected count at the configured average chunk size) and only its tail
         # is written by a batch; the L3 table and the four L4 band tables are updated in place (hmse_l3_index_update,
         # hmse_l4_lsh_update), so a batch costs the same whatever came before it.
-        self.max_chunks = int(max_chunks or (capacity_bytes // max(1, cfg.avg_size // 2) + capacity_bytes // cfg.seg_size + 64))
-        self.max_unique = min(self.max_chunks, 1 << 23)              # the band tables hold 2^24 slots at load <= 0.5
+        self.max_chunks = int(max_chunks or default_max_chunks(capacity_bytes, cfg))
+        self.max_unique = max_stored(self.max_chunks)
         mc, mu = self.max_chunks, self.max_unique
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
         self._cuts = z(mc + 1, torch.int64)
@@ -84,8 +86,9 @@ class StreamIngest:
         self.graph = bool(graph)
         if self.graph:
             self._state = torch.zeros(16, dtype=torch.int64, device=device)
-            self._streams = torch.empty(int(stream_capacity or (capacity_bytes // 2 + (64 << 20))), dtype=torch.uint8, device=device)
-            self._graphs: dict[int, tuple] = {}     # batch bytes -> (CUDAGraph, workspace, seg_off) once captured; None after the eager first batch
+            self._streams = torch.empty(int(stream_capacity or default_stream_capacity(capacity_bytes)), dtype=torch.uint8, device=device)
+            # per batch size: segment offsets and a chain workspace; the one enqueue of a batch is captured at the size's second use
+            self._graphs = PhaseGraphs(True, lambda n: SizeEntry(ops.segment_offsets(n, cfg.seg_size, device), ops.stream_workspace(n, cfg, device)))
             self._state_dirty = True                # host counters -> device state before the next chain call
 
     # views of the filled part of the index
@@ -181,8 +184,7 @@ class StreamIngest:
             if self.n_bytes + n > self._wcopy0 + self.window:
                 # this batch opens a new window at the buffer's start: everything enqueued so far may still read the old window's bytes
                 # (dictionaries), so it is processed first and the copy waits for it — the one batch per window whose copy does not overlap
-                while self.pending:
-                    self._process(*self.pending.pop(0))
+                self._drain()
                 done = torch.cuda.Event()
                 done.record()
                 self.copy_stream.wait_event(done)
@@ -190,18 +192,17 @@ class StreamIngest:
                 self._wstarts.append(self.n_bytes)
         elif self.n_bytes + n > self.data.numel():
             raise ValueError("stream capacity exceeded")
-        ev = torch.cuda.Event()
-        with torch.cuda.stream(self.copy_stream):
-            self.data[self.n_bytes - self._wcopy0: self.n_bytes - self._wcopy0 + n].copy_(host_batch, non_blocking=True)
-            ev.record(self.copy_stream)
-        while self.pending:  # batches issued before this one
-            self._process(*self.pending.pop(0))
+        ev = issue_copy(self.copy_stream, self.data, self.n_bytes - self._wcopy0, host_batch)
+        self._drain()           # batches issued before this one
         self.pending.append((self.n_bytes, n, ev))
         self.n_bytes += n
 
-    def finish(self) -> ShardResult:
+    def _drain(self) -> None:
         while self.pending:
             self._process(*self.pending.pop(0))
+
+    def finish(self) -> ShardResult:
+        self._drain()
         if self.graph and not self._state_dirty:
             self._read_state()
             streams = self._streams[: self.stream_bytes]
@@ -219,9 +220,7 @@ class StreamIngest:
         """The ONE host read of the chain: counts after the batches enqueued so far."""
         st = self._state.tolist()
         if st[7]:
-            raise ValueError(f"streaming chain status {st[7]:#x}: bit0 chunk capacity, bit1 stored-chunk capacity, bit2 L2 (the batch holds more cut candidates than the chain's fixed candidate list, or more chunks than its cut list: bytes that dense are ingested by ingest_shard or a graph=False stream, whose L2 call is run again with a larger list), bit3 exchange row, bit4 workspace not initialised, bit5 state block inconsistent ([8] != [1] on one rank), "
-                             "bits 8.. DEFLATE (0x100 stream capacity, 0x200 workspace); the failing batch and every later one were dropped "
-                             f"({st[0]} bytes / {st[1]} chunks are intact)")
+            raise chain_status_error(st[7], intact=f" ({st[0]} bytes / {st[1]} chunks are intact)")
         self.n_done, self.n_chunks, self.n_unique, self.stream_bytes = st[0], st[1], st[3], st[5]
 
     def _chain_call(self, n: int, seg_off: torch.Tensor, ws: torch.Tensor) -> None:
@@ -230,7 +229,6 @@ class StreamIngest:
                          self._stream_off, self._streams, ws, data_origin=self._wproc0)
 
     def _process_chain(self, off: int, n: int, copied: torch.cuda.Event) -> None:
-        dev = self.dev
         if self._state_dirty:   # first chain call (possibly after resume()): host counters -> device state
             self._chain_s0 = self.stream_bytes
             if self.n_chunks == 0:
@@ -245,22 +243,10 @@ class StreamIngest:
             self._wproc0 = self._wstarts.pop(0)
             self.window_starts.append(self._wproc0)
             ops.l4_lsh_update(self._sig, 0, 0, self.cfg, self._band_keys, self._base, self._lsh_tables)
-            self._graphs = {k: (None, v[1], v[2]) for k, v in self._graphs.items()}
-        entry = self._graphs.get(n, 0)
-        if entry == 0:          # first batch of this size: plain enqueue (also sets the kernels' attributes before any capture)
-            seg_off = ops.segment_offsets(n, self.cfg.seg_size, dev)
-            ws = ops.stream_workspace(n, self.cfg, dev)
-            self._chain_call(n, seg_off, ws)
-            self._graphs[n] = (None, ws, seg_off)
-        else:
-            g, ws, seg_off = entry
-            if g is None:       # second batch of this size: capture the enqueue once ...
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._chain_call(n, seg_off, ws)
-                self._graphs[n] = (g, ws, seg_off)
-            g.replay()          # ... and from then on every batch of this size is one graph launch
+            self._graphs.drop_graphs()
+        e = self._graphs.entry(n)
+        self._graphs.run(n, "chain", lambda: self._chain_call(n, e.seg_off, e.ws))
+        self._graphs.end_batch(n)
         self.n_done = off + n
         self._n_chain_batches += 1
         if self.poll_status_every and self._n_chain_batches % self.poll_status_every == 0:
@@ -276,8 +262,7 @@ class StreamIngest:
             host, _, nb = self._polls.pop(0)
             st = int(host.item())
             if st:
-                raise ValueError(f"streaming chain status {st:#x} (polled after batch {nb}): bit0 chunk capacity, bit1 stored-chunk capacity, "
-                                 "bit2 L2 (more cut candidates than the chain's fixed candidate list holds, or more chunks than its cut list), bits 8.. DEFLATE (0x100 stream capacity, 0x200 workspace); the failing batch and every later one were dropped")
+                raise chain_status_error(st, f" (polled after batch {nb})")
 
     # ------------------------------------------------------------------ one batch, host-sized launches (graph=False)
     def _process(self, off: int, n: int, copied: torch.cuda.Event) -> None:
@@ -310,9 +295,9 @@ class StreamIngest:
         base_new = self._base[u_old: u_old + nu]
         # L1: the dictionary may be a chunk of an earlier batch -> bases as chunk indices
         base_chunk = torch.where(base_new >= 0, self._uniq[base_new.clamp(min=0)], base_new)
-        # one workspace for every batch, sized for the worst case of this batch (every chunk stored, every one with a dictionary):
-        # a fresh multi-GB allocation per batch synchronises the device and stalls the copy/compute overlap
-        worst = (5 * n + 1600 * n_new) + ops.workspace_bytes(ops.STAGE_DEFLATE, n_new, cfg) + (1 << 20)
+        # one workspace for every batch, sized for the worst case of this batch: a fresh multi-GB allocation per batch synchronises
+        # the device and stalls the copy/compute overlap
+        worst = deflate_ws_bytes(n, n_new, cfg)
         if self._ws is None or self._ws.numel() < worst:
             self._ws = None
             self._ws = torch.empty(worst, dtype=torch.uint8, device=dev)

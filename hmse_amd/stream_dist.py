@@ -17,117 +17,37 @@ one-shot ingest (ingest.ingest_shard(distributed=True)) — which is the one-bat
 read happens between the stages; with graph=True phase A and phase B of a piece size are captured into two hipGraphs at their
 second use and replayed from then on (the collective stays an ordinary stream-ordered RCCL call between the two replays).
 
-`exchange(row) -> rows` replaces the collective: tests/ and ingest-on-one-GPU emulations drive several ranks in lock step
-(stream_shards_local).  The oracle of this definition is tests/test_gpu_stream_dist.py::oracle_stream_pipeline.
+tests/ and ingest-on-one-GPU emulations drive several ranks in lock step inside one process, without collectives
+(stream_shards_local; stream_common.RankStream.lockstep).  The oracle of this definition is tests/test_gpu_stream_dist.py::oracle_stream_pipeline.
 """
 from __future__ import annotations
+
+import os
 
 import torch
 
 from . import ops
-from .config import LAYER_L1, LAYER_L2, LAYER_L3, LAYER_L4, IngestConfig
-from .ingest import ShardResult, shard_stats
+from .config import IngestConfig
+from .ingest import ShardResult
+from .stream_common import all_gather_rows, deal_batch  # noqa: F401  (part of this module's surface: tests/ and tools/ call them here)
+from .stream_common import CapturedRankStream, RankStream, deflate_ws_bytes, lockstep_ranks, max_stored, remote_base_rows, serve_chunks, serve_requests
+
+_DEBUG_SYNC = os.environ.get("HMSE_STREAM_DEBUG_SYNC") == "1"
 
 
-import os as _os
-_DEBUG_SYNC = _os.environ.get("HMSE_STREAM_DEBUG_SYNC") == "1"
-
-
-def deal_batch(batch_bytes: int, world: int, seg_size: int) -> list:
-    """Piece boundaries of a global batch of `batch_bytes`: contiguous runs of whole segments, rank r gets segments
-    [r S / R, (r + 1) S / R) of the batch's S segments (the last segment may be partial: only the stream's last batch)."""
-    n_seg = -(-batch_bytes // seg_size)
-    b = [min(batch_bytes, (r * n_seg // world) * seg_size) for r in range(world)] + [batch_bytes]
-    return b
-
-
-def all_gather_rows(row: torch.Tensor, world: int, group=None, out: torch.Tensor | None = None) -> torch.Tensor:
-    """THE collective of a multi-rank stream's batch: all-gather of the ranks' fixed-size exchange rows, in rank order.
-    RCCL over xGMI: device to device, stream-ordered, no host read (1 GiB pieces: 16.8 MB per rank and batch).  gloo (the CPU
-    tests and the one-GPU rehearsal): staged through host memory."""
-    import torch.distributed as dist
-    if out is None:
-        out = torch.empty(world * row.numel(), dtype=torch.uint8, device=row.device)
-    if dist.get_backend(group) == "gloo":
-        rows = torch.empty(world * row.numel(), dtype=torch.uint8)
-        dist.all_gather_into_tensor(rows, row.cpu(), group=group)
-        out.copy_(rows)
-    else:
-        dist.all_gather_into_tensor(out, row, group=group)
-    return out
-
-
-class DistStreamIngest:
+class DistStreamIngest(CapturedRankStream):
     """This rank's side of a stream sharded over `world` ranks.  Every rank pushes ITS piece of every global batch, in the
     same order (a rank with no bytes in a batch pushes an empty tensor) — the per-batch exchange is a collective."""
 
     def __init__(self, cfg: IngestConfig, capacity_bytes: int, piece_bytes: int, device, world: int, rank: int,
                  max_chunks_global: int | None = None, max_chunks: int | None = None, stream_capacity: int | None = None,
-                 graph: bool = True, group=None, exchange=None, always_exchange: bool = False):
-        if cfg.layers != (LAYER_L1 | LAYER_L2 | LAYER_L3 | LAYER_L4):
-            raise ValueError("DistStreamIngest runs the full L1-L4 pipeline")
-        if piece_bytes <= 0 or piece_bytes % cfg.seg_size:
-            raise ValueError("piece_bytes (the nominal piece size) must be a positive multiple of seg_size")
-        if not 0 <= rank < world <= 256:
-            raise ValueError("0 <= rank < world <= 256")
-        self.cfg, self.dev, self.world, self.rank, self.group = cfg, device, int(world), int(rank), group
-        self.cap_bytes = int(piece_bytes)
-        self.data = torch.empty(int(capacity_bytes), dtype=torch.uint8, device=device)
-        self.n_bytes = 0
-        self.copy_stream = torch.cuda.Stream(device=device)
-        self.pending: list[tuple[int, int, torch.cuda.Event]] = []
-        per = max(1, cfg.avg_size // 2)
-        self.max_chunks = int(max_chunks or (capacity_bytes // per + capacity_bytes // cfg.seg_size + 64))
-        self.max_chunks_g = int(max_chunks_global or self.max_chunks * world)
-        self.max_unique = min(self.max_chunks, 1 << 23)
-        mc, mg, mu = self.max_chunks, self.max_chunks_g, self.max_unique
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
-        # this rank's chunks
-        self._cuts = z(mc + 1, torch.int64)
-        self._gidx = z(mc, torch.int64)                       # local chunk -> global chunk index
-        self._uniq = z(mu, torch.int64)                       # local ids of the chunks this rank stores, ascending
-        self._sig = torch.empty((mu, cfg.n_hashes), dtype=torch.int32, device=device)
-        self._band_keys = z((mu, cfg.bands), torch.int32)
-        self._base = z(mu, torch.int64)
-        self._kind = z(mu, torch.uint8)
-        self._stream_off = z(mu + 1, torch.int64)
-        self._lsh_tables = torch.empty((cfg.bands, ops.l4_lsh_slots(mu)), dtype=torch.int32, device=device)
-        self._streams = torch.empty(int(stream_capacity or (capacity_bytes // 2 + (64 << 20))), dtype=torch.uint8, device=device)
-        # the global index: identical on every rank
-        self._digests_g = torch.empty((mg, 32), dtype=torch.uint8, device=device)
-        self._first_occ_g = z(mg, torch.int64)
-        self._refcount_g = z(mg, torch.int32)
-        self._l3_table = torch.empty(ops.l3_index_slots(mg), dtype=torch.int32, device=device)
-        ops.l3_index_update(self._digests_g, 0, 0, self._first_occ_g, self._refcount_g, self._l3_table)     # clears the table
+                 graph: bool = True, group=None, always_exchange: bool = False):
+        super().__init__(cfg, capacity_bytes, piece_bytes, device, world, rank, group, max_chunks, max_chunks_global,
+                         stream_capacity=stream_capacity, graph=graph, always_exchange=always_exchange, before=self._debug_sync if _DEBUG_SYNC else None)
+        self._lsh_tables = torch.empty((cfg.bands, ops.l4_lsh_slots(self.max_unique)), dtype=torch.int32, device=device)    # this rank's band tables
         ops.l4_lsh_update(self._sig, 0, 0, cfg, self._band_keys, self._base, self._lsh_tables)               # clears the tables
-        self._state = torch.zeros(16, dtype=torch.int64, device=device)
-        self._host_error = None
-        self._ws = ops.stream_workspace(self.cap_bytes, cfg, device)
-        self.row_bytes = ops.stream_row_bytes(self.cap_bytes, cfg)
-        self._row = torch.zeros(self.row_bytes, dtype=torch.uint8, device=device)
-        self._rows = torch.zeros(self.world * self.row_bytes, dtype=torch.uint8, device=device)
-        self.graph = bool(graph)
-        self._graphs: dict[int, list] = {}      # piece bytes -> [seg_off, graph A or None, graph B or None, uses]
-        self._exchange = exchange
-        self._always_exchange = bool(always_exchange)    # world size 1 still runs the collective (hardware rehearsal of the graph / RCCL interleaving)
-        self.n_batches = 0
-
-    # ------------------------------------------------------------------ the exchange step
-    def _all_gather(self, row: torch.Tensor) -> torch.Tensor:
-        if self._exchange is not None:
-            return self._exchange(row)
-        if self.world == 1 and not self._always_exchange:
-            return row
-        return all_gather_rows(row, self.world, self.group, out=self._rows)
 
     # ------------------------------------------------------------------ the two phases (enqueue only)
-    def _entry(self, n: int) -> list:
-        e = self._graphs.get(n)
-        if e is None:
-            e = [ops.segment_offsets(n, self.cfg.seg_size, self.dev) if n else None, None, None, 0]
-            self._graphs[n] = e
-        return e
-
     def _call_hash(self, n: int, seg_off) -> None:
         ops.stream_piece_hash(self.data, n, self.cap_bytes, seg_off, self.cfg, self._state, self._cuts, self.max_chunks, self._row, self._ws)
 
@@ -137,110 +57,41 @@ class DistStreamIngest:
                                 self.max_unique, self._sig, self._band_keys, self._base, self._lsh_tables, self._kind, self._stream_off,
                                 self._streams, self._ws)
 
-    def _run(self, which: int, n: int, fn) -> None:
-        """First use of a piece size: plain enqueue (also sets the kernels' attributes before any capture); second use:
-        capture into a hipGraph; from then on: replay."""
-        e = self._entry(n)
-        if _DEBUG_SYNC:     # HMSE_STREAM_DEBUG_SYNC=1: localise a device fault to (rank, batch, phase) — diagnostics only
-            import sys
-            torch.cuda.synchronize()
-            cap = (self.row_bytes - 32) // 32
-            o = (((cap + 1) * 8 + 255) // 256) * 256
-            l2o = o + 512 + 2 * ((cap * 8 + 255) // 256 * 256) + 256 + (((cap + 1) * 8 + 255) // 256) * 256 + ((cap + 255) // 256) * 256 + 256 + ((self.row_bytes + 255) // 256) * 256
-            print(f"[stream_dist] rank {self.rank} batch {self.n_batches} phase {'AB'[which - 1]} n={n} state={self._state.tolist()[:11]} n_cuts={self._ws[o:o + 8].view(torch.int64).item()} "
-                  f"l2_status={self._ws[o + 256:o + 260].view(torch.int32).item()} l2hdr={self._ws[l2o:l2o + 32].view(torch.int64).tolist()}", file=sys.stderr, flush=True)
-        if not self.graph or e[3] < 1:
-            fn()
-        else:
-            if e[which] is None:
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    fn()
-                e[which] = g
-            e[which].replay()
+    def _debug_sync(self, phase: str, n: int) -> None:
+        """HMSE_STREAM_DEBUG_SYNC=1: localise a device fault to (rank, batch, phase) — diagnostics only."""
+        import sys
+        torch.cuda.synchronize()
+        cap = (self.row_bytes - 32) // 32
+        o = (((cap + 1) * 8 + 255) // 256) * 256
+        l2o = o + 512 + 2 * ((cap * 8 + 255) // 256 * 256) + 256 + (((cap + 1) * 8 + 255) // 256) * 256 + ((cap + 255) // 256) * 256 + 256 + ((self.row_bytes + 255) // 256) * 256
+        print(f"[stream_dist] rank {self.rank} batch {self.n_batches} phase {phase} n={n} state={self._state.tolist()[:11]} n_cuts={self._ws[o:o + 8].view(torch.int64).item()} "
+              f"l2_status={self._ws[o + 256:o + 260].view(torch.int32).item()} l2hdr={self._ws[l2o:l2o + 32].view(torch.int64).tolist()}", file=sys.stderr, flush=True)
 
     def hash_piece(self, n: int) -> torch.Tensor:
         """Phase A for the next piece (its bytes are at data[state.off ..)): returns this rank's exchange row."""
-        e = self._entry(n)
-        self._run(1, n, lambda: self._call_hash(n, e[0]))
+        seg_off = self._graphs.entry(n).seg_off
+        self._graphs.run(n, "A", lambda: self._call_hash(n, seg_off))
         return self._row
 
     def encode_piece(self, n: int, rows: torch.Tensor) -> None:
         """Phase B: `rows` = the rows of all ranks in rank order (a tensor whose address is stable across batches when graphs are on)."""
-        if rows.data_ptr() != self._rows.data_ptr() and not (self.world == 1 and rows.data_ptr() == self._row.data_ptr()):
-            self._rows.copy_(rows.reshape(-1))
-            rows = self._rows
-        self._run(2, n, lambda: self._call_encode(n, rows))
-        self._entry(n)[3] += 1
+        rows = self._stable(rows, self._row, self._rows)
+        self._graphs.run(n, "B", lambda: self._call_encode(n, rows))
+        self._graphs.end_batch(n)
         self.n_batches += 1
-
-    # ------------------------------------------------------------------ feeding
-    def push(self, host_piece: torch.Tensor) -> None:
-        """Issue the host -> HBM copy of this rank's piece of the next global batch, then process the piece whose copy was
-        issued by the previous push (its kernels overlap this copy).  COLLECTIVE: every rank pushes once per global batch."""
-        n = host_piece.numel()
-        err = None
-        if n > self.cap_bytes:
-            err = "a piece may not exceed the stream's nominal piece size"
-        elif self.n_bytes % self.cfg.seg_size:
-            err = "only a rank's last piece may end inside a segment"
-        elif self.n_bytes + n > self.data.numel():
-            err = "stream capacity exceeded"
-        if err:
-            # A rank that raised here alone would leave its peers blocked in this batch's all-gather (ADVICE r3).  Instead the piece
-            # is refused THROUGH the chain: sticky status bit 6 on the device (phase A then reports 0 chunks, every later batch of
-            # this rank is a no-op), the rank keeps taking part in the collectives with empty rows, and read_state()'s
-            # all-reduce(MAX) of the status makes EVERY rank raise at finish() — this one with the reason.
-            self._host_error = self._host_error or err
-            n, host_piece = 0, host_piece[:0]
-        ev = torch.cuda.Event()
-        with torch.cuda.stream(self.copy_stream):
-            if n:
-                self.data[self.n_bytes: self.n_bytes + n].copy_(host_piece, non_blocking=True)
-            ev.record(self.copy_stream)
-        while self.pending:
-            self._process(*self.pending.pop(0))
-        if err:
-            self._state[7:8] |= 64      # (behind the piece pushed before, which is still good)
-        self.pending.append((self.n_bytes, n, ev))
-        self.n_bytes += n
 
     def _process(self, off: int, n: int, copied: torch.cuda.Event) -> None:
         torch.cuda.current_stream().wait_event(copied)
-        row = self.hash_piece(n)
-        rows = self._all_gather(row)
+        rows = self._gather(self.hash_piece(n), self._rows)
         self.encode_piece(n, rows)
 
     # ------------------------------------------------------------------ results
-    def read_state(self, check: bool = True) -> list:
-        st = self._state.tolist()
-        status = st[7]
-        if check and self.world > 1 and self._exchange is None:
-            # a failed rank must fail the whole stream: its chunks are missing from every rank's index
-            import torch.distributed as dist
-            t = torch.tensor([status], dtype=torch.int64, device="cpu" if dist.get_backend(self.group) == "gloo" else self.dev)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
-            status = max(status, int(t.item()))
-        if check and status:
-            raise ValueError(f"streaming chain status {status:#x} on some rank: bit0 chunk capacity, bit1 stored-chunk capacity, bit2 L2, bit3 "
-                             "exchange row, bit4 workspace not initialised, bit5 state block inconsistent, bit6 a piece refused by push()"
-                             + (f" (this rank: {self._host_error})" if self._host_error else "")
-                             + ", bits 8.. DEFLATE (0x100 stream capacity, 0x200 workspace); the failing batch and every later one were dropped")
-        return st
-
     def finish(self, check: bool = True) -> ShardResult:
-        while self.pending:
-            self._process(*self.pending.pop(0))
+        self._drain()
         st = self.read_state(check)
-        n_done, n_chunks, n_unique, s_bytes, n_global = st[0], st[1], st[3], st[5], st[8]
-        gidx = self._gidx[:n_chunks]
-        res = ShardResult(n_done, self._cuts[: n_chunks + 1], self._digests_g[gidx], 0, n_global, self._first_occ_g[gidx], self._refcount_g[gidx],
-                          self._uniq[:n_unique], self._sig[:n_unique], self._band_keys[:n_unique], self._base[:n_unique], self._streams[:s_bytes],
-                          self._stream_off[: n_unique + 1], self._kind[:n_unique])
-        res.gidx = gidx
-        res.stats = shard_stats(res)
-        return res
+        n_unique = st[3]
+        return self._result(st[0], st[1], st[8], self._uniq[:n_unique], self._sig[:n_unique], self._band_keys[:n_unique], self._base[:n_unique],
+                            self._streams[: st[5]], self._stream_off[: n_unique + 1], self._kind[:n_unique])
 
 
 def stream_shards_local(batches: list, cfg: IngestConfig, world: int, device, piece_bytes: int | None = None, graph: bool = True,
@@ -248,25 +99,13 @@ def stream_shards_local(batches: list, cfg: IngestConfig, world: int, device, pi
     """A `world`-rank stream with every rank on THIS GPU, in lock step: phase A of every rank, the rows concatenated as the
     all-gather would deliver them, phase B of every rank — per global batch.  `batches`: host uint8 tensors (the global
     batches, whole segments except the last).  Each result is what the rank would hold after DistStreamIngest.finish()."""
-    seg = cfg.seg_size
-    bounds = [deal_batch(b.numel(), world, seg) for b in batches]
-    pb = piece_bytes or max(max(bd[r + 1] - bd[r] for r in range(world)) for bd in bounds)
-    pb = -(-pb // seg) * seg
-    local_total = [sum(bd[r + 1] - bd[r] for bd in bounds) for r in range(world)]
-    ranks = [DistStreamIngest(cfg, max(local_total[r], 1), pb, device, world, r, graph=graph, exchange=lambda row: row, **kw) for r in range(world)]
+    ranks, steps = lockstep_ranks(batches, cfg, world, lambda cap, pb, r: DistStreamIngest(cfg, cap, pb, device, world, r, graph=graph, **kw), piece_bytes)
     rows = torch.zeros(world * ranks[0].row_bytes, dtype=torch.uint8, device=device)
-    for b, bd in zip(batches, bounds):
-        ns = []
-        for r, s in enumerate(ranks):
-            n = bd[r + 1] - bd[r]
-            if n:
-                s.data[s.n_bytes: s.n_bytes + n].copy_(b[bd[r]: bd[r + 1]])
-            ns.append(n)
-            row = s.hash_piece(n)
-            rows[r * s.row_bytes: (r + 1) * s.row_bytes].copy_(row)
+    for ns in steps:
+        for r, (n, s) in enumerate(zip(ns, ranks)):
+            rows[r * s.row_bytes: (r + 1) * s.row_bytes].copy_(s.hash_piece(n))
         for n, s in zip(ns, ranks):
             s.encode_piece(n, rows)
-            s.n_bytes += n
     return [s.finish() for s in ranks]
 
 
@@ -302,12 +141,7 @@ def store_results(results: list, only: int | None = None) -> list:
         pieces = np.zeros(len(starts), PIECE_DTYPE)
         pieces["g0"] = g[starts] if len(g) else 0
         pieces["n"] = ends - starts
-        rr = dataclasses.replace(r, first_occ=to_store[r.first_occ], chunk_base=vb, shard_bases=list(vbase))
-        rr.gidx, rr.pieces = r.gidx, pieces
-        for extra in ("ug", "remote_bases"):          # a global-L4 stream's shard (GlobalL4StreamIngest)
-            if hasattr(r, extra):
-                setattr(rr, extra, getattr(r, extra))
-        out.append(rr)
+        out.append(dataclasses.replace(r, first_occ=to_store[r.first_occ], chunk_base=vb, shard_bases=list(vbase), pieces=pieces))
     return out
 
 
@@ -329,7 +163,7 @@ def gather_global_index(res, group=None):
 # ---------------------------------------------------------------------------------------------------------------------------
 # Global L4 for a multi-rank stream ("cross-GPU base-chunk fetch over xGMI for global L4 (config 5)")
 # ---------------------------------------------------------------------------------------------------------------------------
-class GlobalL4StreamIngest:
+class GlobalL4StreamIngest(RankStream):
     """This rank's side of a multi-rank stream whose L4 base selection spans ALL ranks (README.md:1375-1383 against one band
     table): besides the digests, every batch all-gathers the signatures of its newly stored chunks; every rank keeps the same
     band tables over the GLOBAL stored-chunk order (batch, rank, local) and so finds the same bases as a one-rank run; a base
@@ -348,50 +182,29 @@ class GlobalL4StreamIngest:
 
     def __init__(self, cfg: IngestConfig, capacity_bytes: int, piece_bytes: int, device, world: int, rank: int, group=None,
                  max_chunks: int | None = None, max_chunks_global: int | None = None, ghost_bytes: int | None = None):
-        if cfg.layers != (LAYER_L1 | LAYER_L2 | LAYER_L3 | LAYER_L4):
-            raise ValueError("GlobalL4StreamIngest runs the full L1-L4 pipeline")
-        if piece_bytes <= 0 or piece_bytes % cfg.seg_size:
-            raise ValueError("piece_bytes (the nominal piece size) must be a positive multiple of seg_size")
-        if not 0 <= rank < world <= 256:
-            raise ValueError("0 <= rank < world <= 256")
-        self.cfg, self.dev, self.world, self.rank, self.group = cfg, device, int(world), int(rank), group
-        self.capacity = int(capacity_bytes)
-        self.ghost_cap = int(ghost_bytes if ghost_bytes is not None else 2 * piece_bytes)
-        self.data = torch.empty(self.capacity + self.ghost_cap, dtype=torch.uint8, device=device)   # [0, capacity): this rank's pieces; behind: ghosts
-        self.n_bytes = 0
-        self.copy_stream = torch.cuda.Stream(device=device)
-        self.pending: list = []
-        per = max(1, cfg.avg_size // 2)
-        self.max_chunks = int(max_chunks or (capacity_bytes // per + capacity_bytes // cfg.seg_size + 64))
-        self.max_chunks_g = int(max_chunks_global or self.max_chunks * world)
-        mc, mg = self.max_chunks, self.max_chunks_g
+        super().__init__(cfg, capacity_bytes, piece_bytes, device, world, rank, group, max_chunks, max_chunks_global,
+                         ghost_bytes=ghost_bytes if ghost_bytes is not None else 2 * piece_bytes, limit_pieces=False)    # (stages are sized per batch: a piece may have any size)
+        mg = self.max_chunks_g
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
-        self._cuts = z(mc + 1, torch.int64)
-        self._gidx = z(mc, torch.int64)
+        self._cuts = z(self.max_chunks + 1, torch.int64)
         self.n_chunks = 0
         # this rank's stored chunks (appended per batch)
         self._uniq, self._ug, self._base, self._base_global, self._kind, self._sig_l, self._keys_l = [], [], [], [], [], [], []
         self._stream_parts, self._stream_lens = [], []
         self.n_unique = 0
-        # the global index and the global band tables: identical on every rank
-        self._digests_g = torch.empty((mg, 32), dtype=torch.uint8, device=device)
-        self._first_occ_g = z(mg, torch.int64)
-        self._refcount_g = z(mg, torch.int32)
-        self._l3_table = torch.empty(ops.l3_index_slots(mg), dtype=torch.int32, device=device)
-        self._mug = min(mg, 1 << 23)
+        # the global band tables: identical on every rank (like the global index)
+        self._mug = max_stored(mg)
         self._sig_g = torch.empty((self._mug, cfg.n_hashes), dtype=torch.int32, device=device)
         self._keys_g = z((self._mug, cfg.bands), torch.int32)
         self._base_g = z(self._mug, torch.int64)
         self._lsh_tables = torch.empty((cfg.bands, ops.l4_lsh_slots(self._mug)), dtype=torch.int32, device=device)
         self._g_owner = z(self._mug, torch.int64)     # global stored chunk -> owning rank, that rank's stored slot
         self._g_local = z(self._mug, torch.int64)
-        ops.l3_index_update(self._digests_g, 0, 0, self._first_occ_g, self._refcount_g, self._l3_table)
-        ops.l4_lsh_update(self._sig_g, 0, 0, cfg, self._keys_g, self._base_g, self._lsh_tables)
+        ops.l4_lsh_update(self._sig_g, 0, 0, cfg, self._keys_g, self._base_g, self._lsh_tables)               # clears the tables
         self.n_global = 0
         self.u_global = 0
         self.u_counts = [0] * self.world
         self._ws = None
-        self.n_batches = 0
         self.remote_dictionaries = 0
         self.ghost_bytes_fetched = 0
 
@@ -470,11 +283,7 @@ class GlobalL4StreamIngest:
         c = getattr(self, "_cur", None)
         if c is not None and "uniq_new" in c and not c.get("committed", False):
             uniq = torch.cat([uniq, c["uniq_new"]])                          # (a chunk of THIS batch can already be a peer's dictionary)
-        cid = uniq[local_slots]
-        ln = self._cuts[cid + 1] - self._cuts[cid]
-        oc = torch.zeros(cid.numel() + 1, dtype=torch.int64, device=self.dev)
-        torch.cumsum(ln, 0, out=oc[1:])
-        return (ops.read_assemble(oc, cid, self._cuts, self.data) if cid.numel() else torch.empty(0, dtype=torch.uint8, device=self.dev)), ln
+        return serve_chunks(uniq, self._cuts, self.data, local_slots)
 
     def stage_encode(self, ghost: torch.Tensor, ghost_lens: torch.Tensor) -> None:
         """DEFLATE of this rank's newly stored chunks; a remote dictionary is ghost chunk j (the j-th request of stage_lsh)."""
@@ -499,7 +308,7 @@ class GlobalL4StreamIngest:
             self.ghost_bytes_fetched += gb
         if uniq_new.numel():
             n_b = c["n_b"]
-            worst = (5 * c["n"] + 1600 * n_b) + ops.workspace_bytes(ops.STAGE_DEFLATE, n_b, cfg) + (1 << 20)
+            worst = deflate_ws_bytes(c["n"], n_b, cfg)
             if self._ws is None or self._ws.numel() < worst:
                 self._ws = None
                 self._ws = torch.empty(worst, dtype=torch.uint8, device=dev)
@@ -540,25 +349,10 @@ class GlobalL4StreamIngest:
         self._agree(err)
         return out
 
-    def push(self, host_piece: torch.Tensor) -> None:
-        """COLLECTIVE (every rank pushes once per global batch, an empty tensor if it has no bytes in it): issue the host -> HBM
-        copy of this piece, then process the piece pushed before."""
-        n = host_piece.numel()
-        err = None
-        if self.n_bytes % self.cfg.seg_size:
-            err = ValueError("only a rank's last piece may end inside a segment")
-        elif self.n_bytes + n > self.capacity:
-            err = ValueError("stream capacity exceeded")
-        self._agree(err)
-        ev = torch.cuda.Event()
-        with torch.cuda.stream(self.copy_stream):
-            if n:
-                self.data[self.n_bytes: self.n_bytes + n].copy_(host_piece, non_blocking=True)
-            ev.record(self.copy_stream)
-        while self.pending:
-            self._process(*self.pending.pop(0))
-        self.pending.append((self.n_bytes, n, ev))
-        self.n_bytes += n
+    def _refuse(self, err) -> bool:
+        """push(): a piece this rank cannot take is agreed with the peers — every rank raises, none goes on to the batch's collectives."""
+        self._agree(None if err is None else ValueError(err))
+        return False
 
     def _process(self, off: int, n: int, copied) -> None:
         from .ingest import fetch_chunks_routed, gather_rows
@@ -580,64 +374,31 @@ class GlobalL4StreamIngest:
         self._guard(self.stage_encode, ghost, glens)
 
     def finish(self) -> ShardResult:
-        while self.pending:
-            self._process(*self.pending.pop(0))
+        self._drain()
         dev = self.dev
         cat = lambda parts, dt, shape=(0,): torch.cat(parts) if parts else torch.empty(shape, dtype=dt, device=dev)
-        n_c = self.n_chunks
-        gidx = self._gidx[:n_c]
-        uniq = cat(self._uniq, torch.int64)
         lens = cat(self._stream_lens, torch.int64)
         off = torch.zeros(lens.numel() + 1, dtype=torch.int64, device=dev)
         torch.cumsum(lens, 0, out=off[1:])
         base, bg = cat(self._base, torch.int64), cat(self._base_global, torch.int64)
         kind = cat(self._kind, torch.uint8)
-        res = ShardResult(self.n_bytes, self._cuts[: n_c + 1], self._digests_g[gidx], 0, self.n_global, self._first_occ_g[gidx], self._refcount_g[gidx],
-                          uniq, cat(self._sig_l, torch.int32, (0, self.cfg.n_hashes)), cat(self._keys_l, torch.int32, (0, self.cfg.bands)), base,
-                          cat(self._stream_parts, torch.uint8), off, kind, base_global=bg)
-        res.gidx, res.ug = gidx, cat(self._ug, torch.int64)
-        import numpy as np
-        from .manifest import REMOTE_BASE_DTYPE
-        slots = ((bg >= 0) & (base < 0) & (kind == 2)).nonzero().flatten()
-        tab = np.zeros(int(slots.numel()), REMOTE_BASE_DTYPE)
-        if slots.numel():
-            tab["slot"] = slots.cpu().numpy(); tab["shard"] = self._g_owner[bg[slots]].cpu().numpy(); tab["base_slot"] = self._g_local[bg[slots]].cpu().numpy()
-        res.remote_bases = tab if len(tab) else None
-        res.stats = shard_stats(res)
-        return res
+        return self._result(self.n_bytes, self.n_chunks, self.n_global, cat(self._uniq, torch.int64), cat(self._sig_l, torch.int32, (0, self.cfg.n_hashes)),
+                            cat(self._keys_l, torch.int32, (0, self.cfg.bands)), base, cat(self._stream_parts, torch.uint8), off, kind,
+                            base_global=bg, ug=cat(self._ug, torch.int64), remote_bases=remote_base_rows(bg, base, kind, self._g_owner, self._g_local))
 
 
 def stream_shards_local_global_l4(batches: list, cfg: IngestConfig, world: int, device, **kw) -> list:
     """A `world`-rank global-L4 stream with every rank on THIS GPU, in lock step: per global batch each stage of every rank, the
     exchanges delivered as the collectives would (concatenation in rank order; remote dictionaries served by the owner's
     `serve`).  Each result is what the rank would hold after GlobalL4StreamIngest.finish()."""
-    seg = cfg.seg_size
-    bounds = [deal_batch(b.numel(), world, seg) for b in batches]
-    pb = -(-max(max(bd[r + 1] - bd[r] for r in range(world)) for bd in bounds) // seg) * seg
-    local_total = [sum(bd[r + 1] - bd[r] for bd in bounds) for r in range(world)]
-    ranks = [GlobalL4StreamIngest(cfg, max(local_total[r], 1), pb, device, world, r, **kw) for r in range(world)]
-    for b, bd in zip(batches, bounds):
-        ns, dgs = [], []
-        for r, s in enumerate(ranks):
-            n = bd[r + 1] - bd[r]
-            if n:
-                s.data[s.n_bytes: s.n_bytes + n].copy_(b[bd[r]: bd[r + 1]])
-            ns.append(n)
-            dgs.append(s.stage_hash(s.n_bytes, n))
+    ranks, steps = lockstep_ranks(batches, cfg, world, lambda cap, pb, r: GlobalL4StreamIngest(cfg, cap, pb, device, world, r, **kw))
+    for ns in steps:
+        dgs = [s.stage_hash(s.n_bytes, n) for n, s in zip(ns, ranks)]
         alld, counts = torch.cat(dgs), [int(d.shape[0]) for d in dgs]
         sigs = [s.stage_index(alld, counts) for s in ranks]
         alls, counts_u = torch.cat(sigs), [int(x.shape[0]) for x in sigs]
         reqs = [s.stage_lsh(alls, counts_u) for s in ranks]
-        for s, (rc, rl) in zip(ranks, reqs):
-            parts, lens, o = [], [], 0
-            for owner, cnt in enumerate(rc.tolist()):
-                if cnt:
-                    by, ln = ranks[owner].serve(rl[o: o + cnt])
-                    parts.append(by); lens.append(ln); o += cnt
-            ghost = torch.cat(parts) if parts else torch.empty(0, dtype=torch.uint8, device=device)
-            glens = torch.cat(lens) if lens else torch.empty(0, dtype=torch.int64, device=device)
-            s._ghost = (ghost, glens)
-        for n, s in zip(ns, ranks):
-            s.stage_encode(*s._ghost)
-            s.n_bytes += n
+        ghosts = [serve_requests(ranks, rc.tolist(), rl) for rc, rl in reqs]       # (every rank is served before any commits its batch)
+        for s, ghost in zip(ranks, ghosts):
+            s.stage_encode(*ghost)
     return [s.finish() for s in ranks]

@@ -145,7 +145,7 @@ def test_captured_chain_equals_eager_and_one_shot(dev):
         for name in names:
             assert torch.equal(getattr(res, name), getattr(whole, name)), (graph, name)
         if graph:
-            sizes = {k: (v[0] is not None) for k, v in st._graphs.items()}
+            sizes = {k: bool(st._graphs.captured(k)) for k in st._graphs.sizes()}
             assert sizes[B] is True and len(sizes) == 2          # the common size was captured and replayed; the ragged tail ran directly
             assert torch.equal(read.reconstruct_shard(res, verify=True), torch.from_numpy(data).to(dev))
     # resume() + captured chain

@@ -164,8 +164,7 @@ def test_graphs_are_captured_once_per_piece_size(dev):
     for a in range(0, data.size, 2 << 20):
         s.push(torch.from_numpy(data[a: a + (2 << 20)].copy()).pin_memory())
     res = s.finish()
-    e = s._graphs[2 << 20]
-    assert e[1] is not None and e[2] is not None and e[3] == 4      # eager once, captured at the second use, replayed after
+    assert s._graphs.captured(2 << 20) == {"A", "B"} and s._graphs.uses(2 << 20) == 4      # eager once, captured at the second use, replayed after
     assert int(res.cuts[-1]) == data.size and res.n_global == res.cuts.numel() - 1
 
 
@@ -337,8 +336,7 @@ def test_world_size_1_stream_with_the_rccl_all_gather_between_the_graph_replays(
         torch.cuda.synchronize()
     finally:
         dist.destroy_process_group()
-    e = s._graphs[2 << 20]
-    assert e[1] is not None and e[2] is not None and e[3] == 5
+    assert s._graphs.captured(2 << 20) == {"A", "B"} and s._graphs.uses(2 << 20) == 5
     for name in NAMES:
         assert torch.equal(getattr(res, name), getattr(whole, name)), name
 

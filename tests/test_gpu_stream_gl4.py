@@ -90,8 +90,7 @@ def test_one_rank_captured_global_l4_chain_equals_one_shot_ingest_also_over_rccl
             s.push(torch.from_numpy(data[a: a + P].copy()).pin_memory())
         res = s.finish()
         torch.cuda.synchronize()
-        e = s._graphs[P]
-        assert all(e[i] is not None for i in (1, 2, 3, 4)) and e[5] == 5
+        assert s._graphs.captured(P) == {"A", "B1", "B2", "B3"} and s._graphs.uses(P) == 5
         return res
     res = run(False)
     for name in NAMES:

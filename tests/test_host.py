@@ -437,3 +437,23 @@ def test_python_side_class_caps_are_the_kernel_source_s():
     caps = tuple(int(re.search(r"#define %s (\d+)" % name, src).group(1)) for name in ("HMSE_TCAP_S", "HMSE_TCAP_S2", "HMSE_TCAP_SG", "HMSE_TCAP_SG2"))
     sg3 = int(re.search(r"TCAP_SG3 = (\d+)", src).group(1))
     assert caps + (sg3,) == tuple(ops.DEFLATE_CLASS_CAPS)
+
+
+def test_remote_base_table_of_a_global_l4_stream_shard_without_remote_dictionaries():
+    """A global-L4 STREAM's shard carries its own owner table (`remote_bases`); `None` there means "no remote dictionary" and must not send
+    manifest.remote_base_table into the one-shot path, which derives the owners from `u_bases` (a stream's shard has none).  `ug` is
+    what identifies such a shard."""
+    import numpy as np
+    import torch
+    from hmse_amd import ingest, manifest
+    i64 = lambda *v: torch.tensor(v, dtype=torch.int64)
+    mk = lambda **kw: ingest.ShardResult(0, i64(0, 10, 20), None, 0, 2, None, None, i64(0, 1), None, None, i64(-1, -1), None, None,
+                                         torch.tensor([0, 2], dtype=torch.uint8), base_global=i64(-1, 0), **kw)
+    assert manifest.remote_base_table(mk(ug=i64(0, 1), gidx=i64(0, 1))) is None          # a remote base by the numbers, but the stream says: none
+    tab = np.zeros(1, manifest.REMOTE_BASE_DTYPE)
+    tab["slot"], tab["shard"], tab["base_slot"] = 1, 1, 0
+    assert manifest.remote_base_table(mk(ug=i64(0, 1), gidx=i64(0, 1), remote_bases=tab)) is tab
+    got = manifest.remote_base_table(mk(u_base=1, u_bases=[0, 1]))                       # a one-shot global-L4 shard: derived from u_bases
+    assert got is not None and (int(got["slot"][0]), int(got["shard"][0]), int(got["base_slot"][0])) == (1, 0, 0)
+    plain = ingest.ShardResult(0, i64(0), None, 0, 0, None, None, i64(), None, None, None, None, None, None)
+    assert manifest.remote_base_table(plain) is None                                     # shard-local bases: no table

@@ -17,7 +17,7 @@ P = 2 << 20
 data = torch.from_numpy(corpus.wiki_synth(4 * P, seed=11))
 s = stream_dist.DistStreamIngest(cfg, data.numel(), P, dev, 1, 0, graph=False)
 s.data.copy_(data)
-seg_off = s._entry(P)[0]
+seg_off = s._graphs.entry(P).seg_off
 
 
 def A():
