@@ -109,6 +109,24 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
+// Workgroup exclusive scan of one u32 per thread, for the match kernel: the wavefronts' totals are scanned by ONE more wave-level scan
+// (one LDS read per thread, two v_readlane).  common.h's block_exclusive_scan reads all NT / 64 totals in every thread and picks with
+// NT / 64 lane masks `w < wave` — 16 wave-uniform SGPR pairs that depend on nothing but the thread index, which the compiler computed
+// once per job and kept in spilled SGPRs: ~48 vector instructions and 32 spill reloads per call (tools/spill_audit.py), here ~12 and 0.
+// `t` = the caller's (laundered) thread index.  Same sums.
+template <int NT>
+__device__ __forceinline__ uint32_t block_exclusive_scan_w(uint32_t v, uint32_t t, uint32_t* red, uint32_t* total) {
+  const uint32_t lane = t & 63u, wave = uni32(t >> 6);
+  const uint32_t inc = wave_incl_scan(v);
+  if (lane == 63u) red[wave] = inc;
+  __syncthreads();
+  const uint32_t c = lane < (uint32_t)(NT / 64) ? red[lane] : 0u;
+  const uint32_t ci = wave_incl_scan(c);
+  __syncthreads();
+  *total = (uint32_t)__builtin_amdgcn_readlane((int)ci, 63);
+  return (uint32_t)__builtin_amdgcn_readlane((int)(ci - c), (int)wave) + inc - v;
+}
+
 template <int N>
 struct HuffScratchT {
   uint32_t key[N];         // compacted (freq << 9 | sym)
@@ -128,6 +146,7 @@ struct Small {
   uint32_t qhead;
   uint32_t ocnt[4];   // sorted ranks per chain-length class (the matcher's hand-out order)
   struct { uint32_t ji, job, L, Dl; uint64_t c, cstart, rec_at, dstart; } nx;   // the NEXT job's metadata, fetched while this one runs
+  struct { uint64_t rec_at; } cur;   // the RUNNING job's record offset (nx is overwritten while it runs)
   uint32_t pexit[NT / 64], pexit2[NT / 64], pconv[NT / 64];
   uint8_t wtab[WQ ? NT : 64];   // class B's dictionary jobs (no hand-out list): per wavefront, lane that holds the r-th pending work rank of the wave's window
 };
@@ -412,6 +431,20 @@ struct Args {
 };
 
 
+// The kernels' arguments ON DEMAND (round 8).  `Args` is 22 fields, mostly 64-bit pointers; read as a by-value parameter the whole struct
+// is loaded in the prologue and stays live across the persistent loop — far more wave-uniform state than a wavefront has SGPRs, so the
+// compiler parked the overflow in VGPR lanes and every use became a v_readlane: a VECTOR instruction in kernels whose time follows the
+// vector instructions they issue (tools/spill_audit.py).  The struct lives in the kernarg segment — scalar-cached and
+// read-only —, so a phase reads the fields it needs from there (s_load: scalar memory pipe, no vector slot).  The pointer is
+// laundered by an empty asm at every call, the idiom used for threadIdx.x below: loads through it are not hoisted out of the phase
+// that asked for them.  Loads only.  (`Args` must stay the kernels' FIRST parameter: the segment starts with it.)
+typedef const __attribute__((address_space(4))) Args* KArgs;
+__device__ __forceinline__ KArgs kargs() {
+  KArgs p = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return p;
+}
+
 // per-workgroup global scratch of the big class
 struct Scratch {
   uint16_t S[65536]; uint8_t K[65536 + 16];
@@ -421,7 +454,7 @@ struct Scratch {
 // DICT: the instantiation that runs the dictionary jobs of its class (chunk + base chunk; yields the DELTA and the FULL
 // record).  Plain jobs run the DICT = false instantiation, which carries none of the snapshot code or its registers.
 template <int NT, int TCAP, int LCAP_, bool LDSM, bool MDG = false, bool MLG = false, bool NOK = false, bool DICT = false>
-__global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4) : 2)) void l1_deflate_kernel(Args a) {
+__global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4) : 2)) void l1_deflate_kernel(Args) {
   using LY = Layout<NT, TCAP, LCAP_, LDSM, MDG, MLG, NOK>;
   constexpr int LCAP = LY::LCAP;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -429,30 +462,34 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
   uint32_t* const cur = (uint32_t*)(smem + LY::CUR_OFF);
   uint32_t* const mark = (uint32_t*)(smem + LY::MARK_OFF);
   Small<NT, !LDSM>& sm = *(Small<NT, !LDSM>*)(smem + LY::SMALL_OFF);
-  Scratch* const sc = LDSM ? nullptr : (Scratch*)(a.scratch + (size_t)blockIdx.x * a.scratch_stride);
-  uint16_t* const mdist_g = (uint16_t*)(a.scratch2 + (size_t)blockIdx.x * a.scratch2_stride);  // used by S2/SG/B only
+  // this workgroup's slices of the global scratch areas, derived where they are used (class B: S / K / jump; S2 / SG / B: match
+  // distances and lengths; the LDS classes: the hand-out list)
+  auto scratch_wg = [&]() -> Scratch* { const KArgs a = kargs(); return (Scratch*)(a->scratch + (size_t)blockIdx.x * a->scratch_stride); };
+  auto scratch2_wg = [&]() -> uint8_t* { const KArgs a = kargs(); return a->scratch2 + (size_t)blockIdx.x * a->scratch2_stride; };
+  Scratch* const sc = LDSM ? nullptr : scratch_wg();
   uint16_t* const S = LDSM ? (uint16_t*)(smem + LY::A_OFF) : sc->S;
   uint16_t* const jump = LDSM ? (uint16_t*)(smem + LY::A_OFF) : sc->jumpA;
   uint8_t* const K = LDSM ? (uint8_t*)(smem + LY::K_OFF) : sc->K;
-  const uint32_t n_jobs = *a.n_jobs;
+  auto n_jobs_now = [&]() -> uint32_t { return *kargs()->n_jobs; };   // (fixed while the kernel runs)
 #ifdef HMSE_DFL_STAMPS
   unsigned long long stamp_acc[24] = {0}, stamp_last = clock64();
 #endif
 
   // the whole chain at once (thread 0; the first job of a workgroup, and behind a job that was refused)
   auto pf_fetch_sync = [&]() {
-    const uint32_t ji2 = atomicAdd(a.counter, 1u);
+    const KArgs a = kargs();
+    const uint32_t ji2 = atomicAdd(a->counter, 1u);
     sm.nx.ji = ji2;
-    if (ji2 >= n_jobs) return;
-    const uint32_t job2 = a.jobs[ji2];
+    if (ji2 >= *a->n_jobs) return;
+    const uint32_t job2 = a->jobs[ji2];
     const uint64_t k2 = job2 >> 1;
-    const uint64_t c2 = a.chunk_ids ? a.chunk_ids[k2] : k2;
-    const uint64_t cs = a.cuts[c2];
-    sm.nx.job = job2; sm.nx.c = c2; sm.nx.cstart = cs; sm.nx.L = (uint32_t)(a.cuts[c2 + 1] - cs); sm.nx.rec_at = a.rec_off[k2];
+    const uint64_t c2 = a->chunk_ids ? a->chunk_ids[k2] : k2;
+    const uint64_t cs = a->cuts[c2];
+    sm.nx.job = job2; sm.nx.c = c2; sm.nx.cstart = cs; sm.nx.L = (uint32_t)(a->cuts[c2 + 1] - cs); sm.nx.rec_at = a->rec_off[k2];
     if constexpr (DICT) {
-      const int64_t bsel = a.base[k2];
-      const uint64_t bc = (a.chunk_ids && !a.base_is_chunk) ? a.chunk_ids[bsel] : (uint64_t)bsel;
-      uint64_t ds = a.cuts[bc], dl = a.cuts[bc + 1] - ds;
+      const int64_t bsel = a->base[k2];
+      const uint64_t bc = (a->chunk_ids && !a->base_is_chunk) ? a->chunk_ids[bsel] : (uint64_t)bsel;
+      uint64_t ds = a->cuts[bc], dl = a->cuts[bc + 1] - ds;
       if (dl > WMAX) { ds += dl - WMAX; dl = WMAX; }
       sm.nx.dstart = ds; sm.nx.Dl = (uint32_t)dl;
     }
@@ -472,43 +509,38 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     // changes nothing: 39.4 against 39.5 ms of plain kernels at 2 GB; the second workgroup of the CU fills the wait.)
     __syncthreads();
     const uint32_t ji = uni32(sm.nx.ji);   // wave-uniform, and said so: lengths and loop bounds live in SGPRs
-    if (ji >= n_jobs) break;
+    if (ji >= n_jobs_now()) break;
     STAMP(10);
-    const uint32_t job = uni32(sm.nx.job);
-    const uint64_t k = job >> 1;
     constexpr uint32_t variant = DICT ? 1u : 0u;  // (== job & 1: the lists are split by variant)
-    const uint64_t c = uni64(sm.nx.c);
-    const uint64_t cstart = uni64(sm.nx.cstart);
     const uint32_t L = uni32(sm.nx.L);
     const uint32_t Dl = variant ? uni32(sm.nx.Dl) : 0u;
-    const uint64_t dstart = variant ? uni64(sm.nx.dstart) : 0ull;
-    (void)c;
-    uint32_t* len_out = variant ? a.len_delta : a.len_full;
     const uint32_t T = Dl + L;
     // links of the next job's chain in flight (thread 0): issued at one PF_STAGE, consumed at the next; nothing is in flight
     // across the matcher's state machine (its registers are the kernel's peak)
     uint32_t pf_u = 0; uint64_t pf_a = 0, pf_b = 0, pf_c = 0;
     auto pf_stage = [&](int stg) {
+      const KArgs a = kargs();
+      const uint32_t n_jobs = *a->n_jobs;
       const bool valid = stg <= 1 || sm.nx.ji < n_jobs;
       switch (stg) {
-        case 0: pf_u = atomicAdd(a.counter, 1u); break;
-        case 1: sm.nx.ji = pf_u; pf_u = pf_u < n_jobs ? a.jobs[pf_u] : 0u; break;
+        case 0: pf_u = atomicAdd(a->counter, 1u); break;
+        case 1: sm.nx.ji = pf_u; pf_u = pf_u < n_jobs ? a->jobs[pf_u] : 0u; break;
         case 2: {
           sm.nx.job = pf_u;
-          if (valid) { const uint64_t k2 = pf_u >> 1; pf_a = a.chunk_ids ? a.chunk_ids[k2] : k2; pf_b = a.rec_off[k2]; if (DICT) pf_c = (uint64_t)a.base[k2]; }
+          if (valid) { const uint64_t k2 = pf_u >> 1; pf_a = a->chunk_ids ? a->chunk_ids[k2] : k2; pf_b = a->rec_off[k2]; if (DICT) pf_c = (uint64_t)a->base[k2]; }
           break;
         }
         case 3: sm.nx.c = pf_a; sm.nx.rec_at = pf_b; if (DICT) sm.nx.dstart = pf_c; break;   // (dstart: the base index, until stage 6)
         case 4:
           if (valid) {
             const uint64_t c2 = sm.nx.c;
-            pf_a = a.cuts[c2]; pf_b = a.cuts[c2 + 1];
-            if (DICT) { const uint64_t bsel = sm.nx.dstart; pf_c = (a.chunk_ids && !a.base_is_chunk) ? a.chunk_ids[bsel] : bsel; }
+            pf_a = a->cuts[c2]; pf_b = a->cuts[c2 + 1];
+            if (DICT) { const uint64_t bsel = sm.nx.dstart; pf_c = (a->chunk_ids && !a->base_is_chunk) ? a->chunk_ids[bsel] : bsel; }
           }
           break;
         case 5:
           sm.nx.cstart = pf_a; sm.nx.L = (uint32_t)(pf_b - pf_a);
-          if (DICT && valid) { const uint64_t bc = pf_c; pf_a = a.cuts[bc]; pf_b = a.cuts[bc + 1]; }
+          if (DICT && valid) { const uint64_t bc = pf_c; pf_a = a->cuts[bc]; pf_b = a->cuts[bc + 1]; }
           break;
         default:
           if (DICT && valid) { uint64_t ds = pf_a, dl = pf_b - pf_a; if (dl > WMAX) { ds += dl - WMAX; dl = WMAX; } sm.nx.dstart = ds; sm.nx.Dl = (uint32_t)dl; }
@@ -518,20 +550,32 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
 #define PF_STAGE(n) do { if (t == 0) pf_stage(n); } while (0)
     // job record: histograms and the token list go to the encode kernel through it.  Classes S2/SG/B keep the match
     // distances (S2) or lengths and distances (SG, B) in a per-workgroup global array while matching.
-    const uint64_t rec_at = uni64(sm.nx.rec_at);
-    uint8_t* const rec = a.recs + rec_at;
-    uint16_t* const mdist = (LDSM && !MDG) ? (uint16_t*)(smem + LY::MD_OFF) : mdist_g;
-    uint8_t* const mlen = (LDSM && !MLG) ? (uint8_t*)(smem + LY::ML_OFF) : (uint8_t*)(mdist_g + LCAP);
+    // (where they live in the global scratch the two pointers are derived again by every phase that uses them: nothing 64-bit and
+    // wave-uniform is carried across the sort and the matcher)
+    auto mdist_of = [&]() -> uint16_t* { if constexpr (LDSM && !MDG) return (uint16_t*)(smem + LY::MD_OFF); else return (uint16_t*)scratch2_wg(); };
+    auto mlen_of = [&]() -> uint8_t* { if constexpr (LDSM && !MLG) return (uint8_t*)(smem + LY::ML_OFF); else return scratch2_wg() + 2u * (uint32_t)LCAP; };
     // A dictionary job yields the chunk's DELTA record only (round 3, rule 7 of the oracle): the FULL record of a chunk with a
     // base is produced by a plain job in a second pass, and only when the delta turns out larger than a fifth of the chunk.
-    if (L > (uint32_t)LCAP || T > (uint32_t)TCAP || rec_at + (uint64_t)rec_size(L, variant != 0) > a.rec_cap) {
-      if (t == 0) { len_out[k] = 0xFFFFFFFFu; if (L <= 32768u) atomicOr(a.status, 2u); }  // record area too small
-      __syncthreads();                 // everybody has read sm.nx
-      if (t == 0) pf_fetch_sync();     // (no phases to hide the chain behind)
-      continue;
+    // The job's 64-bit values are needed here and at record-out only; sm.nx is overwritten by the next job's prefetch, so the record
+    // offset waits in sm.cur (visible behind phase 0's barrier) and is read again in phase 7.
+    {
+      const KArgs a = kargs();
+      const uint64_t rec_at = uni64(sm.nx.rec_at);
+      if (L > (uint32_t)LCAP || T > (uint32_t)TCAP || rec_at + (uint64_t)rec_size(L, variant != 0) > a->rec_cap) {
+        if (t == 0) {
+          const uint64_t k = sm.nx.job >> 1;
+          (variant ? a->len_delta : a->len_full)[k] = 0xFFFFFFFFu;
+          if (L <= 32768u) atomicOr(a->status, 2u);   // record area too small
+        }
+        __syncthreads();                 // everybody has read sm.nx
+        if (t == 0) pf_fetch_sync();     // (no phases to hide the chain behind)
+        continue;
+      }
+      if (t == 0) sm.cur.rec_at = rec_at;
     }
-    const uint8_t* csrc = a.data + cstart;
-    const uint8_t* dsrc = a.data + dstart;
+    const uint8_t* const csrc = kargs()->data + uni64(sm.nx.cstart);
+    const uint8_t* const dsrc = kargs()->data + (variant ? uni64(sm.nx.dstart) : 0ull);
+    uint8_t* const mlen0 = mlen_of();
 
     // ---- phase 0: window into LDS, clear tables -----------------------------------------------
     for (uint32_t i = t * 16; i < Dl; i += NT * 16) {
@@ -555,7 +599,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     if (t == 0) sm.qhead = 0;
     if (t < 4) sm.ocnt[t] = 0;
     // (16 bytes per store: both arrays start on a 16-byte boundary and hold LCAP = a multiple of 16 bytes)
-    for (uint32_t i = t * 16; i < L; i += NT * 16) *(uint4*)(mlen + i) = make_uint4(0, 0, 0, 0);
+    for (uint32_t i = t * 16; i < L; i += NT * 16) *(uint4*)(mlen0 + i) = make_uint4(0, 0, 0, 0);
     __syncthreads();
 
     STAMP(0);
@@ -582,7 +626,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         sum += (wv[i] & 0xFFFFu) + (wv[i] >> 16);
       }
       uint32_t total;
-      uint32_t ex = block_exclusive_scan<NT>(sum, sm.red, &total);
+      uint32_t ex = block_exclusive_scan_w<NT>(sum, t, sm.red, &total);
 #pragma unroll
       for (int i = 0; i < PERW; i++) {
         const uint32_t idx = t * PERW + i;
@@ -720,6 +764,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
       return bm;
     };
     if constexpr (DICT) {
+      uint8_t* const mlen = mlen_of(); uint16_t* const mdist = mdist_of();
       for (uint32_t x = t; x < L; x += NT) {
         const uint32_t p = Dl + x;
         if (p + 4 > T) continue;
@@ -728,7 +773,9 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         const uint32_t bm = hint_of(p, maxlen, bq);
         if (bm >= 16u) { mlen[x] = (uint8_t)(bm - 3); mdist[x] = (uint16_t)(p - bq); }
       }
-      // (no barrier needed: the state machine never touches a hinted position's slots, and the parse starts behind a barrier)
+      // (the state machine never touches a hinted position's slots, and the parse starts behind a barrier; the barrier here is for the
+      // hand-out pass below, which reads the verdicts back where the match lengths live in LDS)
+      if constexpr (!MLG && LDSM) __syncthreads();
     }
     // ---- phase 4c (LDS classes): the matcher's hand-out order ---------------------------------------------------------
     // A walk lasts about as many trips as its position has candidates (in-bucket index, capped at the depth), candidates per position
@@ -748,8 +795,10 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
 #else
     constexpr bool ORD = LDSM;
 #endif
-    uint32_t* const ord = (uint32_t*)(a.scratch2 + (size_t)blockIdx.x * a.scratch2_stride + 98304u);
+    auto ord_of = [&]() -> uint32_t* { return (uint32_t*)(scratch2_wg() + 98304u); };
     if constexpr (ORD) {
+      const uint32_t depth = kargs()->depth;
+      uint32_t* const ord = ord_of();
       // Two passes over this wavefront's ranks (64 per step, a step every NT ranks; ITER steps at most): the first classifies — all
       // its LDS reads are independent and issue back to back — and counts per class in scalars; ONE LDS atomic per wavefront and class
       // reserves the list slots, and a barrier later the class totals place the four lists one behind the other; the second pass (no
@@ -768,8 +817,9 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
       {
         const uint32_t last = nh ? nh - 1u : 0u;
         constexpr int G = DICT ? 2 : ITER > 12 ? 4 : 8;   // steps staged together (registers: the larger classes run under a 64-VGPR cap)
+        [[maybe_unused]] const uint8_t* const mlen_h = mlen_of();
 #pragma unroll
-        for (int g = 0; g < ITER; g += G) {
+        for (int g = 0; g < ITER; g += G) if ((uint32_t)g * NT < nh) {   // (whole stage groups past the job's last rank are skipped: the unroll is over the class cap)
           uint32_t pv[G], hv[G], lv[G];
 #pragma unroll
           for (int u = 0; u < G; u++) if (g + u < ITER) { const uint32_t r = (wv << 6) + (uint32_t)(g + u) * NT + lane; pv[u] = S[r < last ? r : last]; }
@@ -782,21 +832,28 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
             const int it = g + u;
             const uint32_t r = (wv << 6) + (uint32_t)it * NT + lane;
             uint32_t km = r - ((hv[u] >> (32 - HB)) ? lv[u] : 0u);
-            km = km < a.depth ? km : a.depth;
+            km = km < depth ? km : depth;
             km = km < 63u ? km : 63u;   // (6 bits in the entry; a deeper configuration recomputes the count at the pull)
             km = r < nh ? km : 0u;
             if constexpr (DICT) {
               const uint32_t pp = pv[u];
-              uint32_t bq;
-              const uint32_t bm = pp >= Dl ? hint_of(pp, (T - pp) < MAXM ? (T - pp) : MAXM, bq) : 16u;
-              km = bm >= 16u ? 0u : km;   // a dictionary position (a candidate only) or a hinted chunk position: no walk
+              if constexpr (!MLG) {
+                // the pre-pass has decided already: a non-zero length at this point means "hinted" (nothing else has been matched yet)
+                km = (pp < Dl || mlen_h[pp >= Dl ? pp - Dl : 0u] != 0) ? 0u : km;
+              } else {
+                uint32_t bq;
+                const uint32_t bm = pp >= Dl ? hint_of(pp, (T - pp) < MAXM ? (T - pp) : MAXM, bq) : 16u;
+                km = bm >= 16u ? 0u : km;   // a dictionary position (a candidate only) or a hinted chunk position: no walk
+              }
             }
             pk[it / 3] |= (km | ((hv[u] >> 10) & 0x3C0u)) << (10 * (it % 3));   // km (6 bits) | bits 16..19 of the hash product << 6
-            n0 += (uint32_t)__builtin_popcountll(__ballot(km >= 24u)); n1 += (uint32_t)__builtin_popcountll(__ballot(km >= 12u && km < 24u));
-            n2 += (uint32_t)__builtin_popcountll(__ballot(km >= 4u && km < 12u)); n3 += (uint32_t)__builtin_popcountll(__ballot(km >= 1u && km < 4u));
+            // (cumulative here — one compare per ballot; the class counts are differences, taken once behind the steps)
+            n0 += (uint32_t)__builtin_popcountll(__ballot(km >= 24u)); n1 += (uint32_t)__builtin_popcountll(__ballot(km >= 12u));
+            n2 += (uint32_t)__builtin_popcountll(__ballot(km >= 4u)); n3 += (uint32_t)__builtin_popcountll(__ballot(km >= 1u));
           }
         }
       }
+      n3 -= n2; n2 -= n1; n1 -= n0;
       uint32_t bv = 0;
       if (lane < 4u) bv = atomicAdd(&sm.ocnt[lane], lane == 0u ? n0 : lane == 1u ? n1 : lane == 2u ? n2 : n3);
       uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane((int)bv, 0), b1 = (uint32_t)__builtin_amdgcn_readlane((int)bv, 1),
@@ -811,7 +868,8 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         const uint32_t r0 = (wv << 6) + (uint32_t)it * NT;
         if (r0 < nh) {
           const uint32_t kv = (pk[it / 3] >> (10 * (it % 3))) & 0x3FFu, km = kv & 63u;
-          const uint64_t m0 = __ballot(km >= 24u), m1 = __ballot(km >= 12u && km < 24u), m2 = __ballot(km >= 4u && km < 12u), m3 = __ballot(km >= 1u && km < 4u);
+          const uint64_t c0 = __ballot(km >= 24u), c1 = __ballot(km >= 12u), c2 = __ballot(km >= 4u), c3 = __ballot(km >= 1u);   // cumulative: one compare each
+          const uint64_t m0 = c0, m1 = c1 & ~c0, m2 = c2 & ~c1, m3 = c3 & ~c2;
           if (km != 0u) {
             const uint64_t mm = km >= 24u ? m0 : km >= 12u ? m1 : km >= 4u ? m2 : m3;
             const uint32_t pos = (km >= 24u ? b0 : km >= 12u ? b1 : km >= 4u ? b2 : b3) + mbcnt64(mm);
@@ -826,7 +884,12 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     }
     STAMP(6);
     PF_STAGE(3);
+    // ---- phase 5, the state machine: every lane pulls ranks and walks their candidates -------------------------------
     {
+      // (the matcher's wave-uniform values: read once in front of its loop)
+      const uint32_t depth = kargs()->depth;
+      uint8_t* const mlen = mlen_of(); uint16_t* const mdist = mdist_of();
+      const uint32_t* const ord = ORD ? ord_of() : nullptr;
       enum { FETCH = 0, PROBE = 1, EXTEND = 2, DONE = 3 };
 #ifndef HMSE_FETCH_BATCH
 #define HMSE_FETCH_BATCH 16
@@ -871,7 +934,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         const uint32_t lo = h ? cur_get(cur, h - 1) : 0u;
         maxlen = (T - p) < MAXM ? (T - p) : MAXM;
         kmax = i - lo;
-        if (kmax > a.depth) kmax = a.depth;
+        if (kmax > depth) kmax = depth;
         best = MINM - 1; bd = 0; probe = pw0; kk = 1;
 #ifdef HMSE_DFL_STAMPS
         if (DICT && t == 0) stamp_acc[7]++;  // lane 0's walked positions
@@ -892,7 +955,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         pkey = (pw1 & 0x0Fu) | ((e >> 17) & 0xF0u);
         if (kmax == 63u) {   // (the entry's count saturates at 63: a deeper configuration recomputes it — no lane comes here at depth <= 62)
           const uint32_t h = hash4(pw0), lo = h ? cur_get(cur, h - 1) : 0u;
-          kmax = i - lo < a.depth ? i - lo : a.depth;
+          kmax = i - lo < depth ? i - lo : depth;
         }
         maxlen = (T - p) < MAXM ? (T - p) : MAXM;
         best = MINM - 1; bd = 0; probe = pw0; kk = 1;
@@ -903,7 +966,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
       };
       // every wavefront leaves this loop: by running out of work, or — never observed on a correct build — by using up a trip
       // budget no legal walk can reach (status bit 4: the job's record is then garbage and the call reports it)
-      const uint32_t trip_budget = (nh + 64u) * (a.depth + 16u);
+      const uint32_t trip_budget = (nh + 64u) * (depth + 16u);
       uint32_t trips = 0;
       for (;;) {
 #ifdef HMSE_DFL_STAMPS
@@ -912,10 +975,10 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         if (++trips > uni32(trip_budget)) {
 #ifdef HMSE_DIAG
           const uint64_t sf = __ballot(st == FETCH), sp = __ballot(st == PROBE), se = __ballot(st == EXTEND);
-          if (lane == 0) printf("[dfl] trip budget: job %u k %llu L %u Dl %u nh %u wave %u qhead %u wq_base %u wq_mask %llx wq_done %d FETCH %llx PROBE %llx EXTEND %llx p %u kk %u kmax %u best %u ml %u maxlen %u q %u\n",
-                                ji, (unsigned long long)k, L, Dl, nh, wave, sm.qhead, wq_base, (unsigned long long)wq_mask, (int)wq_done, (unsigned long long)sf, (unsigned long long)sp, (unsigned long long)se, p, kk, kmax, best, ml, maxlen, q);
+          if (lane == 0) printf("[dfl] trip budget: job %u rec_at %llu L %u Dl %u nh %u wave %u qhead %u wq_base %u wq_mask %llx wq_done %d FETCH %llx PROBE %llx EXTEND %llx p %u kk %u kmax %u best %u ml %u maxlen %u q %u\n",
+                                ji, (unsigned long long)sm.cur.rec_at, L, Dl, nh, wave, sm.qhead, wq_base, (unsigned long long)wq_mask, (int)wq_done, (unsigned long long)sf, (unsigned long long)sp, (unsigned long long)se, p, kk, kmax, best, ml, maxlen, q);
 #endif
-          if (lane == 0) atomicOr(a.status, 16u);
+          if (lane == 0) atomicOr(kargs()->status, 16u);
           break;
         }
         uint64_t need = uni64(__ballot(st == FETCH));
@@ -1077,7 +1140,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     for (uint32_t i = t; i < (L >> 5) + 2; i += NT) mark[i] = 0;   // (held the diagonal anchors of a dictionary job until here)
     STAMP(3);
     PF_STAGE(4);
-    const uint8_t* mlen_c = mlen;
+    const uint8_t* mlen_c = mlen_of();
     // Match lengths that live in HBM (the classes that keep them out of LDS) are staged into a free LDS region first: the
     // parse reads each of them three times.
     {
@@ -1094,8 +1157,6 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         __syncthreads();
       }
     }
-    const uint16_t* const mdist_c = mdist;
-    uint8_t* const rec_c = rec;
     // ---- phase 6: parse by pointer doubling -------------------------------------------------------
     auto take = [&](uint32_t x) -> bool {
       const uint32_t ml = mlen_c[x];
@@ -1246,6 +1307,9 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     // token index of a marked position = number of marked positions before it: workgroup prefix scan over the
     // popcounts of contiguous mark words, then every thread walks the set bits of its own words
     {
+      const KArgs a = kargs();
+      uint8_t* const rec_c = a->recs + uni64(sm.cur.rec_at);   // job record: histograms and the token list go to the encode kernel through it
+      const uint16_t* const mdist_c = mdist_of();
       uint32_t* const tok = (uint32_t*)(rec_c + rec_tok_off());
       // every thread owns ceil(L / NT) consecutive positions (not whole mark words: with one 32-position word per
       // thread only L/32 of the NT threads would have work, each with a serial run of ~9 tokens)
@@ -1259,14 +1323,19 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
       uint32_t cntm = 0;
       for (uint32_t pos = p0; pos < p1; pos += 32) cntm += (uint32_t)__builtin_popcount(bits_at(pos, p1 - pos));
       uint32_t ntok;
-      uint32_t idx = block_exclusive_scan<NT>(cntm, sm.red, &ntok);
+      uint32_t idx = block_exclusive_scan_w<NT>(cntm, t, sm.red, &ntok);
       for (uint32_t pos = p0; pos < p1; pos += 32) {
         uint32_t m = bits_at(pos, p1 - pos);
         while (m) {
           const uint32_t x = pos + (uint32_t)__builtin_ctz(m);
           m &= m - 1;
-          if (take(x)) {
-            const uint32_t l3 = mlen_c[x], dd = mdist_c[x];
+          // (LDS classes: phase 6 left its verdict in jump[] — a step of more than one position is a match of that length)
+          uint32_t l3 = 0;
+          bool tk;
+          if constexpr (LDSM) { const uint32_t nxj = jump[x]; tk = nxj > x + 1u; l3 = nxj - x - 3u; }
+          else { tk = take(x); if (tk) l3 = mlen_c[x]; }
+          if (tk) {
+            const uint32_t dd = mdist_c[x];
             uint32_t code, eb, ev;
             len_sym(l3 + 3u, code, eb, ev); atomicAdd(&sm.lf[code], 1u);
             dist_sym(dd, code, eb, ev); atomicAdd(&sm.df[code], 1u);
@@ -1279,7 +1348,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
           idx++;
         }
       }
-      if (t == 0) { atomicAdd(&sm.lf[256], 1u); *(uint32_t*)(rec_c + rec_ntok_off()) = ntok; if (a.prof_ctr) atomicAdd(&a.prof_ctr[a.prof_slot], (unsigned long long)ntok); }
+      if (t == 0) { atomicAdd(&sm.lf[256], 1u); *(uint32_t*)(rec_c + rec_ntok_off()) = ntok; if (a->prof_ctr) atomicAdd(&a->prof_ctr[a->prof_slot], (unsigned long long)ntok); }
       __syncthreads();
       STAMP(5);
       uint32_t* const r_hist = (uint32_t*)rec_c;

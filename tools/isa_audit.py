@@ -86,13 +86,11 @@ def disassemble(elf_bytes):
     return funcs
 
 
-def audit_function(ins):
-    """-> (findings, loops, divergent loops); a finding = (offset, mnemonic, operands, (loop header offset, latch offset)) for a cross-lane
-    instruction inside a divergent NATURAL loop of the kernel's control-flow graph (back edges by dominators: the code layout places loop
-    blocks in front of their header, so address ranges would not do)."""
+def natural_loops(ins):
+    """-> (blocks, block of every instruction, successors, loops) of one kernel's instruction list: basic blocks as (first, end) instruction
+    indices, and every NATURAL loop as (header block, latch block, body set) — back edges by dominators: the code layout places loop
+    blocks in front of their header, so address ranges would not do.  (tools/spill_audit.py counts per loop with the same graph.)"""
     n = len(ins)
-    if n == 0:
-        return [], 0, 0
     idx = {off: i for i, (off, _, _, _) in enumerate(ins)}
     leaders = {0}
     for i, (off, mn, ops, tgt) in enumerate(ins):
@@ -161,6 +159,15 @@ def audit_function(ins):
                         if q not in body:
                             body.add(q); stack.append(q)
                 loops.append((h, u, body))
+    return blocks, blk_of, succ, loops
+
+
+def audit_function(ins):
+    """-> (findings, loops, divergent loops); a finding = (offset, mnemonic, operands, (loop header offset, latch offset)) for a cross-lane
+    instruction inside a divergent natural loop of the kernel's control-flow graph."""
+    if len(ins) == 0:
+        return [], 0, 0
+    blocks, blk_of, succ, loops = natural_loops(ins)
     EXECB = ("s_cbranch_execnz", "s_cbranch_execz")
     div = []
     for h, u, body in loops:

@@ -11,4 +11,5 @@ for blk in md.split("  - .agpr_count:")[1:]:
     g = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk).group(1)
     name = subprocess.run(["c++filt", g("name")], capture_output=True, text=True).stdout.strip()
     name = re.sub(r"\(.*", "", name).replace("void ", "").replace("dfl::", "")
-    print("%-72s vgpr %3s spill %3s scratch %4s B  lds %6s" % (name[:72], g("vgpr_count"), g("vgpr_spill_count"), g("private_segment_fixed_size"), g("group_segment_fixed_size")))
+    print("%-72s vgpr %3s spill %3s scratch %4s B  sgpr %3s spill %3s  lds %6s" % (name[:72], g("vgpr_count"), g("vgpr_spill_count"), g("private_segment_fixed_size"),
+                                                                                   g("sgpr_count"), g("sgpr_spill_count"), g("group_segment_fixed_size")))
