@@ -162,7 +162,7 @@ constexpr uint32_t SIG_HDR = 32;
 constexpr uint32_t SIG_BYTES = 512;   // 128 x u32 (the device path is specialised to n_hashes = 128)
 
 // this rank's new signatures (sig_all[u_old .. u_old + u_new)) -> its exchange row; a batch with more new stored chunks than a row holds
-// is dropped with status bit 7
+// is dropped with status bit 7 (a defence: the row is sized for the worst-case chunk count of a piece, sb_sig_cap)
 __global__ __launch_bounds__(256) void sig_row_kernel(const uint32_t* __restrict__ sig_all, uint64_t* st, uint64_t sig_cap, uint8_t* __restrict__ row) {
   const uint64_t u_old = st[SB_U_OLD];
   uint64_t u_new = st[SB_U_NEW];
@@ -213,7 +213,8 @@ __global__ __launch_bounds__(256) void ingest_sig_rows_kernel(const uint8_t* __r
 }
 
 // dictionary of every new stored chunk of this rank: own -> its chunk id; remote -> ghost chunk ghost0 + j and request j = (owner, slot),
-// requests grouped by owner (counts[q], counts[world] = total).  One workgroup.
+// requests grouped by owner (counts[q], counts[world] = total; counts[world + 1] = this rank's stored chunks INCLUDING this batch's: the
+// bound of the slots a peer may ask of it in this batch's fetch).  One workgroup.
 __global__ __launch_bounds__(1024) void resolve_bases_kernel(const int64_t* __restrict__ base_g, const uint32_t* __restrict__ keys_g, uint32_t bands,
                                                               const uint32_t* __restrict__ g_owner, const uint64_t* __restrict__ g_local,
                                                               const uint64_t* __restrict__ uniq_all, uint32_t world, uint32_t rank, uint64_t ghost0,
@@ -232,7 +233,7 @@ __global__ __launch_bounds__(1024) void resolve_bases_kernel(const int64_t* __re
     if (bg >= 0 && g_owner[bg] != rank) atomicAdd(&cnt[g_owner[bg]], 1u);
   }
   __syncthreads();
-  if (t == 0) { uint32_t run = 0; for (uint32_t q = 0; q < world; q++) { const uint32_t c = cnt[q]; req_counts[q] = c; cur[q] = run; run += c; } req_counts[world] = run; *n_sel = nu; }
+  if (t == 0) { uint32_t run = 0; for (uint32_t q = 0; q < world; q++) { const uint32_t c = cnt[q]; req_counts[q] = c; cur[q] = run; run += c; } req_counts[world] = run; req_counts[world + 1] = u_old + nu; *n_sel = nu; }
   __syncthreads();
   for (uint64_t k = t; k < nu; k += 1024) {
     const uint64_t gi = m0 + k;
@@ -249,6 +250,12 @@ __global__ __launch_bounds__(1024) void resolve_bases_kernel(const int64_t* __re
     }
     base_all[u_old + k] = bl; sel_base[k] = bc;
   }
+}
+
+// phase B3 of a batch whose status word is set — possibly by the HOST since phase B2 (bit 16: the remote dictionaries did not arrive, so
+// the ghost chunks' bounds are those of an earlier batch) — encodes nothing and commits nothing
+__global__ void drop_failed_kernel(uint64_t* st, uint64_t* n_sel) {
+  if (st[SB_STATUS]) { *n_sel = 0; st[SB_U_NEW] = 0; st[SB_N_NEW] = 0; }
 }
 
 __global__ void advance_g_kernel(uint64_t* gst, const uint64_t* st) {
@@ -436,7 +443,8 @@ extern "C" int hmse_stream_batch(uint8_t* data, uint64_t data_cap, uint64_t batc
 
 
 // ---- global L4 as captured phases (see the kernels above) ----------------------------------------------------------------------
-static uint64_t sb_sig_cap(uint64_t cap_bytes, const hmse_cfg* cfg) { return 2 * (cap_bytes / cfg->avg_size) + 64; }   // twice the expected stored chunks of a piece
+// a signature row holds every chunk a piece can have (like the digest row): a piece of dense cut points, all of them new, is legal input
+static uint64_t sb_sig_cap(uint64_t cap_bytes, const hmse_cfg* cfg) { return sb_cap_chunks(cap_bytes, cfg); }
 
 extern "C" uint64_t hmse_stream_sig_cap(uint64_t cap_bytes, const hmse_cfg* cfg) {
   return (hmse_cfg_validate_impl(cfg) != 0 || cap_bytes == 0) ? 0 : sb_sig_cap(cap_bytes, cfg);
@@ -508,6 +516,7 @@ extern "C" int hmse_stream_piece_encode_g(uint8_t* data, uint64_t data_cap, uint
   if (!ws || ws_bytes < w.total) return HMSE_ENOSPC;
   const uint64_t cap = sb_cap_chunks(cap_bytes, cfg);
   int rc;
+  sb::drop_failed_kernel<<<dim3(1), dim3(1), 0, stream>>>(state, w.n_sel);
   if ((rc = hmse_l1_deflate_dyn(data, data_cap, cuts_all, w.sel_ids, w.sel_base, w.n_sel, cap, state + SB_S_OLD, cfg, out, out_cap, w.out_off, w.kind,
                                 w.dfl_status, w.dfl_ws, w.dfl_bytes, stream)) != HMSE_OK) return rc;
   uint32_t ab = (uint32_t)((cap + 255) / 256); if (ab > 1024) ab = 1024;

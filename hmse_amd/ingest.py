@@ -116,14 +116,23 @@ def fetch_chunks(req: torch.Tensor, u_bases: list, data: torch.Tensor, cuts: tor
 
 
 def fetch_chunks_routed(counts: torch.Tensor, local_idx: torch.Tensor, data: torch.Tensor, cuts: torch.Tensor, uniq_ids: torch.Tensor,
-                        group=None, gather=None):
+                        group=None, gather=None, n_stored: int | None = None, refused: list | None = None):
     """fetch_chunks() with the routing done by the caller: `counts[r]` requests go to rank r, `local_idx` holds the owners' local
     stored-chunk indices grouped by owner in rank order (a multi-rank STREAM's stored chunks interleave in the global numbering, so
-    the owner is looked up, not computed from a base table: stream_dist.GlobalL4StreamIngest).  Returns (bytes, lens) in that order."""
+    the owner is looked up, not computed from a base table: stream_dist.GlobalL4StreamIngest).  Returns (bytes, lens) in that order.
+
+    `n_stored`: how many entries of `uniq_ids` are stored chunks (default: all of it; a stream's array is longer than its fill).
+    COLLECTIVE, and it stays one whatever a peer sends: all FOUR all-to-alls always complete.  A peer's slot outside [0, n_stored) is
+    served as a chunk of length 0, an impossible announced length counts as 0, and the refusal is reported only after the last
+    collective — to the owner (it saw the slot) and to the requester (a chunk it asked for came back with length 0; real chunks
+    hold at least one byte).  Reported: appended to `refused` if the caller gave a list (the call returns, the refused chunks are
+    the zero-length ones), raised as ValueError otherwise."""
     import torch.distributed as dist
     world = dist.get_world_size(group)
     dev = data.device
     xdev = torch.device("cpu") if dist.get_backend(group) == "gloo" else dev
+    n_stored = int(uniq_ids.numel() if n_stored is None else min(int(n_stored), uniq_ids.numel()))
+    why = []
     want = counts.to(xdev)
     asked = torch.empty(world, dtype=torch.int64, device=xdev)
     dist.all_to_all_single(asked, want, group=group)                    # how many chunks each rank asks of me
@@ -131,23 +140,50 @@ def fetch_chunks_routed(counts: torch.Tensor, local_idx: torch.Tensor, data: tor
     ids_in = torch.empty(sum(al), dtype=torch.int64, device=xdev)
     dist.all_to_all_single(ids_in, local_idx.to(xdev), output_split_sizes=al, input_split_sizes=wl, group=group)
     # serve: the requested chunks' bytes, in request order (ids come from other ranks: checked before they index anything)
-    if ids_in.numel() and (int(ids_in.min()) < 0 or int(ids_in.max()) >= uniq_ids.numel()):
-        raise ValueError(f"fetch_chunks: a peer asked for stored chunk {int(ids_in.max())} of {uniq_ids.numel()} (mismatched u_bases?)")
-    cid = uniq_ids[ids_in.to(dev)]
-    lens_out = cuts[cid + 1] - cuts[cid]
+    ids_d = ids_in.to(dev)
+    ok = (ids_d >= 0) & (ids_d < n_stored)
+    if not bool(ok.all()):
+        bad = ids_in[~ok.to(xdev)]
+        why.append(f"fetch_chunks: a peer asked for stored chunk {int(bad[0])} of {n_stored} (mismatched u_bases?); served as an empty chunk")
+    if n_stored:
+        cid = uniq_ids[torch.where(ok, ids_d, torch.zeros_like(ids_d))]
+        lens_out = cuts[cid + 1] - cuts[cid]
+        sane = (lens_out > 0) & (lens_out <= 65536)      # the requester applies the same bound to what it is told: both sides size alike
+        if not bool((sane | ~ok).all()):
+            why.append("fetch_chunks: a requested stored chunk has an impossible length here; served as an empty chunk")
+        ok = ok & sane
+        lens_out = torch.where(ok, lens_out, torch.zeros_like(ids_d))
+    else:
+        cid, lens_out = torch.zeros_like(ids_d), torch.zeros_like(ids_d)
     out_cuts = torch.zeros(cid.numel() + 1, dtype=torch.int64, device=dev)
     torch.cumsum(lens_out, 0, out=out_cuts[1:])
-    payload = (gather or ops.read_assemble)(out_cuts, cid, cuts, data) if cid.numel() else torch.empty(0, dtype=torch.uint8, device=dev)
+    served = ok.nonzero().flatten()          # a refused slot sends no byte: the gather never sees it
+    if served.numel():
+        sc = torch.zeros(served.numel() + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(lens_out[served], 0, out=sc[1:])
+        payload = (gather or ops.read_assemble)(sc, cid[served], cuts, data)
+    else:
+        payload = torch.empty(0, dtype=torch.uint8, device=dev)
     lens_in = torch.empty(sum(wl), dtype=torch.int64, device=xdev)
     dist.all_to_all_single(lens_in, lens_out.to(xdev), output_split_sizes=wl, input_split_sizes=al, group=group)
     oc = out_cuts.tolist()
     send_b = [oc[sum(al[:r + 1])] - oc[sum(al[:r])] for r in range(world)]
+    impossible = (lens_in < 0) | (lens_in > 65536)
+    if bool(impossible.any()):          # (an owner running this code never announces one: it serves such a chunk as empty)
+        why.append("fetch_chunks: a peer announced an impossible chunk length; taken as an empty chunk")
+        lens_in = torch.where(impossible, torch.zeros_like(lens_in), lens_in)
     li = lens_in.tolist()
     recv_b = [sum(li[sum(wl[:r]): sum(wl[:r + 1])]) for r in range(world)]
-    if (lens_in < 0).any() or (lens_in > 65536).any():
-        raise ValueError("fetch_chunks: a peer announced an impossible chunk length")
     got = torch.empty(sum(recv_b), dtype=torch.uint8, device=xdev)
     dist.all_to_all_single(got, payload.to(xdev), output_split_sizes=recv_b, input_split_sizes=send_b, group=group)
+    if li and min(li) == 0:
+        j = li.index(0)
+        owner = next(r for r in range(world) if j < sum(wl[:r + 1]))
+        why.append(f"fetch_chunks: rank {owner} refused request {j} (stored slot {int(local_idx[j])}): no such stored chunk there")
+    if why:
+        if refused is None:
+            raise ValueError("; ".join(why))
+        refused.extend(why)
     return got.to(dev), lens_in.to(dev)
 
 

@@ -100,13 +100,19 @@ class PhaseGraphs:
 # ---------------------------------------------------------------------------------------------------------------------------
 # the chain's sticky status word (state[7])
 # ---------------------------------------------------------------------------------------------------------------------------
+HOST_REFUSED = 1 << 16      # state[7] bit 16: set by the HOST of a captured rank between two phases of a batch (CapturedRankStream._host_refuse)
+
+
 def chain_status_error(status: int, where: str = "", host_error: str | None = None, intact: str = "") -> ValueError:
     return ValueError(
         f"streaming chain status {status:#x}{where}: bit0 chunk capacity, bit1 stored-chunk capacity, bit2 L2 (the batch holds more cut "
         "candidates than the chain's fixed candidate list, or more chunks than its cut list: bytes that dense are ingested by ingest_shard or a "
         "graph=False stream, whose L2 call is run again with a larger list), bit3 exchange row, bit4 workspace not initialised, bit5 state block "
-        "inconsistent ([8] != [1] on one rank), bit6 a piece refused by push()" + (f" (this rank: {host_error})" if host_error else "")
-        + ", bit7 more new stored chunks than a signature row holds, bits 8.. DEFLATE (0x100 stream capacity, 0x200 workspace); the failing batch "
+        "inconsistent ([8] != [1] on one rank), bit6 a piece refused by push()" + (f" (this rank: {host_error})" if host_error and not status & HOST_REFUSED else "")
+        + ", bit7 more new stored chunks than a signature row holds (the row is sized for the worst-case chunk count of a piece: a row of another "
+        "build), bits 8..12 DEFLATE (0x100 stream capacity, 0x200 workspace), bit16 a batch refused on the host between two phases (a remote "
+        "dictionary a peer did not serve, the ghost area, a phase's error code)" + (f" (this rank: {host_error})" if host_error and status & HOST_REFUSED else "")
+        + "; the failing batch "
         "and every later one were dropped" + intact)
 
 
@@ -274,6 +280,7 @@ class CapturedRankStream(RankStream):
         self._streams = torch.empty(int(stream_capacity or default_stream_capacity(self.capacity)), dtype=torch.uint8, device=device)
         self._state = z(16, torch.int64)
         self._host_error = None
+        self._host_refused = False
         self._ws = ops.stream_workspace(self.cap_bytes, self.cfg, device)
         self.row_bytes = ops.stream_row_bytes(self.cap_bytes, self.cfg)
         self._row = torch.zeros(self.row_bytes, dtype=torch.uint8, device=device)
@@ -293,6 +300,14 @@ class CapturedRankStream(RankStream):
 
     def _mark_refused(self) -> None:
         self._state[7:8] |= 64
+
+    def _host_refuse(self, reason: str) -> None:
+        """A rank-local failure BETWEEN two phases of a batch (the peers are at, or on their way to, the next collective): like
+        _mark_refused, a sticky bit of the device's status word, set in stream order — so the phases enqueued after it drop the batch,
+        every later batch is a no-op, the rank keeps taking part in every collective, and finish() raises on every rank."""
+        self._host_error = self._host_error or reason
+        self._host_refused = True
+        self._state[7:8] |= HOST_REFUSED
 
     def _gather(self, row: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
         if self.world == 1 and not self._always_exchange:

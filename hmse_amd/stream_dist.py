@@ -344,7 +344,7 @@ class GlobalL4StreamIngest(RankStream):
         """Run one stage; its rank-local refusal (a capacity) is agreed with the peers before anybody meets the next collective."""
         try:
             out, err = fn(*args), None
-        except ValueError as e:
+        except Exception as e:        # (ops.HmseError is a RuntimeError)
             out, err = None, e
         self._agree(err)
         return out
@@ -370,7 +370,8 @@ class GlobalL4StreamIngest(RankStream):
         counts_u = [b - a for a, b in zip(ub, list(ub[1:]) + [alls.shape[0]])]
         rc, rl = self._guard(self.stage_lsh, alls, counts_u)
         uniq_all = torch.cat(self._uniq + [self._cur["uniq_new"]])
-        ghost, glens = fetch_chunks_routed(rc, rl, self.data, self._cuts, uniq_all, self.group)
+        # (the fetch completes its collectives whatever a peer sent and raises behind the last one: agreed like a stage's refusal)
+        ghost, glens = self._guard(fetch_chunks_routed, rc, rl, self.data, self._cuts, uniq_all, self.group)
         self._guard(self.stage_encode, ghost, glens)
 
     def finish(self) -> ShardResult:

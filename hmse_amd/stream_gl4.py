@@ -12,9 +12,12 @@ fixed-size is: per batch and rank
     --        remote dictionaries fetched (ingest.fetch_chunks_routed: the ONE step left eager; skipped with one rank)
     phase B3  hmse_stream_piece_encode_g  DEFLATE, tails, states advanced
 
-each phase captured into a hipGraph at its second use and replayed afterwards; the host reads ONE small array per batch (the request counts,
-only when world > 1).  The result of every rank equals `GlobalL4StreamIngest`'s (tests/test_gpu_stream_gl4.py: 2 and 3 ranks in lock step
-against the oracle's single pass over the logical stream).
+each phase captured into a hipGraph at its second use and replayed afterwards; the host reads ONE small array per batch (the request counts
+and this rank's stored count, only when world > 1).  Whatever a rank cannot do between two collectives (a fetch that a peer refused, a
+ghost area too small, a phase's error code) becomes sticky status bit 16 on the device: the rank drops the batch, stays in every
+collective with empty rows, and finish() raises on every rank.  The result of every rank equals `GlobalL4StreamIngest`'s
+(tests/test_gpu_stream_gl4.py: 2 and 3 ranks in lock step, and two real processes over gloo, against the oracle's single pass over the
+logical stream).
 """
 from __future__ import annotations
 
@@ -25,7 +28,8 @@ import torch
 from . import _lib, ops
 from .config import IngestConfig
 from .ingest import ShardResult
-from .stream_common import CapturedRankStream, lockstep_ranks, max_stored, remote_base_rows, serve_chunks, serve_requests
+from .stream_common import (CapturedRankStream, chain_status_error, lockstep_ranks, max_stored, remote_base_rows, serve_chunks,
+                            serve_requests)
 
 
 class GraphGlobalL4StreamIngest(CapturedRankStream):
@@ -58,7 +62,7 @@ class GraphGlobalL4StreamIngest(CapturedRankStream):
         self.sig_row_bytes = ops.stream_sig_row_bytes(self.cap_bytes, cfg)
         self._sig_row = z(self.sig_row_bytes, torch.uint8)
         self._sig_rows = z(self.world * self.sig_row_bytes, torch.uint8)
-        self._req_counts = z(self.world + 1, torch.int64)
+        self._req_counts = z(self.world + 2, torch.int64)      # [world] = total, [world + 1] = this rank's stored chunks, this batch's included
         self._req_slots = z(self.sig_cap, torch.int64)
         g = _lib.HmseGl4()
         g.struct_size = C.sizeof(_lib.HmseGl4); g.world = self.world; g.rank = self.rank; g.reserved = 0
@@ -70,6 +74,7 @@ class GraphGlobalL4StreamIngest(CapturedRankStream):
         self._gl4 = g
         self.remote_dictionaries = 0
         self.ghost_bytes_fetched = 0
+        self.n_stored_now = 0                        # what requests() last read: the bound of the slots a peer may ask for
 
     # ------------------------------------------------------------------ the phases of one batch (enqueue only; captured at a size's second use)
     def phase_a(self, n: int) -> torch.Tensor:
@@ -96,8 +101,12 @@ class GraphGlobalL4StreamIngest(CapturedRankStream):
 
     # ------------------------------------------------------------------ the remote dictionaries of a batch (eager)
     def requests(self):
-        """(requests per owner rank [world], the owners' stored slots grouped by owner) of the batch phase B2 just resolved — ONE host read."""
+        """(requests per owner rank [world], the owners' stored slots grouped by owner) of the batch phase B2 just resolved — ONE host read,
+        which also brings this rank's stored count (`n_stored_now`: what a peer may ask of it in this batch)."""
         c = self._req_counts.tolist()
+        self.n_stored_now = c[self.world + 1]
+        if self._host_refused:          # this rank is out: it asks for nothing (the array may be a batch old), and goes on serving
+            return [0] * self.world, self._req_slots[:0]
         return c[: self.world], self._req_slots[: c[self.world]]
 
     def serve(self, local_slots: torch.Tensor):
@@ -106,11 +115,13 @@ class GraphGlobalL4StreamIngest(CapturedRankStream):
         return serve_chunks(self._uniq, self._cuts, self.data, local_slots)
 
     def write_ghost(self, ghost: torch.Tensor, lens: torch.Tensor) -> None:
-        """The fetched dictionaries, in request order, behind this rank's data; their bounds behind its cuts (request j = chunk ghost_chunk0 + j)."""
+        """The fetched dictionaries, in request order, behind this rank's data; their bounds behind its cuts (request j = chunk ghost_chunk0 + j).
+        A batch whose dictionaries do not fit is REFUSED through the chain (status bit 16), never raised: the peers are at the next collective."""
         gb, k = int(ghost.numel()), int(lens.numel())
         if gb > self.ghost_cap or k > self.sig_cap:
-            raise ValueError(f"a batch needs {gb} bytes / {k} remote dictionaries, the ghost area holds {self.ghost_cap} bytes / {self.sig_cap} chunks (ghost_bytes=)")
-        if k:
+            self._host_refuse(f"a batch needs {gb} bytes / {k} remote dictionaries, the ghost area holds {self.ghost_cap} bytes / {self.sig_cap} chunks (ghost_bytes=)")
+            return
+        if k and not self._host_refused:
             self.data[self.capacity: self.capacity + gb] = ghost
             g0 = self.ghost_chunk0
             self._cuts[g0] = self.capacity
@@ -119,17 +130,34 @@ class GraphGlobalL4StreamIngest(CapturedRankStream):
             self.ghost_bytes_fetched += gb
 
     # ------------------------------------------------------------------ N processes: the phases joined by collectives
+    def _try(self, what: str, fn, *args):
+        """One phase of a batch.  A rank that raised here alone would leave its peers blocked in the batch's next collective with no diagnosis
+        (ADVICE r3), so its failure (ops.HmseError is a RuntimeError) is refused through the chain instead; -> None then."""
+        try:
+            return fn(*args)
+        except Exception as e:
+            self._host_refuse(f"{what}: {e}")
+            return None
+
     def _process(self, off: int, n: int, copied) -> None:
         torch.cuda.current_stream().wait_event(copied)
-        rows = self._gather(self.phase_a(n), self._rows)
-        sig_rows = self._gather(self.phase_b1(n, rows), self._sig_rows)
-        self.phase_b2(n, sig_rows)
+        if self._try("phase A", self.phase_a, n) is None:
+            self._row[:8] = 0                       # (the row of an earlier batch must not be gathered again)
+        rows = self._gather(self._row, self._rows)
+        if self._try("phase B1", self.phase_b1, n, rows) is None:
+            self._sig_row[:8] = 0
+        sig_rows = self._gather(self._sig_row, self._sig_rows)
+        self._try("phase B2", self.phase_b2, n, sig_rows)
         if self.world > 1:
             from .ingest import fetch_chunks_routed
             counts, slots = self.requests()
-            ghost, lens = fetch_chunks_routed(torch.tensor(counts, dtype=torch.int64), slots, self.data, self._cuts, self._uniq, self.group)
+            refused = []
+            ghost, lens = fetch_chunks_routed(torch.tensor(counts, dtype=torch.int64), slots, self.data, self._cuts, self._uniq, self.group,
+                                              n_stored=self.n_stored_now, refused=refused)
+            if refused:
+                self._host_refuse("; ".join(refused))
             self.write_ghost(ghost, lens)
-        self.phase_b3(n)
+        self._try("phase B3", self.phase_b3, n)     # (the status bit is on the device by now: B3 and every later batch are no-ops)
 
     # ------------------------------------------------------------------ results
     def finish(self, check: bool = True) -> ShardResult:
@@ -142,18 +170,44 @@ class GraphGlobalL4StreamIngest(CapturedRankStream):
                             remote_bases=remote_base_rows(bg, base, kind, self._g_owner, self._g_local))
 
 
-def stream_shards_local_gl4_graph(batches: list, cfg: IngestConfig, world: int, device, **kw) -> list:
-    """A `world`-rank captured global-L4 stream with every rank on THIS GPU, in lock step: per global batch each phase of every rank, the
-    exchanges delivered as the collectives would (rows concatenated in rank order; remote dictionaries served by the owner's `serve`).
-    Each result is what the rank would hold after GraphGlobalL4StreamIngest.finish()."""
-    ranks, steps = lockstep_ranks(batches, cfg, world, lambda cap, pb, r: GraphGlobalL4StreamIngest(cfg, cap, pb, device, world, r, **kw))
+def lockstep_gl4_graph(batches: list, cfg: IngestConfig, world: int, device, rank_kw: list | None = None, setup=None, **kw) -> list:
+    """`world` ranks of a captured global-L4 stream on THIS GPU, driven in lock step over `batches`: per global batch each phase of every rank,
+    the exchanges delivered as the collectives would (rows concatenated in rank order; remote dictionaries served by the owner's `serve`,
+    a slot at or above the owner's stored count refused on both sides as ingest.fetch_chunks_routed does).  `rank_kw[r]`: keyword
+    arguments of rank r alone; `setup(ranks)` runs before the first batch.  -> the ranks, before finish()."""
+    mk = lambda cap, pb, r: GraphGlobalL4StreamIngest(cfg, cap, pb, device, world, r, **{**kw, **(rank_kw[r] if rank_kw else {})})
+    ranks, steps = lockstep_ranks(batches, cfg, world, mk)
+    if setup is not None:
+        setup(ranks)
     for ns in steps:
         rows = torch.cat([s.phase_a(n).clone() for n, s in zip(ns, ranks)])
         sig_rows = torch.cat([s.phase_b1(n, rows).clone() for n, s in zip(ns, ranks)])
         for n, s in zip(ns, ranks):
             s.phase_b2(n, sig_rows)
-        for s in ranks:
-            s.write_ghost(*serve_requests(ranks, *s.requests()))
+        reqs = [s.requests() for s in ranks]          # (every rank's stored count is read before anybody is served)
+        for s, (counts, slots) in zip(ranks, reqs):
+            o, bad = 0, None
+            for owner, cnt in enumerate(counts):
+                if cnt and int(slots[o: o + cnt].max()) >= ranks[owner].n_stored_now:
+                    bad = owner
+                    ranks[owner]._host_refuse(f"fetch_chunks: a peer asked for stored chunk {int(slots[o: o + cnt].max())} of {ranks[owner].n_stored_now}")
+                o += cnt
+            if bad is not None:
+                s._host_refuse(f"fetch_chunks: rank {bad} refused a request: no such stored chunk there")
+            else:
+                s.write_ghost(*serve_requests(ranks, counts, slots))
         for n, s in zip(ns, ranks):
             s.phase_b3(n)
+    return ranks
+
+
+def stream_shards_local_gl4_graph(batches: list, cfg: IngestConfig, world: int, device, **kw) -> list:
+    """A `world`-rank captured global-L4 stream with every rank on THIS GPU (lockstep_gl4_graph).  Each result is what the rank would hold
+    after GraphGlobalL4StreamIngest.finish() — which fails on EVERY rank if one rank dropped a batch (between processes: the all-reduce
+    of the status; here the same rule by hand, for the peers of such a rank have indexed chunks that nobody stores)."""
+    ranks = lockstep_gl4_graph(batches, cfg, world, device, **kw)
+    status = [int(s._state[7].item()) for s in ranks]
+    if any(status):
+        r = max(range(world), key=lambda i: status[i])
+        raise chain_status_error(status[r], f" on rank {r}", ranks[r]._host_error)
     return [s.finish() for s in ranks]

@@ -362,16 +362,22 @@ int hmse_stream_piece_encode(uint8_t* data, uint64_t data_cap, uint64_t piece_by
  * finds, for each of its chunks, the dictionary that ONE rank ingesting the whole stream would find.  Phase B of a batch becomes three
  * enqueue-only calls around two more exchange steps:
  *   hmse_stream_piece_sign      rows of all ranks (as for hmse_stream_piece_encode) -> global index -> this rank's new stored chunks ->
- *                               MinHash -> sig_row {u64 count, u64 first local stored slot, 16 B pad, sig_cap x 512 B}
+ *                               MinHash -> sig_row {u64 count, u64 first local stored slot, 16 B pad, sig_cap x 512 B}, sig_cap = the row's chunk capacity
+ *                               (hmse_stream_sig_cap: the worst-case chunk count of a piece, as in the digest row)
  *   -- all-gather of the signature rows (fixed size: hmse_stream_sig_row_bytes) --
  *   hmse_stream_piece_bases     sig rows -> global signature array + owner map -> global band tables -> for every new stored chunk of
  *                               this rank its dictionary: a chunk of this rank, or a REMOTE one -> request (owner, owner's stored slot);
- *                               g->req_counts[q] requests to rank q ([world] = total), g->req_slots grouped by owner
+ *                               g->req_counts[q] requests to rank q ([world] = total, [world + 1] = this rank's stored chunks including
+ *                               this batch's: the bound of the slots a peer may ask of it now), g->req_slots grouped by owner
  *   -- the requested chunks are fetched (all-to-all; the caller writes the bytes behind its data and their bounds into
  *      cuts_all[g->ghost_chunk0 ..]: request j is chunk ghost_chunk0 + j) --
  *   hmse_stream_piece_encode_g  DEFLATE of the new stored chunks with those dictionaries, tails, both state blocks advanced
  * gstate: DEVICE u64[16], word [3] = stored chunks of ALL ranks before this batch, [4] = of this batch (out), [10] = global stored index
- * of this rank's first new chunk (out).  Status bits as hmse_stream_batch, plus bit7: more new stored chunks than a signature row holds.
+ * of this rank's first new chunk (out).  Status bits as hmse_stream_batch, plus bit7: more new stored chunks than a signature row holds
+ * (sig_cap is the worst-case chunk count of a piece, cap_bytes / min_size + segments + 2, so phase A's own bound fires first: a defence
+ * against a row that another build wrote).  Bit6 (a piece refused by the caller's feeder) and bit16 (a refusal on the host between the
+ * phases of a batch: the fetch of the remote dictionaries, the ghost area, a phase's return code) are set by the CALLER, before the next
+ * phase is enqueued, to drop the batch through the chain instead of leaving the collectives alone.
  * All arrays are the caller's; sizes in the struct.
  */
 typedef struct hmse_gl4 {
@@ -388,7 +394,7 @@ typedef struct hmse_gl4 {
   uint64_t* g_local;       /* [max_stored_g] the owner's stored slot */
   uint64_t* ug;            /* [max_unique] this rank's stored chunks: global stored index (out, appended) */
   int64_t*  base_global;   /* [max_unique] this rank's stored chunks: base_g (out, appended) */
-  uint64_t* req_counts;    /* DEVICE u64[world + 1] (out) */
+  uint64_t* req_counts;    /* DEVICE u64[world + 2] (out) */
   uint64_t* req_slots;     /* DEVICE u64[cap chunks of a piece] (out) */
   uint64_t  ghost_chunk0;  /* chunk id of the batch's first fetched dictionary */
 } hmse_gl4;

@@ -137,6 +137,33 @@ def l2_corpus_with_dense_stretch(pair, text: np.ndarray):
     return np.concatenate([t, pair_run(600_000, pair), v, t[200_000: 500_000]]), {"dense_bytes": 600_000}
 
 
+# ---- a piece of dense CUT POINTS (not dense candidates): the stream chain's per-chunk rows -----------------------------------------
+DENSE_CUT_FILL, DENSE_CUT_RUN = 2040, 72
+
+
+def dense_cut_piece(pair, n: int, seed: int, text: bool = False) -> np.ndarray:
+    """n bytes whose chunks are about as small as chunks get: DENSE_CUT_FILL bytes of filler (random bytes, or words with `text`: every
+    period different, so all digests differ), then DENSE_CUT_RUN bytes of `pair` — a pair of dense_pairs(G, mask_s), the HARD mask, so the
+    first position of the run that is min_size (2048) behind the last cut is a cut: one chunk per period of 2112 bytes, a quarter of
+    avg_size.  The runs are short: the candidate count stays far below the list's capacity (unlike l2_overflow)."""
+    period = DENSE_CUT_FILL + DENSE_CUT_RUN
+    k = -(-n // period)
+    fill = (words_text(k * DENSE_CUT_FILL, seed=seed) if text else np.random.default_rng(seed).integers(0, 256, k * DENSE_CUT_FILL, dtype=np.uint8))
+    out = np.empty((k, period), np.uint8)
+    out[:, :DENSE_CUT_FILL] = np.asarray(fill[: k * DENSE_CUT_FILL]).reshape(k, DENSE_CUT_FILL)
+    out[:, DENSE_CUT_FILL:] = pair_run(DENSE_CUT_RUN, pair)
+    return out.reshape(-1)[:n].copy()
+
+
+def dense_cut_near_duplicate(piece: np.ndarray, every: int = 1) -> np.ndarray:
+    """A dense-cut piece for ANOTHER piece of the stream: the same bytes with one letter's case flipped in the middle of every `every`-th
+    period's filler (far from the 64-byte windows that decide the cuts): the same cut points, chunks that are near-duplicates of
+    `piece`'s — dictionaries for L4 to find on whichever rank got `piece`."""
+    out = piece.copy()
+    out[DENSE_CUT_FILL // 2:: (DENSE_CUT_FILL + DENSE_CUT_RUN) * every] ^= 0x20
+    return out
+
+
 # ---- L1 DEFLATE: windows on the class caps --------------------------------------------------------------------------------------
 CONTENTS = ("text", "neardup", "run", "period", "random")
 

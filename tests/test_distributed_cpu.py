@@ -112,6 +112,81 @@ def test_cross_rank_base_fetch_three_ranks():
     assert ub[3] == len(stored)
 
 
+def _bad_slot_worker(rank, world, port, shards, n_stored, reqs, out_q):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from hmse_amd import ingest
+        data, cuts, uniq = (torch.from_numpy(x) for x in shards[rank])
+
+        def gather(out_cuts, cid, cuts_, data_):      # the HIP gather (hmse_read_assemble) restated for the CPU test
+            return torch.cat([data_[int(cuts_[c]): int(cuts_[c + 1])] for c in cid.tolist()]) if cid.numel() else data_[:0]
+        counts, slots = reqs[rank]
+        refused = []
+        got, lens = ingest.fetch_chunks_routed(torch.tensor(counts, dtype=torch.int64), torch.tensor(slots, dtype=torch.int64), data, cuts, uniq,
+                                               gather=gather, n_stored=n_stored[rank], refused=refused)
+        out_q.put((rank, got.numpy().copy(), lens.numpy().copy(), refused))
+    except Exception as e:                             # (reported, so that the test fails at once and with the reason)
+        out_q.put((rank, None, None, ["worker raised " + repr(e)]))
+    dist.barrier()                                     # every rank came back from the fetch: nobody is left in a collective
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("case", ["beyond_the_array", "inside_the_array_beyond_the_stored_count"])
+def test_a_peer_s_out_of_range_slot_is_refused_behind_the_last_collective_never_served_as_chunk_0(case):
+    """fetch_chunks_routed is a collective; ids come from other ranks.  Rank 2 asks rank 0 for a stored slot rank 0 does not have.  The owner
+    must not raise between two all-to-alls (its peers would block in the next one), and must not index with it: a stream's stored-id
+    array (GraphGlobalL4StreamIngest._uniq) is LONGER than its fill, its tail is zeros, so a slot inside the array but at or above the
+    stored count names chunk 0 — whose bytes the requester would take for its dictionary.  All four all-to-alls complete on all three
+    ranks; the bad slot comes back as a chunk of length 0; owner and requester report it; the bystander's fetch is exact."""
+    rng = np.random.default_rng(11)
+    shards, stored, n_stored = [], [], []
+    for r in range(3):
+        lens = rng.integers(1, 4000, 40 + 7 * r)
+        cuts = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        data = rng.integers(0, 256, int(cuts[-1]), dtype=np.uint8)
+        uniq = np.sort(rng.choice(np.arange(1, len(lens)), 25 + r, replace=False)).astype(np.int64)     # the chunks this rank stores (never chunk 0)
+        stored.append([data[cuts[c]: cuts[c + 1]] for c in uniq])
+        if case == "beyond_the_array":
+            n_stored.append(None)
+        else:
+            n_stored.append(len(uniq))
+            uniq = np.concatenate([uniq, np.zeros(64 - len(uniq), np.int64)])                           # capacity 64, zeros behind the fill
+        shards.append([data, cuts, uniq])
+    bad = 64 + 5 if case == "beyond_the_array" else 30          # rank 0 stores 25 chunks
+    reqs = [([0, 2, 2], [5, 6, 9, 10]),
+            ([1, 0, 1], [3, 0]),
+            ([3, 1, 0], [0, bad, 24, 25])]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_bad_slot_worker, args=(r, 3, port, shards, n_stored, reqs, q)) for r in range(3)]
+    for p in procs:
+        p.start()
+    try:
+        got = {t[0]: t[1:] for t in (q.get(timeout=120) for _ in range(3))}
+        for p in procs:
+            p.join(timeout=60)
+            assert p.exitcode == 0                                # ... and reached the barrier behind it
+    finally:
+        for p in procs:
+            if p.is_alive():
+                p.terminate()
+    assert all(g[0] is not None for g in got.values()), [g[2] for g in got.values()]
+    want = {0: [stored[1][5], stored[1][6], stored[2][9], stored[2][10]], 1: [stored[0][3], stored[2][0]],
+            2: [stored[0][0], np.zeros(0, np.uint8), stored[0][24], stored[1][25]]}
+    for r in range(3):
+        payload, lens, _ = got[r]
+        assert lens.tolist() == [len(w) for w in want[r]], r
+        assert np.array_equal(payload, np.concatenate(want[r])), r
+    assert got[1][2] == []                                        # the bystander saw nothing of it
+    assert len(got[0][2]) == 1 and f"asked for stored chunk {bad} of 25" in got[0][2][0]
+    assert len(got[2][2]) == 1 and "rank 0 refused request 1" in got[2][2][0]
+    chunk0 = shards[0][0][: int(shards[0][1][1])]                  # what the parent's code sent for the slot inside the array
+    assert got[2][1][1] == 0 and got[2][0].size == sum(len(w) for w in want[2]) and chunk0.size > 0
+
+
 def _row_worker(rank, world, port, rows_by_batch, out_q):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -196,14 +271,19 @@ def _agree_worker(rank, world, port, q):
     s = object.__new__(GlobalL4StreamIngest)          # the agreement logic only: no device state
     s.world, s.rank, s.group, s.failed = world, rank, None, False
 
-    def stage(ok):
+    def stage(ok, exc=ValueError):
         if not ok:
-            raise ValueError("stream index capacity exceeded (max_chunks)")
+            raise exc("stream index capacity exceeded (max_chunks)")
         return 7
     out = []
     out.append(s._guard(stage, True))                 # batch 1: both fine
     try:
         s._guard(stage, rank != 1)                    # batch 2: rank 1 is refused
+        out.append("no error")
+    except ValueError as e:
+        out.append(str(e))
+    try:                                              # a stage's HmseError is a RuntimeError: agreed like a capacity, not raised alone
+        s._guard(stage, rank != 0, RuntimeError)
         out.append("no error")
     except ValueError as e:
         out.append(str(e))
@@ -230,3 +310,4 @@ def test_a_rank_local_refusal_in_a_global_l4_stream_raises_on_every_rank():
     for r in range(world):
         assert got[r][0] == 7
         assert "rank 1: stream index capacity exceeded" in got[r][1] and "abandoned on every rank" in got[r][1]
+        assert "rank 0: stream index capacity exceeded" in got[r][2] and "abandoned on every rank" in got[r][2]

@@ -237,3 +237,38 @@ def test_hot_bucket_populations(spread, K):
         nh = struct.unpack_from("<Q", one, 8 + 24)[0]
         hdr = np.frombuffer(one, bandtable.HDR_DTYPE, nh, 8 + 24 + 8)
         assert int((hdr["band_hash"] == 0x1234).sum()) == pieces, (hot, pieces)
+
+
+@pytest.mark.parametrize("text", [False, True], ids=["random", "text"])
+@pytest.mark.parametrize("mib", [1, 2])
+def test_dense_cut_piece_has_more_chunks_than_twice_the_expected_count_and_few_candidates(orc, K, mib, text):
+    """The facts tests/test_gpu_stream_gl4.py's dense-piece test relies on, from the oracle: a nominal piece of dense_cut_piece() holds more
+    chunks than `2 * piece / avg_size + 64` (what a signature row of the captured global-L4 stream held before it was sized like every other
+    array of the chain), no more than the chain's worst case `piece / min_size + segments + 2`, every chunk different (all of them are
+    stored), and so few cut candidates that the fixed candidate list never overflows (status bit 2 cannot stand in for the row's bit 7).
+    The formulas are written out, not read from the library: retune a size and this fails first."""
+    from hmse_amd import IngestConfig
+    cfg = IngestConfig(seg_size=1 << 20)
+    oc = orc.default_cfg(**asdict(cfg))
+    G = orc.gear_table()
+    ms, ml = orc.cdc_masks(oc)
+    pairs = E.dense_pairs(G, ms)
+    assert pairs, "no byte pair whose alternating run passes the HARD mask: a cut just behind min_size cannot be forced for the default configuration"
+    assert pairs[0] in E.dense_pairs(G, ml)                   # (the hard mask's bits include the easy mask's)
+    piece = mib << 20
+    data = E.dense_cut_piece(pairs[0], piece, seed=5, text=text)
+    assert data.size == piece and np.array_equal(data, E.dense_cut_piece(pairs[0], piece, seed=5, text=text))      # deterministic
+    cuts = orc.cdc(data, oc)
+    n_chunks = len(cuts) - 1
+    segments = piece // cfg.seg_size
+    assert n_chunks > 2 * (piece // cfg.avg_size) + 64
+    assert n_chunks <= piece // cfg.min_size + segments + 2
+    assert int(np.diff(cuts.astype(np.int64)).min()) >= 1 and int(np.median(np.diff(cuts.astype(np.int64)))) == E.DENSE_CUT_FILL + E.DENSE_CUT_RUN
+    dg = orc.sha256_chunks(data, cuts)
+    assert len(np.unique(dg, axis=0)) == n_chunks
+    assert int(E.gear_candidates(data, G, ml).sum()) < E.l2_cand_capacity(piece, cfg, K)
+    # the planted near-duplicates: same cut points, every chunk different from its original AND from every other chunk
+    twin = E.dense_cut_near_duplicate(data)
+    assert np.array_equal(orc.cdc(twin, oc), cuts)
+    both = np.concatenate([dg, orc.sha256_chunks(twin, cuts)])
+    assert len(np.unique(both, axis=0)) >= 2 * n_chunks - 1    # (the last period may end in front of its flipped byte)
