@@ -234,6 +234,7 @@ __global__ __launch_bounds__(64) void bt_status_kernel(uint32_t* status, uint32_
 extern "C" int hmse_band_tables_write(const uint32_t* band_keys, uint64_t n, uint32_t bands, uint32_t band_bits, const uint32_t* sig,
                                       uint32_t n_hashes, uint8_t* out, uint64_t out_cap, uint64_t* out_bytes, uint32_t* status, void* ws,
                                       size_t ws_bytes, void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   if (!out_bytes || !status || !out || bands == 0) return HMSE_EINVAL;
   if (n && !band_keys) return HMSE_EINVAL;
   if (n && n_hashes && !sig) return HMSE_EINVAL;
@@ -353,6 +354,7 @@ static int bt_sort_u32(const uint32_t* keys, uint64_t n, uint32_t stride, uint32
 
 extern "C" int hmse_l4_index_build(const uint32_t* keys, uint64_t n, uint32_t bands, uint32_t* sorted_keys, uint32_t* sorted_ids,
                                    uint32_t* status, void* ws, size_t ws_bytes, void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   if (!status || bands == 0 || bands > 16 || (bands & (bands - 1))) return HMSE_EINVAL;
   if (n >= (1ull << 32)) return HMSE_EINVAL;
   if (n && (!keys || !sorted_keys || !sorted_ids)) return HMSE_EINVAL;

@@ -18,6 +18,13 @@
 
 static inline size_t hmse_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// A workspace is 256-byte aligned (include/hmse.h): the carver below hands out 256-byte pieces and the kernels store 16 bytes at a time
+// into them.  First statement of every entry point that takes one: HMSE_EINVAL before anything is cleared or launched.
+#define HMSE_WS_ALIGNED(ws)                                     \
+  do {                                                          \
+    if (((uintptr_t)(ws)) & 255u) return HMSE_EINVAL;           \
+  } while (0)
+
 // carve a sub-buffer out of the caller's workspace (256-B aligned pieces)
 struct WsCarver {
   uint8_t* base;

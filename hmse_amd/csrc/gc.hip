@@ -126,6 +126,7 @@ extern "C" int hmse_gc_plan(const uint64_t* cuts, uint64_t n_chunks, const uint3
                             uint32_t n_seg, const uint8_t* drop, const uint8_t* digests_old, uint64_t* counts, int64_t* old_chunk,
                             int64_t* first_occ, uint32_t* refcount, uint8_t* digests, int64_t* uniq_ids, int64_t* old_slot,
                             int64_t* new_slot_of_old, uint32_t* status, void* ws, size_t ws_bytes, void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   if (!counts || !status || n_seg == 0 || !seg_off || !drop) return HMSE_EINVAL;
   if (n_chunks >= 0x7FFFFFFFull || n_slots > n_chunks) return HMSE_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;

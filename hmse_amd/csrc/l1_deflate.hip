@@ -2026,6 +2026,7 @@ static int deflate_impl(const uint8_t* data, uint64_t n, const uint64_t* cuts, c
                         const int64_t* base, uint64_t n_sel, const uint64_t* n_dev, const uint64_t* out_base_dev, const hmse_cfg* cfg, uint32_t flags,
                         uint8_t* out, uint64_t out_cap, uint64_t* out_off, uint8_t* kind, uint32_t* status, void* ws, size_t ws_bytes,
                         void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   using namespace dfl;
   if (hmse_cfg_validate_impl(cfg) != 0) return HMSE_EINVAL;
   if (flags & ~(uint32_t)HMSE_DEFLATE_BASE_IS_CHUNK_ID) return HMSE_EINVAL;

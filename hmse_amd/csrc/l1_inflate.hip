@@ -1007,6 +1007,7 @@ size_t hmse_l1_inflate_workspace_bytes_impl(uint64_t n_sel) { return 256 + hmse_
 extern "C" int hmse_l1_inflate(const uint8_t* streams, uint64_t streams_bytes, const uint64_t* stream_off, const uint32_t* stream_len,
                                const uint8_t* kind, const int64_t* base, uint64_t n_sel, const uint64_t* raw_off, uint8_t* raw_out,
                                uint64_t raw_cap, uint8_t* ok, uint32_t* status, void* ws, size_t ws_bytes, void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   using namespace ifl;
   if (!status) return HMSE_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;

@@ -455,6 +455,7 @@ extern "C" int hmse_l2_cdc(const uint8_t* data, uint64_t n, const uint64_t* seg_
 int hmse_l2_cdc_impl(const uint8_t* data, const uint64_t* data_off_dev, uint64_t n, const uint64_t* seg_off, uint32_t n_seg,
                      const hmse_cfg* cfg, uint64_t* cuts, uint64_t cuts_cap, uint64_t* n_cuts, uint32_t* status, void* ws,
                      size_t ws_bytes, hipStream_t stream_) {
+  HMSE_WS_ALIGNED(ws);
   if (hmse_cfg_validate_impl(cfg) != 0) return HMSE_EINVAL;
   if (!cuts || !n_cuts || !status || !seg_off || cuts_cap < 1) return HMSE_EINVAL;
   if (n > 0 && !data) return HMSE_EINVAL;

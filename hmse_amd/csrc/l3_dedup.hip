@@ -88,6 +88,7 @@ size_t hmse_l3_dedup_workspace_bytes_impl(uint64_t n) { return hmse_align_up((si
 
 extern "C" int hmse_l3_dedup(const uint8_t* digests_all, uint64_t n_all, uint64_t* first_occ, uint32_t* refcount, void* ws,
                              size_t ws_bytes, void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   if (n_all == 0) return HMSE_OK;
   if (!digests_all || !first_occ) return HMSE_EINVAL;
   if (n_all >= 0x7FFFFFFFull) return HMSE_EINVAL;

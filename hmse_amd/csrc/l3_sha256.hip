@@ -211,6 +211,7 @@ size_t hmse_l3_sha256_workspace_bytes_impl(uint64_t n_chunks) { return 256 + ORD
 
 extern "C" int hmse_l3_sha256(const uint8_t* data, uint64_t n, const uint64_t* cuts, uint64_t n_chunks, uint8_t* digests,
                               void* ws, size_t ws_bytes, void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   if (n_chunks == 0) return HMSE_OK;
   if (!data || !cuts || !digests) return HMSE_EINVAL;
   if (!ws || ws_bytes < 8) return HMSE_ENOSPC;

@@ -113,6 +113,7 @@ size_t hmse_l4_lsh_workspace_bytes_impl(uint64_t n, const hmse_cfg* cfg) {
 
 extern "C" int hmse_l4_lsh(const uint32_t* sig, uint64_t n_sel, const hmse_cfg* cfg, uint32_t* band_keys, int64_t* base,
                            void* ws, size_t ws_bytes, void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   if (hmse_cfg_validate_impl(cfg) != 0) return HMSE_EINVAL;
   if (n_sel == 0) return HMSE_OK;
   if (!sig || !band_keys || !base) return HMSE_EINVAL;

@@ -161,7 +161,8 @@ __global__ __launch_bounds__(NT, NT == 1024 ? 8 : 4) void l4_minhash_kernel(cons
     {
       const uint64_t b0 = start + sub0;                      // byte offset of this pass's first shingle
       const uint32_t sh = (uint32_t)(b0 & 3u);
-      const uint8_t* const abase = data + (b0 - sh);         // 4-byte aligned (data comes from the allocator: 256-byte aligned; offsets are bytes)
+      const uint8_t* const abase = data + (b0 - sh);         // 4-byte aligned when `data` is
+      // any byte pointer is a legal `data` (include/hmse.h): a base off a dword takes the byte-wise branch below, like the buffer's last 12 bytes
       const bool base_aligned = (((uintptr_t)data) & 3u) == 0;
       for (uint32_t p4 = t * 4u; p4 < (V == 3 ? 0u : cnt); p4 += NT * 4u) {
         const uint64_t a = (b0 - sh) + p4;
@@ -377,6 +378,7 @@ size_t hmse_l4_minhash_workspace_bytes_impl(uint64_t) { return 256 + ((size_t)8 
 
 extern "C" int hmse_l4_minhash(const uint8_t* data, uint64_t n, const uint64_t* cuts, const uint64_t* chunk_ids,
                                uint64_t n_sel, const hmse_cfg* cfg, uint32_t* sig, void* ws, size_t ws_bytes, void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   if (hmse_cfg_validate_impl(cfg) != 0) return HMSE_EINVAL;
   if (n_sel == 0) return HMSE_OK;
   if (!data || !cuts || !sig) return HMSE_EINVAL;

@@ -153,6 +153,7 @@ extern "C" int hmse_l4_query(const uint32_t* sig_q, const uint32_t* keys_q, uint
                              const uint32_t* sorted_keys, const uint32_t* sorted_ids, const hmse_cfg* cfg, uint32_t top_k, uint32_t min_score,
                              uint32_t flags, int64_t* out_ids, int32_t* out_scores, uint32_t* n_hits, uint64_t* n_candidates, uint32_t* status,
                              void* ws, size_t ws_bytes, void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   if (hmse_cfg_validate_impl(cfg) != 0) return HMSE_EINVAL;
   if (top_k < 1 || top_k > 64 || min_score > 128 || (flags & ~(uint32_t)HMSE_QUERY_EXCLUDE_SELF)) return HMSE_EINVAL;
   if (n_q >= (1ull << 32) || n_s >= (1ull << 32) || !status) return HMSE_EINVAL;

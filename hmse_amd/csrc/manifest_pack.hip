@@ -143,6 +143,7 @@ extern "C" int hmse_manifest_pack_ex(const uint8_t* streams, const uint64_t* str
                                      uint32_t lba_unit, const uint64_t* ptr_index, uint8_t* blob, uint64_t blob_bytes, void* index,
                                      void* chunk_map, void* pointers, uint64_t n_pointers, uint32_t* status, void* ws, size_t ws_bytes,
                                      void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   using namespace mfp;
   if (flags & ~(uint32_t)HMSE_MANIFEST_ANY_SHARD_TARGET) return HMSE_EINVAL;
   if (!status || lba_unit == 0 || (lba_unit & (lba_unit - 1)) || n_shards == 0 || shard >= n_shards || n_shards > 256) return HMSE_EINVAL;

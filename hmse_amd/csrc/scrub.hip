@@ -268,6 +268,7 @@ extern "C" int hmse_scrub_attribute(uint64_t n, const uint8_t* status, const int
                                     const int64_t* chunk_slot, const uint64_t* cuts, uint8_t* status_out, int64_t* root, int64_t* chunk_root,
                                     uint64_t* root_records, uint64_t* root_chunks, uint64_t* root_bytes, uint64_t* ranges, uint64_t* counts,
                                     void* ws, size_t ws_bytes, void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   if (!counts || n >= 0x7FFFFFFFull || n_chunks >= 0x7FFFFFFFull || max_depth_log2 > 30) return HMSE_EINVAL;
   if (n && (!status || !dict || !ok || !status_out || !root || !root_records || !root_chunks || !root_bytes)) return HMSE_EINVAL;
   if (n && check_digest && (!got_sha || !want_sha)) return HMSE_EINVAL;

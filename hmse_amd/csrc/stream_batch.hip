@@ -314,6 +314,7 @@ extern "C" uint64_t hmse_stream_batch_workspace_bytes(uint64_t cap_bytes, const 
 }
 
 extern "C" int hmse_stream_workspace_init(void* ws, size_t ws_bytes, uint64_t cap_bytes, const hmse_cfg* cfg, void* stream) {
+  HMSE_WS_ALIGNED(ws);
   if (hmse_cfg_validate_impl(cfg) != 0 || cap_bytes == 0 || !ws) return HMSE_EINVAL;
   const sb::Ws w = sb_carve(ws, cap_bytes, cfg);
   if (ws_bytes < w.total) return HMSE_ENOSPC;
@@ -390,6 +391,7 @@ static bool sb_piece_args_ok(uint64_t piece_bytes, uint64_t cap_bytes, uint32_t 
 extern "C" int hmse_stream_piece_hash(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const uint64_t* seg_off,
                                       uint32_t n_seg, const hmse_cfg* cfg, uint64_t* state, uint64_t* cuts_all, uint64_t max_chunks,
                                       uint8_t* row, void* ws, size_t ws_bytes, void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   if (!sb_piece_args_ok(piece_bytes, cap_bytes, n_seg, cfg)) return HMSE_EINVAL;
   if (!data || !state || !cuts_all || !row || (piece_bytes && !seg_off)) return HMSE_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;
@@ -405,6 +407,7 @@ extern "C" int hmse_stream_piece_encode(uint8_t* data, uint64_t data_cap, uint64
                                         uint32_t* l3_table, uint64_t l3_slots, uint64_t* uniq_all, uint64_t max_unique, uint32_t* sig_all,
                                         uint32_t* band_keys, int64_t* base_all, uint32_t* lsh_tables, uint64_t lsh_slots, uint8_t* kind_all,
                                         uint64_t* stream_off_all, uint8_t* out, uint64_t out_cap, void* ws, size_t ws_bytes, void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   if (!sb_piece_args_ok(piece_bytes, cap_bytes, piece_bytes ? 1u : 0u, cfg)) return HMSE_EINVAL;
   if (!data || !state || !rows || !cuts_all || !digests_g || !first_occ_g || !refcount_g || !l3_table || !uniq_all || !sig_all || !band_keys ||
       !base_all || !lsh_tables || !kind_all || !stream_off_all || !out || world == 0 || world > 256 || rank >= world)
@@ -426,6 +429,7 @@ extern "C" int hmse_stream_batch(uint8_t* data, uint64_t data_cap, uint64_t batc
                                  uint64_t max_unique, uint32_t* sig_all, uint32_t* band_keys, int64_t* base_all, uint32_t* lsh_tables,
                                  uint64_t lsh_slots, uint8_t* kind_all, uint64_t* stream_off_all, uint8_t* out, uint64_t out_cap,
                                  void* ws, size_t ws_bytes, void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   if (batch_bytes == 0 || !sb_piece_args_ok(batch_bytes, batch_bytes, n_seg, cfg)) return HMSE_EINVAL;
   if (!data || !seg_off || !state || !cuts_all || !digests_all || !first_occ || !refcount || !l3_table || !uniq_all || !sig_all || !band_keys ||
       !base_all || !lsh_tables || !kind_all || !stream_off_all || !out)
@@ -462,6 +466,7 @@ extern "C" int hmse_stream_piece_sign(uint8_t* data, uint64_t data_cap, uint64_t
                                       const uint8_t* rows, uint32_t world, uint32_t rank, const uint64_t* cuts_all, uint64_t* gidx, uint8_t* digests_g,
                                       uint64_t max_chunks_g, uint64_t* first_occ_g, uint32_t* refcount_g, uint32_t* l3_table, uint64_t l3_slots,
                                       uint64_t* uniq_all, uint64_t max_unique, uint32_t* sig_all, uint8_t* sig_row, void* ws, size_t ws_bytes, void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   if (!sb_piece_args_ok(piece_bytes, cap_bytes, piece_bytes ? 1u : 0u, cfg)) return HMSE_EINVAL;
   if (!data || !state || !rows || !cuts_all || !digests_g || !first_occ_g || !refcount_g || !l3_table || !uniq_all || !sig_all || !sig_row || world == 0 ||
       world > 256 || rank >= world || (world > 1 && !gidx))
@@ -485,6 +490,7 @@ extern "C" int hmse_stream_piece_sign(uint8_t* data, uint64_t data_cap, uint64_t
 
 extern "C" int hmse_stream_piece_bases(uint64_t cap_bytes, const hmse_cfg* cfg, uint64_t* state, const uint8_t* sig_rows, const hmse_gl4* g,
                                        const uint64_t* uniq_all, uint32_t* band_keys, int64_t* base_all, void* ws, size_t ws_bytes, void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   if (hmse_cfg_validate_impl(cfg) != 0 || cap_bytes == 0 || !state || !sig_rows || !gl4_ok(g) || !uniq_all || !band_keys || !base_all) return HMSE_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;
   (void)hipGetLastError();
@@ -508,6 +514,7 @@ extern "C" int hmse_stream_piece_bases(uint64_t cap_bytes, const hmse_cfg* cfg, 
 extern "C" int hmse_stream_piece_encode_g(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const hmse_cfg* cfg, uint64_t* state,
                                           uint64_t* gstate, const uint64_t* cuts_all, uint8_t* kind_all, uint64_t* stream_off_all, uint8_t* out,
                                           uint64_t out_cap, void* ws, size_t ws_bytes, void* stream_) {
+  HMSE_WS_ALIGNED(ws);
   if (!sb_piece_args_ok(piece_bytes, cap_bytes, piece_bytes ? 1u : 0u, cfg)) return HMSE_EINVAL;
   if (!data || !state || !gstate || !cuts_all || !kind_all || !stream_off_all || !out) return HMSE_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;

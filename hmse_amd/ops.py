@@ -53,6 +53,17 @@ def _ws(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+def _buf(shape, dtype, device, fill: int | None = None) -> torch.Tensor:
+    """Every device buffer this module hands to the library besides a workspace (_ws): outputs, status words, placeholders.
+    `fill` (0 or -1) is the wrapper's own caution, not part of the C contract: include/hmse.h tells a caller to clear nothing, the
+    library writes every element it declares valid.  tests/arena.py replaces _ws and _buf to decide what memory a call sees."""
+    if fill is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if fill == 0:
+        return torch.zeros(shape, dtype=dtype, device=device)
+    return torch.full(shape if isinstance(shape, tuple) else (shape,), fill, dtype=dtype, device=device)
+
+
 def workspace_bytes(stage: int, n: int, cfg: IngestConfig) -> int:
     c = cfg.to_c()
     return int(_lib.hip_lib().hmse_workspace_bytes(stage, n, C.byref(c)))
@@ -76,8 +87,8 @@ def l2_cdc(data: torch.Tensor, cfg: IngestConfig, seg_off: torch.Tensor | None =
     c = cfg.to_c()
     lib = _lib.hip_lib()
     cap = n // cfg.min_size + n_seg + 2
-    cuts = torch.empty(cap, dtype=torch.int64, device=dev)
-    meta = torch.zeros(2, dtype=torch.int64, device=dev)  # [n_cuts, status]
+    cuts = _buf(cap, torch.int64, dev)
+    meta = _buf(2, torch.int64, dev, fill=0)  # [n_cuts, status]
     # exact workspace for this segmentation: the generic sizing assumes ceil(n/seg_size) segments
     ws_bytes = workspace_bytes(STAGE_L2, n, cfg) + 24 * max(0, n_seg - n // cfg.seg_size) + 4096
     # The provisioned candidate list holds 8x the expected density.  Bytes that are denser still (status bit 0) are legitimate
@@ -101,7 +112,7 @@ def l3_sha256(data: torch.Tensor, cuts: torch.Tensor) -> torch.Tensor:
     _require_gpu(data, "data")
     _require_gpu(cuts, "cuts")
     n_chunks = cuts.numel() - 1
-    out = torch.empty((max(n_chunks, 0), 32), dtype=torch.uint8, device=data.device)
+    out = _buf((max(n_chunks, 0), 32), torch.uint8, data.device)
     if n_chunks <= 0:
         return out
     ws = _ws(workspace_bytes(STAGE_SHA, n_chunks, IngestConfig()), data.device)
@@ -115,8 +126,8 @@ def l3_dedup(digests: torch.Tensor):
     _require_gpu(digests, "digests")
     n = digests.shape[0]
     dev = digests.device
-    fo = torch.empty(n, dtype=torch.int64, device=dev)
-    rc_t = torch.empty(n, dtype=torch.int32, device=dev)
+    fo = _buf(n, torch.int64, dev)
+    rc_t = _buf(n, torch.int32, dev)
     if n == 0:
         return fo, rc_t
     c = IngestConfig().to_c()
@@ -170,7 +181,7 @@ def l4_minhash(data: torch.Tensor, cuts: torch.Tensor, cfg: IngestConfig, chunk_
     if chunk_ids is not None:
         _require_gpu(chunk_ids, "chunk_ids")
     n_sel = (cuts.numel() - 1) if chunk_ids is None else chunk_ids.numel()
-    sig = torch.empty((max(n_sel, 0), cfg.n_hashes), dtype=torch.int32, device=data.device)
+    sig = _buf((max(n_sel, 0), cfg.n_hashes), torch.int32, data.device)
     if n_sel <= 0:
         return sig
     c = cfg.to_c()
@@ -186,8 +197,8 @@ def l4_lsh(sig: torch.Tensor, cfg: IngestConfig):
     _require_gpu(sig, "sig")
     n = sig.shape[0]
     dev = sig.device
-    keys = torch.empty((n, cfg.bands), dtype=torch.int32, device=dev)
-    base = torch.empty(n, dtype=torch.int64, device=dev)
+    keys = _buf((n, cfg.bands), torch.int32, dev)
+    base = _buf(n, torch.int64, dev)
     if n == 0:
         return keys, base
     c = cfg.to_c()
@@ -241,18 +252,18 @@ def l1_deflate(data: torch.Tensor, cuts: torch.Tensor, cfg: IngestConfig, chunk_
     _require_gpu(cuts, "cuts")
     dev = data.device
     n_sel = (cuts.numel() - 1) if chunk_ids is None else chunk_ids.numel()
-    out_off = torch.zeros(max(n_sel, 0) + 1, dtype=torch.int64, device=dev)
-    kind = torch.zeros(max(n_sel, 0), dtype=torch.uint8, device=dev)
+    out_off = _buf(max(n_sel, 0) + 1, torch.int64, dev, fill=0)
+    kind = _buf(max(n_sel, 0), torch.uint8, dev, fill=0)
     if n_sel <= 0:
-        return torch.empty(0, dtype=torch.uint8, device=dev), out_off, kind
+        return _buf(0, torch.uint8, dev), out_off, kind
     lens = (cuts[1:] - cuts[:-1]) if chunk_ids is None else (cuts[chunk_ids + 1] - cuts[chunk_ids])
     # per-chunk record of the C-ABI workspace = hmse_l1_deflate_record_bytes[_dict](len), evaluated on the device;
     # tests/test_abi.py holds the formulas together
     rec = record_bytes(lens, None if base is None else base >= 0)
     raw, need = (int(v) for v in torch.stack([lens.sum(), rec.sum()]).tolist())
     cap = raw + 5 * n_sel + 64  # a stored block is the worst case
-    out = torch.empty(cap, dtype=torch.uint8, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = _buf(cap, torch.uint8, dev)
+    status = _buf(1, torch.int32, dev, fill=0)
     c = cfg.to_c()
     limit = deflate_ws_limit(dev) if ws_limit is None else int(ws_limit)
     if need <= limit:
@@ -272,6 +283,7 @@ def l1_deflate(data: torch.Tensor, cuts: torch.Tensor, cfg: IngestConfig, chunk_
         ids_all = chunk_ids if chunk_ids is not None else torch.arange(n_sel, dtype=torch.int64, device=dev)
         base_all = None if base is None else (base if base_is_chunk_id else torch.where(base >= 0, ids_all[base.clamp(min=0)], base))
         by_id = True
+        out_off[:1] = 0     # (the pieces' offsets are copied behind it: the one element no call writes)
     total = 0
     for a, e, need_p in pieces:
         n_p = e - a
@@ -281,7 +293,7 @@ def l1_deflate(data: torch.Tensor, cuts: torch.Tensor, cfg: IngestConfig, chunk_
             ws = _ws(nb + need_p + 4096, dev)
         ids_p = None if ids_all is None else ids_all[a:e]
         base_p = None if base_all is None else base_all[a:e]
-        off_p = out_off[a: e + 1] if len(pieces) == 1 else torch.zeros(n_p + 1, dtype=torch.int64, device=dev)
+        off_p = out_off[a: e + 1] if len(pieces) == 1 else _buf(n_p + 1, torch.int64, dev, fill=0)
         rc = _lib.hip_lib().hmse_l1_deflate_ex(_ptr(data), data.numel(), _ptr(cuts), _ptr(ids_p), _ptr(base_p), n_p, C.byref(c),
                                                1 if by_id else 0, out.data_ptr() + total, cap - total, _ptr(off_p), _ptr(kind[a:e]), _ptr(status),
                                                ws.data_ptr(), ws.numel(), _stream())
@@ -315,12 +327,13 @@ def l1_inflate(streams: torch.Tensor, stream_off: torch.Tensor, kind: torch.Tens
     n_sel = kind.numel()
     if stream_off.numel() != (n_sel if stream_len is not None else n_sel + 1) or raw_len.numel() != n_sel:
         raise HmseError(-1, "l1_inflate: stream_off / raw_len do not match kind")
-    raw_off = torch.zeros(n_sel + 1, dtype=torch.int64, device=dev)
+    raw_off = _buf(n_sel + 1, torch.int64, dev)
+    raw_off[:1] = 0        # (an input of the call, built here: exclusive sums of raw_len)
     torch.cumsum(raw_len, 0, out=raw_off[1:])
     total = int(raw_off[-1].item()) if n_sel else 0
-    raw = torch.empty(total, dtype=torch.uint8, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    ok = torch.zeros(n_sel, dtype=torch.uint8, device=dev)
+    raw = _buf(total, torch.uint8, dev)
+    status = _buf(1, torch.int32, dev, fill=0)
+    ok = _buf(n_sel, torch.uint8, dev, fill=0)
     if n_sel == 0:
         return raw, raw_off, ok
     if base is not None:
@@ -328,7 +341,7 @@ def l1_inflate(streams: torch.Tensor, stream_off: torch.Tensor, kind: torch.Tens
     if stream_len is not None:
         _require_gpu(stream_len, "stream_len")
     ws = _ws(workspace_bytes(STAGE_INFLATE, n_sel, IngestConfig()), dev)
-    keep = torch.empty(1, dtype=torch.uint8, device=dev) if total == 0 else raw  # a valid pointer even when every chunk is empty
+    keep = _buf(1, torch.uint8, dev) if total == 0 else raw  # a valid pointer even when every chunk is empty
     rc = _lib.hip_lib().hmse_l1_inflate(_ptr(streams), streams.numel(), _ptr(stream_off), _ptr(stream_len), _ptr(kind), _ptr(base),
                                         n_sel, _ptr(raw_off), _ptr(keep), total, _ptr(ok), _ptr(status), ws.data_ptr(), ws.numel(), _stream())
     _check(rc, "hmse_l1_inflate")
@@ -344,8 +357,8 @@ def read_assemble(cuts: torch.Tensor, slot_of_chunk: torch.Tensor, raw_off: torc
         _require_gpu(t, nm)
     n_chunks = cuts.numel() - 1
     n = int(cuts[-1].item()) if n_chunks > 0 else 0
-    out = torch.empty(n, dtype=torch.uint8, device=cuts.device)
-    status = torch.zeros(1, dtype=torch.int32, device=cuts.device)
+    out = _buf(n, torch.uint8, cuts.device)
+    status = _buf(1, torch.int32, cuts.device, fill=0)
     if n_chunks <= 0 or n == 0:
         return out
     rc = _lib.hip_lib().hmse_read_assemble(_ptr(cuts), n_chunks, _ptr(slot_of_chunk), raw_off.numel() - 1, _ptr(raw_off), _ptr(raw),
@@ -365,9 +378,9 @@ def manifest_pack(res, shard: int, n_shards: int, shard_bases, rec_off: torch.Te
         _require_gpu(t, nm)
     dev = res.cuts.device
     n = res.cuts.numel() - 1
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = _buf(1, torch.int32, dev, fill=0)
     ws = _ws(workspace_bytes(STAGE_MANIFEST, n, IngestConfig()), dev)
-    base = res.base if res.base is not None else torch.full((res.uniq_ids.numel(),), -1, dtype=torch.int64, device=dev)
+    base = res.base if res.base is not None else torch.full((res.uniq_ids.numel(),), -1, dtype=torch.int64, device=dev)   # (an input, built here)
     if res.base_global is not None:   # dictionaries stored on other shards: -2 (an unresolved DeltaChunk header)
         base = torch.where((res.base_global >= 0) & (base < 0), torch.full_like(base, -2), base)
     sb = None
@@ -375,7 +388,7 @@ def manifest_pack(res, shard: int, n_shards: int, shard_bases, rec_off: torch.Te
         sb = torch.as_tensor(list(shard_bases), dtype=torch.int64, device=dev)
         if sb.numel() != n_shards:
             raise HmseError(-1, "manifest_pack: one chunk base per shard")
-    keep = blob if blob.numel() else torch.empty(1, dtype=torch.uint8, device=dev)
+    keep = blob if blob.numel() else _buf(1, torch.uint8, dev)
     rc = _lib.hip_lib().hmse_manifest_pack_ex(_ptr(res.streams), _ptr(res.stream_off), _ptr(res.kind), _ptr(base), _ptr(res.uniq_ids),
                                           res.uniq_ids.numel(), _ptr(res.digests), _ptr(res.refcount), _ptr(res.cuts), n, _ptr(res.first_occ),
                                           int(res.chunk_base), shard, _ptr(sb), n_shards, 1 if any_target else 0, _ptr(rec_off), lba_unit, _ptr(ptr_index), _ptr(keep),
@@ -399,9 +412,9 @@ def gc_plan(cuts: torch.Tensor, slot: torch.Tensor, n_slots: int, seg_off: torch
     n_seg = seg_off.numel() - 1
     if slot.numel() != n or drop.numel() != n_seg or digests_old.shape != (n_slots, 32) or n_seg < 1:
         raise HmseError(-1, "gc_plan: slot / drop / digests_old do not match cuts / seg_off / n_slots")
-    counts = torch.zeros(2, dtype=torch.int64, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
-    e = lambda *shape, dt=torch.int64: torch.empty(shape, dtype=dt, device=dev)
+    counts = _buf(2, torch.int64, dev, fill=0)
+    status = _buf(1, torch.int32, dev, fill=0)
+    e = lambda *shape, dt=torch.int64: _buf(shape, dt, dev)
     old_chunk, first_occ, refcount, digests = e(max(n, 1)), e(max(n, 1)), e(max(n, 1), dt=torch.int32), e(max(n, 1), 32, dt=torch.uint8)
     uniq_ids, old_slot, new_slot_of_old = e(max(n_slots, 1)), e(max(n_slots, 1)), e(max(n_slots, 1))
     ws = _ws(workspace_bytes(STAGE_GC_PLAN, n, IngestConfig()), dev)
@@ -435,9 +448,9 @@ def record_gather(src0: torch.Tensor, src1: torch.Tensor | None, src_off: torch.
     if src_off.numel() != n or dst_off.numel() != n + 1:
         raise HmseError(-1, "record_gather: src_off / src_sel / dst_off do not match")
     if out is None:
-        out = torch.empty(int(dst_off[-1].item()), dtype=torch.uint8, device=dev)
+        out = _buf(int(dst_off[-1].item()), torch.uint8, dev)
     _require_gpu(out, "out")
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    status = _buf(1, torch.int32, dev, fill=0)
     keep = lambda t: t if t is not None and t.numel() else None
     rc = _lib.hip_lib().hmse_record_gather(_ptr(keep(src0)), src0.numel(), _ptr(keep(src1)), 0 if src1 is None else src1.numel(), _ptr(src_off),
                                            _ptr(src_sel), _ptr(dst_off), n, _ptr(out) if out.numel() else None, out.numel(), _ptr(status), _stream())
@@ -455,7 +468,7 @@ def stream_batch_workspace_bytes(batch_bytes: int, cfg: IngestConfig) -> int:
 def stream_workspace(batch_bytes: int, cfg: IngestConfig, device) -> torch.Tensor:
     """A workspace for hmse_stream_batch / hmse_stream_piece_*: allocated and prepared once (hmse_stream_workspace_init: the MinHash
     memo table inside persists across the stream's batches), then passed to every batch."""
-    ws = torch.empty(stream_batch_workspace_bytes(batch_bytes, cfg), dtype=torch.uint8, device=device)
+    ws = _ws(stream_batch_workspace_bytes(batch_bytes, cfg), device)
     c = cfg.to_c()
     _check(_lib.hip_lib().hmse_stream_workspace_init(ws.data_ptr(), ws.numel(), int(batch_bytes), C.byref(c), _stream()), "hmse_stream_workspace_init")
     return ws
@@ -592,8 +605,8 @@ def band_tables_write(keys: torch.Tensor, sig: torch.Tensor | None, band_bits: i
     dev = keys.device
     lib = _lib.hip_lib()
     cap = int(lib.hmse_band_tables_bound(n, bands, band_bits, nh))
-    out = torch.empty(cap, dtype=torch.uint8, device=dev)
-    meta = torch.zeros(2, dtype=torch.int64, device=dev)      # [out_bytes, status]
+    out = _buf(cap, torch.uint8, dev)
+    meta = _buf(2, torch.int64, dev, fill=0)      # [out_bytes, status]
     ws = _ws(lib.hmse_band_tables_workspace_bytes(n), dev)
     rc = lib.hmse_band_tables_write(_ptr(keys) if n else None, n, bands, band_bits, _ptr(sig) if n and nh else None, nh, out.data_ptr(), cap,
                                     meta.data_ptr(), meta.data_ptr() + 8, ws.data_ptr(), ws.numel(), _stream())
@@ -625,9 +638,9 @@ def l4_index_build(keys: torch.Tensor):
         raise HmseError(-1, "l4_index_build: keys must be int32 [n, bands]")
     n, bands = keys.shape
     dev = keys.device
-    sk = torch.empty((bands, n), dtype=torch.int32, device=dev)
-    si = torch.empty((bands, n), dtype=torch.int32, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    sk = _buf((bands, n), torch.int32, dev)
+    si = _buf((bands, n), torch.int32, dev)
+    status = _buf(1, torch.int32, dev, fill=0)
     ws = _ws(workspace_bytes(STAGE_L4_INDEX, n, search_cfg(IngestConfig(), bands)) if bands in (1, 2, 4, 8, 16) else 256, dev)
     rc = _lib.hip_lib().hmse_l4_index_build(_ptr(keys) if n else None, n, bands, sk.data_ptr() if n else None, si.data_ptr() if n else None,
                                             status.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
@@ -646,11 +659,11 @@ def l4_query(sig_q: torch.Tensor, keys_q: torch.Tensor, sig_s: torch.Tensor, sor
             sorted_keys.shape != (cfg.bands, n_s) or sorted_ids.shape != (cfg.bands, n_s):
         raise HmseError(-1, "l4_query: shapes of the signatures, keys and index do not agree with each other or with the banding")
     dev = sig_q.device
-    ids = torch.empty((n_q, int(top_k)), dtype=torch.int64, device=dev)
-    scores = torch.empty((n_q, int(top_k)), dtype=torch.int32, device=dev)
-    n_hits = torch.empty(n_q, dtype=torch.int32, device=dev)
-    n_cand = torch.empty(n_q, dtype=torch.int64, device=dev)
-    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ids = _buf((n_q, int(top_k)), torch.int64, dev)
+    scores = _buf((n_q, int(top_k)), torch.int32, dev)
+    n_hits = _buf(n_q, torch.int32, dev)
+    n_cand = _buf(n_q, torch.int64, dev)
+    status = _buf(1, torch.int32, dev, fill=0)
     c = cfg.to_c()
     ws = _ws(workspace_bytes(STAGE_L4_QUERY, n_q, cfg), dev)
     q = lambda t: _ptr(t) if n_q else None
@@ -680,9 +693,9 @@ def scrub_records(blob: torch.Tensor, rec_shard: torch.Tensor, shard_blob: torch
     if any(t.numel() != n for t in (rec_shard, rec_len, kind, remote, sorted_lba, sorted_slot, meta)) or shard_blob.numel() != n_shards + 1 \
             or shard_slot.numel() != n_shards + 1:
         raise HmseError(-1, "scrub_records: per-record / per-shard arrays do not match")
-    status = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
-    dict_ = torch.full((max(n, 1),), -1, dtype=torch.int64, device=dev)
-    pad = torch.zeros(1, dtype=torch.int64, device=dev)
+    status = _buf(max(n, 1), torch.uint8, dev, fill=0)
+    dict_ = _buf(max(n, 1), torch.int64, dev, fill=-1)
+    pad = _buf(1, torch.int64, dev, fill=0)
     if n_shards == 0:
         return status[:0], dict_[:0], pad
     p = lambda t: _ptr(t) if t.numel() else None
@@ -703,7 +716,7 @@ def scrub_attribute(status: torch.Tensor, dict_: torch.Tensor, ok: torch.Tensor,
     n, nc = status.numel(), chunk_slot.numel()
     if dict_.numel() != n or ok.numel() != n or cuts.numel() != nc + 1 or (check_digest and (got.shape != (n, 32) or want.shape != (n, 32))):
         raise HmseError(-1, "scrub_attribute: per-record / per-chunk arrays do not match")
-    e = lambda k, dt=torch.int64: torch.zeros(max(k, 1), dtype=dt, device=dev)
+    e = lambda k, dt=torch.int64: _buf(max(k, 1), dt, dev, fill=0)
     out = {"status": e(n, torch.uint8), "root": e(n), "chunk_root": e(nc), "root_records": e(n), "root_chunks": e(n), "root_bytes": e(n),
            "ranges": e(2 * (nc // 2 + 1)), "counts": e(8)}
     ws = _ws(workspace_bytes(STAGE_SCRUB_ATTRIBUTE, max(n, nc), IngestConfig()), dev)

@@ -15,6 +15,22 @@
  *     (n_cuts, overflow flags, stream lengths) are written to DEVICE memory;
  *   - one stream = one engine thread (README.md:148-153, "Core 1 HMSE engine").
  *   - integer/byte results are bit-exact against oracle/ (tests/).
+ *
+ * Memory (all entry points; pinned by tests/test_gpu_arguments_only.py):
+ *   - a byte-typed pointer (const uint8_t* / uint8_t* / void* records: data, streams, out, raw_out, blob, digests, kind, ok, ...)
+ *     may have ANY alignment; a typed pointer (u32 / u64 / i64 arrays) needs the natural alignment of its element, no more;
+ *   - a workspace (`ws`) is 256-byte aligned: an entry point given another one returns HMSE_EINVAL before it clears or launches
+ *     anything;
+ *   - what a workspace or an output holds before the call never matters — the library clears what it needs cleared and writes
+ *     every element the call declares valid (statuses, counts, and per-element outputs such as kind[], ok[], out_off[] in full):
+ *     NO argument has to be cleared by the caller.  An output sized for a worst case is written up to the count the call returns
+ *     and left as it was behind it (cuts beyond n_cuts, out beyond out_off[n_sel], the hmse_gc_plan arrays beyond counts[],
+ *     ranges of hmse_scrub_attribute beyond counts[0] pairs): read the count, not the rest.  The two exceptions are state the
+ *     caller carries from call to call and says so: the workspace of a stream between hmse_stream_workspace_init and its batches, and the persistent tables of hmse_l3_index_update / hmse_l4_lsh_update
+ *     (cleared by the call with n_old == 0), with the arrays and the state block they index (of a stream's arrays the first
+ *     batch reads cuts_all[0] and stream_off_all[0], the start of the first chunk and of the first record: 0);
+ *   - nothing outside [p, p + declared size) is read with effect or written: the bytes behind n / streams_bytes / blob_bytes
+ *     and around every output may be anything and are left as they are.
  */
 #ifndef HMSE_H
 #define HMSE_H
