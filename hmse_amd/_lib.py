@@ -33,6 +33,16 @@ class HmseGl4(C.Structure):
                 ("ug", C.c_void_p), ("base_global", C.c_void_p), ("req_counts", C.c_void_p), ("req_slots", C.c_void_p), ("ghost_chunk0", C.c_uint64)]
 
 
+class HmseStream(C.Structure):
+    """Mirror of `hmse_stream` (include/hmse.h): what is fixed for a stream's life — its persistent arrays (device pointers) and capacities."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("world", C.c_uint32), ("rank", C.c_uint32), ("reserved", C.c_uint32),
+                ("state", C.c_void_p), ("cuts", C.c_void_p), ("max_chunks", C.c_uint64), ("gidx", C.c_void_p), ("digests", C.c_void_p), ("max_chunks_g", C.c_uint64),
+                ("first_occ", C.c_void_p), ("refcount", C.c_void_p), ("l3_table", C.c_void_p), ("l3_slots", C.c_uint64), ("uniq", C.c_void_p), ("max_unique", C.c_uint64),
+                ("sig", C.c_void_p), ("band_keys", C.c_void_p), ("base", C.c_void_p), ("lsh_tables", C.c_void_p), ("lsh_slots", C.c_uint64),
+                ("kind", C.c_void_p), ("stream_off", C.c_void_p), ("out", C.c_void_p), ("out_cap", C.c_uint64)]
+
+
 def build(force: bool = False) -> None:
     """Compile every HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     args = ["make", "-C", _CSRC, "-s", "-j8"]
@@ -60,7 +70,7 @@ def hip_lib():
         # two runtimes and every launch fails with a HIP error.
         import torch  # noqa: F401
         L = C.CDLL(HIP_LIB_PATH)
-        cfgp = C.POINTER(HmseCfg)
+        cfgp, strp = C.POINTER(HmseCfg), C.POINTER(HmseStream)
         L.hmse_cfg_default.argtypes = [cfgp]
         L.hmse_cfg_validate.argtypes = [cfgp]
         L.hmse_cfg_validate.restype = C.c_int
@@ -107,26 +117,23 @@ def hip_lib():
         L.hmse_stream_workspace_init.restype = C.c_int
         L.hmse_stream_workspace_init.argtypes = [_VP, _SZ, _U64, cfgp, _VP]
         L.hmse_stream_batch.restype = C.c_int
-        L.hmse_stream_batch.argtypes = [_VP, _U64, _U64, _VP, _U32, cfgp, _VP, _VP, _U64, _VP, _VP, _VP, _VP, _U64, _VP, _U64, _VP, _VP, _VP, _VP,
-                                        _U64, _VP, _VP, _VP, _U64, _VP, _SZ, _VP]
+        L.hmse_stream_batch.argtypes = [_VP, _U64, _U64, _VP, _U32, cfgp, strp, _VP, _SZ, _VP]
         L.hmse_stream_row_bytes.restype = _U64
         L.hmse_stream_row_bytes.argtypes = [_U64, cfgp]
         L.hmse_stream_piece_hash.restype = C.c_int
-        L.hmse_stream_piece_hash.argtypes = [_VP, _U64, _U64, _U64, _VP, _U32, cfgp, _VP, _VP, _U64, _VP, _VP, _SZ, _VP]
+        L.hmse_stream_piece_hash.argtypes = [_VP, _U64, _U64, _U64, _VP, _U32, cfgp, strp, _VP, _VP, _SZ, _VP]
         L.hmse_stream_piece_encode.restype = C.c_int
-        L.hmse_stream_piece_encode.argtypes = [_VP, _U64, _U64, _U64, cfgp, _VP, _VP, _U32, _U32, _VP, _VP, _VP, _U64, _VP, _VP, _VP, _U64, _VP, _U64,
-                                               _VP, _VP, _VP, _VP, _U64, _VP, _VP, _VP, _U64, _VP, _SZ, _VP]
+        L.hmse_stream_piece_encode.argtypes = [_VP, _U64, _U64, _U64, cfgp, strp, _VP, _VP, _SZ, _VP]
         L.hmse_stream_sig_cap.restype = _U64
         L.hmse_stream_sig_cap.argtypes = [_U64, cfgp]
         L.hmse_stream_sig_row_bytes.restype = _U64
         L.hmse_stream_sig_row_bytes.argtypes = [_U64, cfgp]
         L.hmse_stream_piece_sign.restype = C.c_int
-        L.hmse_stream_piece_sign.argtypes = [_VP, _U64, _U64, _U64, cfgp, _VP, _VP, _U32, _U32, _VP, _VP, _VP, _U64, _VP, _VP, _VP, _U64, _VP, _U64,
-                                             _VP, _VP, _VP, _SZ, _VP]
+        L.hmse_stream_piece_sign.argtypes = [_VP, _U64, _U64, _U64, cfgp, strp, _VP, _VP, _VP, _SZ, _VP]
         L.hmse_stream_piece_bases.restype = C.c_int
-        L.hmse_stream_piece_bases.argtypes = [_U64, cfgp, _VP, _VP, C.POINTER(HmseGl4), _VP, _VP, _VP, _VP, _SZ, _VP]
+        L.hmse_stream_piece_bases.argtypes = [_U64, cfgp, strp, _VP, C.POINTER(HmseGl4), _VP, _SZ, _VP]
         L.hmse_stream_piece_encode_g.restype = C.c_int
-        L.hmse_stream_piece_encode_g.argtypes = [_VP, _U64, _U64, _U64, cfgp, _VP, _VP, _VP, _VP, _VP, _VP, _U64, _VP, _SZ, _VP]
+        L.hmse_stream_piece_encode_g.argtypes = [_VP, _U64, _U64, _U64, cfgp, strp, _VP, _VP, _SZ, _VP]
         L.hmse_manifest_pack.restype = C.c_int
         L.hmse_manifest_pack.argtypes = [_VP, _VP, _VP, _VP, _VP, _U64, _VP, _VP, _VP, _U64, _VP, _U64, _U32, _VP, _U32, _VP, _U32, _VP,
                                          _VP, _U64, _VP, _VP, _VP, _U64, _VP, _VP, _SZ, _VP]

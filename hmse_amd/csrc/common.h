@@ -126,23 +126,11 @@ int hmse_cfg_validate_impl(const hmse_cfg* cfg);
 void hmse_cdc_masks_hi(const hmse_cfg* cfg, uint32_t* ms_hi, uint32_t* ml_hi);
 uint32_t hmse_deflate_depth(const hmse_cfg* cfg);
 
-// ---- device-side state of the captured per-batch chain (hmse_stream_batch, stream_batch.hip) ---------------------
-// u64 words in HBM, read by every stage instead of host-side counts, so that the whole chain of one batch can be
-// enqueued (and captured into a hipGraph) without a single host read.
+// ---- device-side state of the captured per-batch chain: the words of include/hmse.h (HMSE_SB_*) under the kernels' short names ----
 enum {
-  SB_OFF = 0,        // byte offset of this batch in the resident corpus (= bytes ingested before it)
-  SB_N_OLD = 1,      // chunks before this batch
-  SB_N_NEW = 2,      // chunks of this batch            (written by the chain)
-  SB_U_OLD = 3,      // stored chunks before this batch
-  SB_U_NEW = 4,      // stored chunks of this batch     (written by the chain)
-  SB_S_OLD = 5,      // stream bytes before this batch
-  SB_S_NEW = 6,      // stream bytes of this batch      (written by the chain)
-  SB_STATUS = 7,     // sticky error bits: once non-zero every later batch of the stream is a no-op
-  // multi-rank streaming (global chunk order = batch, rank, local index); with one rank these mirror SB_N_OLD / SB_N_NEW
-  SB_G_OLD = 8,      // chunks of ALL ranks before this batch
-  SB_G_NEW = 9,      // chunks of all ranks in this batch   (written by the chain)
-  SB_G_BASE = 10,    // global index of this rank's first chunk of this batch (written by the chain)
-  SB_WORDS = 16
+  SB_OFF = HMSE_SB_OFF, SB_N_OLD = HMSE_SB_N_OLD, SB_N_NEW = HMSE_SB_N_NEW, SB_U_OLD = HMSE_SB_U_OLD, SB_U_NEW = HMSE_SB_U_NEW,
+  SB_S_OLD = HMSE_SB_S_OLD, SB_S_NEW = HMSE_SB_S_NEW, SB_STATUS = HMSE_SB_STATUS, SB_G_OLD = HMSE_SB_G_OLD, SB_G_NEW = HMSE_SB_G_NEW,
+  SB_G_BASE = HMSE_SB_G_BASE, SB_WORDS = HMSE_SB_WORDS
 };
 int hmse_l2_cdc_impl(const uint8_t* data, const uint64_t* data_off_dev, uint64_t n, const uint64_t* seg_off, uint32_t n_seg,
                      const hmse_cfg* cfg, uint64_t* cuts, uint64_t cuts_cap, uint64_t* n_cuts, uint32_t* status, void* ws,

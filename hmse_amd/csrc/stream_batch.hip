@@ -2,7 +2,7 @@
 // "4 x 10 GB streamed, 8 x MI355X, hipGraph-captured per-batch pipeline"; the reference's batch loop README.md:1519-1580).
 //
 // hmse_amd/stream.py's eager path reads device counts on the host between stages (chunk count, stored-chunk count, stream
-// bytes) to size the next launch.  Here every stage takes its ranges from a small state block in HBM (common.h, SB_*), grids
+// bytes) to size the next launch.  Here every stage takes its ranges from a small state block in HBM (include/hmse.h, HMSE_SB_*; SB_* here), grids
 // and workspaces are sized for the worst case of the batch (bytes / min_size chunks), and the chain ends by advancing the
 // state itself — so the sequence L2 -> L3 hash | digest exchange | L3 persistent index -> stored-chunk selection -> L4
 // (MinHash + persistent band tables) -> L1 (dictionary DEFLATE) -> index tails can be captured into hipGraphs once and
@@ -33,8 +33,8 @@ __global__ __launch_bounds__(256) void append_cuts_kernel(const uint64_t* __rest
   uint64_t n_new = n_cuts ? *n_cuts : 0ull;
   uint64_t err = 0;
   if (st[SB_STATUS]) n_new = 0;                                      // an earlier batch failed: this one is a no-op
-  else if (l2_status && *l2_status) { err = 4ull; n_new = 0; }       // the cut list is not trustworthy: drop the batch
-  else if (n_new > cap || n_old + n_new > max_chunks) { err = 1ull; n_new = 0; }   // capacity: dropped and flagged, nothing out of bounds
+  else if (l2_status && *l2_status) { err = HMSE_STREAM_ST_L2; n_new = 0; }       // the cut list is not trustworthy: drop the batch
+  else if (n_new > cap || n_old + n_new > max_chunks) { err = HMSE_STREAM_ST_CHUNK_CAP; n_new = 0; }   // capacity: dropped and flagged, nothing out of bounds
   for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < n_new; j += (uint64_t)gridDim.x * 256) cuts_all[n_old + 1 + j] = local[j + 1] + off;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     st[SB_N_NEW] = n_new;
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void ingest_rows_kernel(const uint8_t* __restr
   }
   const bool over = g_old + total > max_chunks_g;
   // one rank: the global chunk order IS the local one, so the two counters must agree (a caller resuming a stream with the
-  // ABI-1 state layout has state[8] = 0 and would overwrite digests from index 0 on) — refused with sticky status bit 5
+  // ABI-1 state layout has state[8] = 0 and would overwrite digests from index 0 on) — refused with the sticky HMSE_STREAM_ST_STATE
   const bool stale = world == 1 && g_old != st[SB_N_OLD];
   if (dead || bad || over || stale) total = 0;
   if (r < world && total && j < cnt_r) {
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void ingest_rows_kernel(const uint8_t* __restr
   if (tid == 0) {
     st[SB_G_NEW] = total;
     st[SB_G_BASE] = g_old + mine_before;
-    if (!dead && (bad || over || stale)) { st[SB_STATUS] |= stale ? 32ull : bad ? 8ull : 1ull; st[SB_N_NEW] = 0; }
+    if (!dead && (bad || over || stale)) { st[SB_STATUS] |= stale ? HMSE_STREAM_ST_STATE : bad ? HMSE_STREAM_ST_ROW : HMSE_STREAM_ST_CHUNK_CAP; st[SB_N_NEW] = 0; }
   }
 }
 
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(1024) void select_uniq_kernel(const uint64_t* __res
   }
   if (threadIdx.x == 0) {
     uint64_t nu = run;
-    if (u_old + nu > max_unique) { nu = 0; st[SB_STATUS] |= 2ull; }
+    if (u_old + nu > max_unique) { nu = 0; st[SB_STATUS] |= HMSE_STREAM_ST_STORED_CAP; }
     st[SB_U_NEW] = nu;
   }
 }
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256) void commit_kernel(const uint8_t* __restrict__
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     st[SB_S_NEW] = total;
-    if (*dfl_status) st[SB_STATUS] |= (uint64_t)*dfl_status << 8;
+    if (*dfl_status) st[SB_STATUS] |= (uint64_t)*dfl_status << HMSE_STREAM_ST_DEFLATE_SHIFT;
   }
 }
 // the state moves on to the next batch — unless this one (or an earlier one) failed: then the counters stay where the last
@@ -162,7 +162,7 @@ constexpr uint32_t SIG_HDR = 32;
 constexpr uint32_t SIG_BYTES = 512;   // 128 x u32 (the device path is specialised to n_hashes = 128)
 
 // this rank's new signatures (sig_all[u_old .. u_old + u_new)) -> its exchange row; a batch with more new stored chunks than a row holds
-// is dropped with status bit 7 (a defence: the row is sized for the worst-case chunk count of a piece, sb_sig_cap)
+// is dropped with HMSE_STREAM_ST_SIG_ROW (a defence: the row is sized for the worst-case chunk count of a piece, sb_sig_cap)
 __global__ __launch_bounds__(256) void sig_row_kernel(const uint32_t* __restrict__ sig_all, uint64_t* st, uint64_t sig_cap, uint8_t* __restrict__ row) {
   const uint64_t u_old = st[SB_U_OLD];
   uint64_t u_new = st[SB_U_NEW];
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void sig_row_kernel(const uint32_t* __restrict
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < u_new * (SIG_BYTES / 16); i += (uint64_t)gridDim.x * 256) dst[i] = src[i];
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     ((uint64_t*)row)[0] = u_new; ((uint64_t*)row)[1] = u_old;
-    if (over && !st[SB_STATUS]) { st[SB_STATUS] |= 128ull; st[SB_U_NEW] = 0; st[SB_N_NEW] = 0; }
+    if (over && !st[SB_STATUS]) { st[SB_STATUS] |= HMSE_STREAM_ST_SIG_ROW; st[SB_U_NEW] = 0; st[SB_N_NEW] = 0; }
   }
 }
 
@@ -208,13 +208,12 @@ __global__ __launch_bounds__(256) void ingest_sig_rows_kernel(const uint8_t* __r
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     gst[SB_U_NEW] = total;
     gst[SB_G_BASE] = ug_old + mine_before;
-    if (!dead && (bad || over)) { st[SB_STATUS] |= bad ? 8ull : 2ull; st[SB_U_NEW] = 0; st[SB_N_NEW] = 0; }
+    if (!dead && (bad || over)) { st[SB_STATUS] |= bad ? HMSE_STREAM_ST_ROW : HMSE_STREAM_ST_STORED_CAP; st[SB_U_NEW] = 0; st[SB_N_NEW] = 0; }
   }
 }
 
 // dictionary of every new stored chunk of this rank: own -> its chunk id; remote -> ghost chunk ghost0 + j and request j = (owner, slot),
-// requests grouped by owner (counts[q], counts[world] = total; counts[world + 1] = this rank's stored chunks INCLUDING this batch's: the
-// bound of the slots a peer may ask of it in this batch's fetch).  One workgroup.
+// requests grouped by owner (counts[q]; behind them HMSE_GL4_REQ_TOTAL and HMSE_GL4_REQ_STORED, include/hmse.h).  One workgroup.
 __global__ __launch_bounds__(1024) void resolve_bases_kernel(const int64_t* __restrict__ base_g, const uint32_t* __restrict__ keys_g, uint32_t bands,
                                                               const uint32_t* __restrict__ g_owner, const uint64_t* __restrict__ g_local,
                                                               const uint64_t* __restrict__ uniq_all, uint32_t world, uint32_t rank, uint64_t ghost0,
@@ -233,7 +232,7 @@ __global__ __launch_bounds__(1024) void resolve_bases_kernel(const int64_t* __re
     if (bg >= 0 && g_owner[bg] != rank) atomicAdd(&cnt[g_owner[bg]], 1u);
   }
   __syncthreads();
-  if (t == 0) { uint32_t run = 0; for (uint32_t q = 0; q < world; q++) { const uint32_t c = cnt[q]; req_counts[q] = c; cur[q] = run; run += c; } req_counts[world] = run; req_counts[world + 1] = u_old + nu; *n_sel = nu; }
+  if (t == 0) { uint32_t run = 0; for (uint32_t q = 0; q < world; q++) { const uint32_t c = cnt[q]; req_counts[q] = c; cur[q] = run; run += c; } req_counts[world + HMSE_GL4_REQ_TOTAL] = run; req_counts[world + HMSE_GL4_REQ_STORED] = u_old + nu; *n_sel = nu; }
   __syncthreads();
   for (uint64_t k = t; k < nu; k += 1024) {
     const uint64_t gi = m0 + k;
@@ -252,7 +251,7 @@ __global__ __launch_bounds__(1024) void resolve_bases_kernel(const int64_t* __re
   }
 }
 
-// phase B3 of a batch whose status word is set — possibly by the HOST since phase B2 (bit 16: the remote dictionaries did not arrive, so
+// phase B3 of a batch whose status word is set — possibly by the HOST since phase B2 (HMSE_STREAM_ST_HOST_REFUSED: the remote dictionaries did not arrive, so
 // the ghost chunks' bounds are those of an earlier batch) — encodes nothing and commits nothing
 __global__ void drop_failed_kernel(uint64_t* st, uint64_t* n_sel) {
   if (st[SB_STATUS]) { *n_sel = 0; st[SB_U_NEW] = 0; st[SB_N_NEW] = 0; }
@@ -326,55 +325,91 @@ extern "C" uint64_t hmse_stream_row_bytes(uint64_t cap_bytes, const hmse_cfg* cf
   return sb::ROW_HDR + 32 * sb_cap_chunks(cap_bytes, cfg);
 }
 
+// ---- the stream's descriptor (include/hmse.h, hmse_stream): the fields an entry point requires; SF_GIDX only with several ranks ----
+enum : unsigned {
+  SF_STATE = 1u << 0, SF_CUTS = 1u << 1, SF_GIDX = 1u << 2, SF_DIGESTS = 1u << 3, SF_FIRST_OCC = 1u << 4, SF_REFCOUNT = 1u << 5, SF_L3_TABLE = 1u << 6,
+  SF_UNIQ = 1u << 7, SF_SIG = 1u << 8, SF_BAND_KEYS = 1u << 9, SF_BASE = 1u << 10, SF_LSH_TABLES = 1u << 11, SF_KIND = 1u << 12, SF_STREAM_OFF = 1u << 13,
+  SF_OUT = 1u << 14,
+  SF_HASH = SF_STATE | SF_CUTS,
+  SF_SIGN = SF_STATE | SF_CUTS | SF_GIDX | SF_DIGESTS | SF_FIRST_OCC | SF_REFCOUNT | SF_L3_TABLE | SF_UNIQ | SF_SIG,
+  SF_BASES = SF_STATE | SF_UNIQ | SF_BAND_KEYS | SF_BASE,
+  SF_ENCODE_G = SF_STATE | SF_CUTS | SF_KIND | SF_STREAM_OFF | SF_OUT,
+  SF_ENCODE = SF_SIGN | SF_BASES | SF_ENCODE_G | SF_LSH_TABLES   // every field
+};
+
+static bool sb_stream_ok(const hmse_stream* s, unsigned need) {
+  if (!s || s->struct_size != sizeof(hmse_stream) || s->world == 0 || s->world > 256 || s->rank >= s->world) return false;
+  const struct { unsigned field; const void* p; } fields[] = {
+      {SF_STATE, s->state}, {SF_CUTS, s->cuts}, {SF_GIDX, s->world > 1 ? (const void*)s->gidx : (const void*)s}, {SF_DIGESTS, s->digests},
+      {SF_FIRST_OCC, s->first_occ}, {SF_REFCOUNT, s->refcount}, {SF_L3_TABLE, s->l3_table}, {SF_UNIQ, s->uniq}, {SF_SIG, s->sig},
+      {SF_BAND_KEYS, s->band_keys}, {SF_BASE, s->base}, {SF_LSH_TABLES, s->lsh_tables}, {SF_KIND, s->kind}, {SF_STREAM_OFF, s->stream_off},
+      {SF_OUT, s->out}};
+  for (const auto& f : fields)
+    if ((need & f.field) && !f.p) return false;
+  return true;
+}
+
+static uint32_t sb_tail_blocks(uint64_t cap) { const uint64_t b = (cap + 255) / 256; return (uint32_t)(b > 1024 ? 1024 : b); }
+
 // ---- phase A ------------------------------------------------------------------------------------------------------------
 static int piece_hash(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const uint64_t* seg_off, uint32_t n_seg,
-                      const hmse_cfg* cfg, uint64_t* state, uint64_t* cuts_all, uint64_t max_chunks, uint8_t* row, const sb::Ws& w,
-                      hipStream_t stream) {
+                      const hmse_cfg* cfg, const hmse_stream* s, uint8_t* row, const sb::Ws& w, hipStream_t stream) {
   const uint64_t cap = sb_cap_chunks(cap_bytes, cfg);
   if (piece_bytes == 0) {   // this rank has nothing in this batch: N_NEW = 0, an empty row
-    sb::append_cuts_kernel<<<dim3(1), dim3(256), 0, stream>>>(nullptr, nullptr, nullptr, cuts_all, state, max_chunks, cap, row);
+    sb::append_cuts_kernel<<<dim3(1), dim3(256), 0, stream>>>(nullptr, nullptr, nullptr, s->cuts, s->state, s->max_chunks, cap, row);
     HMSE_LAUNCH_CHECK();
     return HMSE_OK;
   }
   int rc;
   // L2 on the piece's bytes (data + state[SB_OFF], read on the device)
-  if ((rc = hmse_l2_cdc_impl(data, state + SB_OFF, piece_bytes, seg_off, n_seg, cfg, w.cuts_local, cap + 1, w.n_cuts, w.l2_status, w.l2_ws,
+  if ((rc = hmse_l2_cdc_impl(data, s->state + SB_OFF, piece_bytes, seg_off, n_seg, cfg, w.cuts_local, cap + 1, w.n_cuts, w.l2_status, w.l2_ws,
                              w.l2_bytes, stream)) != HMSE_OK) return rc;
-  uint32_t ab = (uint32_t)((cap + 255) / 256); if (ab > 1024) ab = 1024;
-  sb::append_cuts_kernel<<<dim3(ab), dim3(256), 0, stream>>>(w.cuts_local, w.n_cuts, w.l2_status, cuts_all, state, max_chunks, cap, row);
+  sb::append_cuts_kernel<<<dim3(sb_tail_blocks(cap)), dim3(256), 0, stream>>>(w.cuts_local, w.n_cuts, w.l2_status, s->cuts, s->state, s->max_chunks, cap, row);
   // L3: digests of the new chunks go into the exchange row
-  if ((rc = hmse_l3_sha256_dyn(data, data_cap, cuts_all, nullptr, row + sb::ROW_HDR, state, cap, w.sha_ws, w.sha_bytes, stream)) != HMSE_OK) return rc;
+  if ((rc = hmse_l3_sha256_dyn(data, data_cap, s->cuts, nullptr, row + sb::ROW_HDR, s->state, cap, w.sha_ws, w.sha_bytes, stream)) != HMSE_OK) return rc;
   HMSE_LAUNCH_CHECK();
   return HMSE_OK;
 }
 
 // ---- phase B ------------------------------------------------------------------------------------------------------------
-static int piece_encode(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const hmse_cfg* cfg, uint64_t* state,
-                        const uint8_t* rows, uint32_t world, uint32_t rank, const uint64_t* cuts_all, uint64_t* gidx, uint8_t* digests_g,
-                        uint64_t max_chunks_g, uint64_t* first_occ_g, uint32_t* refcount_g, uint32_t* l3_table, uint64_t l3_slots,
-                        uint64_t* uniq_all, uint64_t max_unique, uint32_t* sig_all, uint32_t* band_keys, int64_t* base_all, uint32_t* lsh_tables,
-                        uint64_t lsh_slots, uint8_t* kind_all, uint64_t* stream_off_all, uint8_t* out, uint64_t out_cap, const sb::Ws& w,
-                        hipStream_t stream) {
+// first half (hmse_stream_piece_encode, hmse_stream_piece_sign): rows of all ranks -> global index -> this rank's stored chunks -> MinHash
+static int index_and_sign(uint8_t* data, uint64_t data_cap, uint64_t cap_bytes, const hmse_cfg* cfg, const hmse_stream* s, const uint8_t* rows,
+                          const sb::Ws& w, hipStream_t stream) {
   const uint64_t cap = sb_cap_chunks(cap_bytes, cfg);
   const uint64_t row_bytes = sb::ROW_HDR + 32 * cap;
   int rc;
-  const uint64_t gthreads = 2ull * world * cap;
-  sb::ingest_rows_kernel<<<dim3((uint32_t)((gthreads + 255) / 256)), dim3(256), 0, stream>>>(rows, row_bytes, world, rank, cap, digests_g, max_chunks_g,
-                                                                                            gidx, state);
+  const uint64_t gthreads = 2ull * s->world * cap;
+  sb::ingest_rows_kernel<<<dim3((uint32_t)((gthreads + 255) / 256)), dim3(256), 0, stream>>>(rows, row_bytes, s->world, s->rank, cap, s->digests, s->max_chunks_g,
+                                                                                            s->gidx, s->state);
   // persistent L3 index over the global chunk order: every rank inserts the same digests under the same indices
-  if ((rc = hmse_l3_index_update_dyn(digests_g, first_occ_g, refcount_g, l3_table, l3_slots, state + SB_G_OLD, (uint64_t)world * cap, stream)) != HMSE_OK)
-    return rc;
-  sb::select_uniq_kernel<<<dim3(1), dim3(1024), 0, stream>>>(first_occ_g, uniq_all, state, max_unique);
-  // L4: signatures of the new stored chunks, persistent band tables (this rank's stored chunks: a dictionary must be resident)
-  if ((rc = hmse_l4_minhash_dyn(data, data_cap, cuts_all, uniq_all, sig_all, state, cap, cfg, w.mh_ws, w.mh_bytes, stream)) != HMSE_OK) return rc;
-  if ((rc = hmse_l4_lsh_update_dyn(sig_all, band_keys, base_all, lsh_tables, lsh_slots, state, cap, cfg, stream)) != HMSE_OK) return rc;
-  // L1: dictionary DEFLATE of the new stored chunks (a dictionary may be any stored chunk of this rank's stream so far)
-  sb::prep_deflate_kernel<<<dim3((uint32_t)((cap + 255) / 256)), dim3(256), 0, stream>>>(uniq_all, base_all, state, w.sel_ids, w.sel_base, w.n_sel);
-  if ((rc = hmse_l1_deflate_dyn(data, data_cap, cuts_all, w.sel_ids, w.sel_base, w.n_sel, cap, state + SB_S_OLD, cfg, out, out_cap, w.out_off, w.kind,
+  if ((rc = hmse_l3_index_update_dyn(s->digests, s->first_occ, s->refcount, s->l3_table, s->l3_slots, s->state + SB_G_OLD, (uint64_t)s->world * cap,
+                                     stream)) != HMSE_OK) return rc;
+  sb::select_uniq_kernel<<<dim3(1), dim3(1024), 0, stream>>>(s->first_occ, s->uniq, s->state, s->max_unique);
+  return hmse_l4_minhash_dyn(data, data_cap, s->cuts, s->uniq, s->sig, s->state, cap, cfg, w.mh_ws, w.mh_bytes, stream);
+}
+
+// second half (hmse_stream_piece_encode, hmse_stream_piece_encode_g): dictionary DEFLATE of the selection in the workspace -> index tails
+static int deflate_and_commit(uint8_t* data, uint64_t data_cap, uint64_t cap_bytes, const hmse_cfg* cfg, const hmse_stream* s, const sb::Ws& w,
+                              hipStream_t stream) {
+  const uint64_t cap = sb_cap_chunks(cap_bytes, cfg);
+  int rc;
+  if ((rc = hmse_l1_deflate_dyn(data, data_cap, s->cuts, w.sel_ids, w.sel_base, w.n_sel, cap, s->state + SB_S_OLD, cfg, s->out, s->out_cap, w.out_off, w.kind,
                                 w.dfl_status, w.dfl_ws, w.dfl_bytes, stream)) != HMSE_OK) return rc;
-  uint32_t ab = (uint32_t)((cap + 255) / 256); if (ab > 1024) ab = 1024;
-  sb::commit_kernel<<<dim3(ab), dim3(256), 0, stream>>>(w.kind, w.out_off, cap, kind_all, stream_off_all, w.dfl_status, state);
-  sb::advance_kernel<<<dim3(1), dim3(1), 0, stream>>>(state, piece_bytes);
+  sb::commit_kernel<<<dim3(sb_tail_blocks(cap)), dim3(256), 0, stream>>>(w.kind, w.out_off, cap, s->kind, s->stream_off, w.dfl_status, s->state);
+  return HMSE_OK;
+}
+
+static int piece_encode(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const hmse_cfg* cfg, const hmse_stream* s,
+                        const uint8_t* rows, const sb::Ws& w, hipStream_t stream) {
+  const uint64_t cap = sb_cap_chunks(cap_bytes, cfg);
+  int rc;
+  if ((rc = index_and_sign(data, data_cap, cap_bytes, cfg, s, rows, w, stream)) != HMSE_OK) return rc;
+  // persistent band tables (this rank's stored chunks: a dictionary must be resident)
+  if ((rc = hmse_l4_lsh_update_dyn(s->sig, s->band_keys, s->base, s->lsh_tables, s->lsh_slots, s->state, cap, cfg, stream)) != HMSE_OK) return rc;
+  // L1: dictionary DEFLATE of the new stored chunks (a dictionary may be any stored chunk of this rank's stream so far)
+  sb::prep_deflate_kernel<<<dim3((uint32_t)((cap + 255) / 256)), dim3(256), 0, stream>>>(s->uniq, s->base, s->state, w.sel_ids, w.sel_base, w.n_sel);
+  if ((rc = deflate_and_commit(data, data_cap, cap_bytes, cfg, s, w, stream)) != HMSE_OK) return rc;
+  sb::advance_kernel<<<dim3(1), dim3(1), 0, stream>>>(s->state, piece_bytes);
   HMSE_LAUNCH_CHECK();
   return HMSE_OK;
 }
@@ -389,60 +424,43 @@ static bool sb_piece_args_ok(uint64_t piece_bytes, uint64_t cap_bytes, uint32_t 
 }
 
 extern "C" int hmse_stream_piece_hash(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const uint64_t* seg_off,
-                                      uint32_t n_seg, const hmse_cfg* cfg, uint64_t* state, uint64_t* cuts_all, uint64_t max_chunks,
-                                      uint8_t* row, void* ws, size_t ws_bytes, void* stream_) {
+                                      uint32_t n_seg, const hmse_cfg* cfg, const hmse_stream* s, uint8_t* row, void* ws, size_t ws_bytes,
+                                      void* stream_) {
   HMSE_WS_ALIGNED(ws);
   if (!sb_piece_args_ok(piece_bytes, cap_bytes, n_seg, cfg)) return HMSE_EINVAL;
-  if (!data || !state || !cuts_all || !row || (piece_bytes && !seg_off)) return HMSE_EINVAL;
+  if (!data || !sb_stream_ok(s, SF_HASH) || !row || (piece_bytes && !seg_off)) return HMSE_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;
   (void)hipGetLastError();
   const sb::Ws w = sb_carve(ws, cap_bytes, cfg);
   if (!ws || ws_bytes < w.total) return HMSE_ENOSPC;
-  return piece_hash(data, data_cap, piece_bytes, cap_bytes, seg_off, n_seg, cfg, state, cuts_all, max_chunks, row, w, stream);
+  return piece_hash(data, data_cap, piece_bytes, cap_bytes, seg_off, n_seg, cfg, s, row, w, stream);
 }
 
 extern "C" int hmse_stream_piece_encode(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const hmse_cfg* cfg,
-                                        uint64_t* state, const uint8_t* rows, uint32_t world, uint32_t rank, const uint64_t* cuts_all,
-                                        uint64_t* gidx, uint8_t* digests_g, uint64_t max_chunks_g, uint64_t* first_occ_g, uint32_t* refcount_g,
-                                        uint32_t* l3_table, uint64_t l3_slots, uint64_t* uniq_all, uint64_t max_unique, uint32_t* sig_all,
-                                        uint32_t* band_keys, int64_t* base_all, uint32_t* lsh_tables, uint64_t lsh_slots, uint8_t* kind_all,
-                                        uint64_t* stream_off_all, uint8_t* out, uint64_t out_cap, void* ws, size_t ws_bytes, void* stream_) {
+                                        const hmse_stream* s, const uint8_t* rows, void* ws, size_t ws_bytes, void* stream_) {
   HMSE_WS_ALIGNED(ws);
   if (!sb_piece_args_ok(piece_bytes, cap_bytes, piece_bytes ? 1u : 0u, cfg)) return HMSE_EINVAL;
-  if (!data || !state || !rows || !cuts_all || !digests_g || !first_occ_g || !refcount_g || !l3_table || !uniq_all || !sig_all || !band_keys ||
-      !base_all || !lsh_tables || !kind_all || !stream_off_all || !out || world == 0 || world > 256 || rank >= world)
-    return HMSE_EINVAL;
-  if (world > 1 && !gidx) return HMSE_EINVAL;
+  if (!data || !sb_stream_ok(s, SF_ENCODE) || !rows) return HMSE_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;
   (void)hipGetLastError();
   const sb::Ws w = sb_carve(ws, cap_bytes, cfg);
   if (!ws || ws_bytes < w.total) return HMSE_ENOSPC;
-  return piece_encode(data, data_cap, piece_bytes, cap_bytes, cfg, state, rows, world, rank, cuts_all, gidx, digests_g, max_chunks_g, first_occ_g,
-                      refcount_g, l3_table, l3_slots, uniq_all, max_unique, sig_all, band_keys, base_all, lsh_tables, lsh_slots, kind_all,
-                      stream_off_all, out, out_cap, w, stream);
+  return piece_encode(data, data_cap, piece_bytes, cap_bytes, cfg, s, rows, w, stream);
 }
 
 // one rank: both phases back to back, the exchange row (kept in the workspace) is the gathered array
 extern "C" int hmse_stream_batch(uint8_t* data, uint64_t data_cap, uint64_t batch_bytes, const uint64_t* seg_off, uint32_t n_seg,
-                                 const hmse_cfg* cfg, uint64_t* state, uint64_t* cuts_all, uint64_t max_chunks, uint8_t* digests_all,
-                                 uint64_t* first_occ, uint32_t* refcount, uint32_t* l3_table, uint64_t l3_slots, uint64_t* uniq_all,
-                                 uint64_t max_unique, uint32_t* sig_all, uint32_t* band_keys, int64_t* base_all, uint32_t* lsh_tables,
-                                 uint64_t lsh_slots, uint8_t* kind_all, uint64_t* stream_off_all, uint8_t* out, uint64_t out_cap,
-                                 void* ws, size_t ws_bytes, void* stream_) {
+                                 const hmse_cfg* cfg, const hmse_stream* s, void* ws, size_t ws_bytes, void* stream_) {
   HMSE_WS_ALIGNED(ws);
   if (batch_bytes == 0 || !sb_piece_args_ok(batch_bytes, batch_bytes, n_seg, cfg)) return HMSE_EINVAL;
-  if (!data || !seg_off || !state || !cuts_all || !digests_all || !first_occ || !refcount || !l3_table || !uniq_all || !sig_all || !band_keys ||
-      !base_all || !lsh_tables || !kind_all || !stream_off_all || !out)
-    return HMSE_EINVAL;
+  if (!data || !seg_off || !sb_stream_ok(s, SF_ENCODE) || s->world != 1) return HMSE_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;
   (void)hipGetLastError();
   const sb::Ws w = sb_carve(ws, batch_bytes, cfg);
   if (!ws || ws_bytes < w.total) return HMSE_ENOSPC;
-  int rc = piece_hash(data, data_cap, batch_bytes, batch_bytes, seg_off, n_seg, cfg, state, cuts_all, max_chunks, w.row, w, stream);
+  int rc = piece_hash(data, data_cap, batch_bytes, batch_bytes, seg_off, n_seg, cfg, s, w.row, w, stream);
   if (rc != HMSE_OK) return rc;
-  return piece_encode(data, data_cap, batch_bytes, batch_bytes, cfg, state, w.row, 1u, 0u, cuts_all, nullptr, digests_all, max_chunks, first_occ, refcount,
-                      l3_table, l3_slots, uniq_all, max_unique, sig_all, band_keys, base_all, lsh_tables, lsh_slots, kind_all, stream_off_all, out,
-                      out_cap, w, stream);
+  return piece_encode(data, data_cap, batch_bytes, batch_bytes, cfg, s, w.row, w, stream);
 }
 
 
@@ -462,36 +480,27 @@ static bool gl4_ok(const hmse_gl4* g) {
          g->base_g && g->lsh_tables_g && g->g_owner && g->g_local && g->ug && g->base_global && g->req_counts && g->req_slots && g->max_stored_g;
 }
 
-extern "C" int hmse_stream_piece_sign(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const hmse_cfg* cfg, uint64_t* state,
-                                      const uint8_t* rows, uint32_t world, uint32_t rank, const uint64_t* cuts_all, uint64_t* gidx, uint8_t* digests_g,
-                                      uint64_t max_chunks_g, uint64_t* first_occ_g, uint32_t* refcount_g, uint32_t* l3_table, uint64_t l3_slots,
-                                      uint64_t* uniq_all, uint64_t max_unique, uint32_t* sig_all, uint8_t* sig_row, void* ws, size_t ws_bytes, void* stream_) {
+extern "C" int hmse_stream_piece_sign(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const hmse_cfg* cfg, const hmse_stream* s,
+                                      const uint8_t* rows, uint8_t* sig_row, void* ws, size_t ws_bytes, void* stream_) {
   HMSE_WS_ALIGNED(ws);
   if (!sb_piece_args_ok(piece_bytes, cap_bytes, piece_bytes ? 1u : 0u, cfg)) return HMSE_EINVAL;
-  if (!data || !state || !rows || !cuts_all || !digests_g || !first_occ_g || !refcount_g || !l3_table || !uniq_all || !sig_all || !sig_row || world == 0 ||
-      world > 256 || rank >= world || (world > 1 && !gidx))
-    return HMSE_EINVAL;
+  if (!data || !sb_stream_ok(s, SF_SIGN) || !rows || !sig_row) return HMSE_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;
   (void)hipGetLastError();
   const sb::Ws w = sb_carve(ws, cap_bytes, cfg);
   if (!ws || ws_bytes < w.total) return HMSE_ENOSPC;
-  const uint64_t cap = sb_cap_chunks(cap_bytes, cfg);
-  const uint64_t row_bytes = sb::ROW_HDR + 32 * cap;
   int rc;
-  const uint64_t gthreads = 2ull * world * cap;
-  sb::ingest_rows_kernel<<<dim3((uint32_t)((gthreads + 255) / 256)), dim3(256), 0, stream>>>(rows, row_bytes, world, rank, cap, digests_g, max_chunks_g, gidx, state);
-  if ((rc = hmse_l3_index_update_dyn(digests_g, first_occ_g, refcount_g, l3_table, l3_slots, state + SB_G_OLD, (uint64_t)world * cap, stream)) != HMSE_OK) return rc;
-  sb::select_uniq_kernel<<<dim3(1), dim3(1024), 0, stream>>>(first_occ_g, uniq_all, state, max_unique);
-  if ((rc = hmse_l4_minhash_dyn(data, data_cap, cuts_all, uniq_all, sig_all, state, cap, cfg, w.mh_ws, w.mh_bytes, stream)) != HMSE_OK) return rc;
-  sb::sig_row_kernel<<<dim3(1024), dim3(256), 0, stream>>>(sig_all, state, sb_sig_cap(cap_bytes, cfg), sig_row);
+  if ((rc = index_and_sign(data, data_cap, cap_bytes, cfg, s, rows, w, stream)) != HMSE_OK) return rc;
+  sb::sig_row_kernel<<<dim3(1024), dim3(256), 0, stream>>>(s->sig, s->state, sb_sig_cap(cap_bytes, cfg), sig_row);
   HMSE_LAUNCH_CHECK();
   return HMSE_OK;
 }
 
-extern "C" int hmse_stream_piece_bases(uint64_t cap_bytes, const hmse_cfg* cfg, uint64_t* state, const uint8_t* sig_rows, const hmse_gl4* g,
-                                       const uint64_t* uniq_all, uint32_t* band_keys, int64_t* base_all, void* ws, size_t ws_bytes, void* stream_) {
+extern "C" int hmse_stream_piece_bases(uint64_t cap_bytes, const hmse_cfg* cfg, const hmse_stream* s, const uint8_t* sig_rows, const hmse_gl4* g,
+                                       void* ws, size_t ws_bytes, void* stream_) {
   HMSE_WS_ALIGNED(ws);
-  if (hmse_cfg_validate_impl(cfg) != 0 || cap_bytes == 0 || !state || !sig_rows || !gl4_ok(g) || !uniq_all || !band_keys || !base_all) return HMSE_EINVAL;
+  if (hmse_cfg_validate_impl(cfg) != 0 || cap_bytes == 0 || !sb_stream_ok(s, SF_BASES) || !sig_rows || !gl4_ok(g)) return HMSE_EINVAL;
+  if (s->world != g->world || s->rank != g->rank) return HMSE_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;
   (void)hipGetLastError();
   const sb::Ws w = sb_carve(ws, cap_bytes, cfg);
@@ -500,36 +509,31 @@ extern "C" int hmse_stream_piece_bases(uint64_t cap_bytes, const hmse_cfg* cfg, 
   if (g->sig_cap != sig_cap) return HMSE_EINVAL;
   const uint64_t row_bytes = sb::SIG_HDR + sb::SIG_BYTES * sig_cap;
   sb::ingest_sig_rows_kernel<<<dim3(2048), dim3(256), 0, stream>>>(sig_rows, row_bytes, g->world, g->rank, sig_cap, g->sig_g, g->g_owner, g->g_local,
-                                                                 g->max_stored_g, g->gstate, state);
+                                                                 g->max_stored_g, g->gstate, s->state);
   int rc;
   if ((rc = hmse_l4_lsh_update_dyn(g->sig_g, g->band_keys_g, g->base_g, g->lsh_tables_g, g->lsh_slots_g, g->gstate, (uint64_t)g->world * sig_cap, cfg, stream)) != HMSE_OK)
     return rc;
-  sb::resolve_bases_kernel<<<dim3(1), dim3(1024), 0, stream>>>(g->base_g, g->band_keys_g, cfg->bands, g->g_owner, g->g_local, uniq_all, g->world, g->rank,
-                                                              g->ghost_chunk0, g->gstate, state, g->ug, g->base_global, base_all, band_keys, w.sel_ids, w.sel_base,
+  sb::resolve_bases_kernel<<<dim3(1), dim3(1024), 0, stream>>>(g->base_g, g->band_keys_g, cfg->bands, g->g_owner, g->g_local, s->uniq, g->world, g->rank,
+                                                              g->ghost_chunk0, g->gstate, s->state, g->ug, g->base_global, s->base, s->band_keys, w.sel_ids, w.sel_base,
                                                               w.n_sel, g->req_counts, g->req_slots);
   HMSE_LAUNCH_CHECK();
   return HMSE_OK;
 }
 
-extern "C" int hmse_stream_piece_encode_g(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const hmse_cfg* cfg, uint64_t* state,
-                                          uint64_t* gstate, const uint64_t* cuts_all, uint8_t* kind_all, uint64_t* stream_off_all, uint8_t* out,
-                                          uint64_t out_cap, void* ws, size_t ws_bytes, void* stream_) {
+extern "C" int hmse_stream_piece_encode_g(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const hmse_cfg* cfg,
+                                          const hmse_stream* s, uint64_t* gstate, void* ws, size_t ws_bytes, void* stream_) {
   HMSE_WS_ALIGNED(ws);
   if (!sb_piece_args_ok(piece_bytes, cap_bytes, piece_bytes ? 1u : 0u, cfg)) return HMSE_EINVAL;
-  if (!data || !state || !gstate || !cuts_all || !kind_all || !stream_off_all || !out) return HMSE_EINVAL;
+  if (!data || !sb_stream_ok(s, SF_ENCODE_G) || !gstate) return HMSE_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;
   (void)hipGetLastError();
   const sb::Ws w = sb_carve(ws, cap_bytes, cfg);
   if (!ws || ws_bytes < w.total) return HMSE_ENOSPC;
-  const uint64_t cap = sb_cap_chunks(cap_bytes, cfg);
   int rc;
-  sb::drop_failed_kernel<<<dim3(1), dim3(1), 0, stream>>>(state, w.n_sel);
-  if ((rc = hmse_l1_deflate_dyn(data, data_cap, cuts_all, w.sel_ids, w.sel_base, w.n_sel, cap, state + SB_S_OLD, cfg, out, out_cap, w.out_off, w.kind,
-                                w.dfl_status, w.dfl_ws, w.dfl_bytes, stream)) != HMSE_OK) return rc;
-  uint32_t ab = (uint32_t)((cap + 255) / 256); if (ab > 1024) ab = 1024;
-  sb::commit_kernel<<<dim3(ab), dim3(256), 0, stream>>>(w.kind, w.out_off, cap, kind_all, stream_off_all, w.dfl_status, state);
-  sb::advance_g_kernel<<<dim3(1), dim3(1), 0, stream>>>(gstate, state);
-  sb::advance_kernel<<<dim3(1), dim3(1), 0, stream>>>(state, piece_bytes);
+  sb::drop_failed_kernel<<<dim3(1), dim3(1), 0, stream>>>(s->state, w.n_sel);
+  if ((rc = deflate_and_commit(data, data_cap, cap_bytes, cfg, s, w, stream)) != HMSE_OK) return rc;
+  sb::advance_g_kernel<<<dim3(1), dim3(1), 0, stream>>>(gstate, s->state);
+  sb::advance_kernel<<<dim3(1), dim3(1), 0, stream>>>(s->state, piece_bytes);
   HMSE_LAUNCH_CHECK();
   return HMSE_OK;
 }

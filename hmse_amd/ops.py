@@ -474,26 +474,35 @@ def stream_workspace(batch_bytes: int, cfg: IngestConfig, device) -> torch.Tenso
     return ws
 
 
-def stream_batch(data: torch.Tensor, batch_bytes: int, seg_off: torch.Tensor, cfg: IngestConfig, state: torch.Tensor, cuts_all: torch.Tensor,
-                 max_chunks: int, digests_all: torch.Tensor, first_occ: torch.Tensor, refcount: torch.Tensor, l3_table: torch.Tensor,
-                 uniq_all: torch.Tensor, max_unique: int, sig_all: torch.Tensor, band_keys: torch.Tensor, base_all: torch.Tensor,
-                 lsh_tables: torch.Tensor, kind_all: torch.Tensor, stream_off_all: torch.Tensor, out: torch.Tensor, ws: torch.Tensor,
+class StreamArrays:
+    """A stream's descriptor (include/hmse.h: hmse_stream), built ONCE per stream from keyword arguments named after the struct's fields: a tensor gives
+    its address (checked and kept alive here), anything else is a capacity or world / rank; None is NULL (the library refuses a call that misses a field)."""
+
+    def __init__(self, **fields):
+        fields = {k: v for k, v in fields.items() if v is not None}
+        self.tensors = {k: v for k, v in fields.items() if isinstance(v, torch.Tensor)}
+        for k, t in self.tensors.items():
+            _require_gpu(t, k)
+        self.c = _lib.HmseStream(struct_size=C.sizeof(_lib.HmseStream), **{k: v.data_ptr() if k in self.tensors else int(v) for k, v in fields.items()})
+
+
+def _stream_call(name: str, *args, **tensors) -> None:
+    """One streaming entry point: `args`, then the workspace and the stream.  `tensors`: what it gets besides the descriptor (None: absent)."""
+    for nm, t in tensors.items():
+        if t is not None:
+            _require_gpu(t, nm)
+    ws = tensors["ws"]
+    _check(getattr(_lib.hip_lib(), name)(*args, ws.data_ptr(), ws.numel(), _stream()), name)
+
+
+def stream_batch(data: torch.Tensor, batch_bytes: int, seg_off: torch.Tensor, cfg: IngestConfig, s: StreamArrays, ws: torch.Tensor,
                  data_origin: int = 0) -> None:
     """hmse_stream_batch: the whole per-batch chain (L2 -> L3 -> index -> L4 -> band tables -> L1) enqueued without a host
     read; capturable into a hipGraph (hmse_amd/stream.py).  README.md:1519-1580."""
-    for t, nm in ((data, "data"), (seg_off, "seg_off"), (state, "state"), (cuts_all, "cuts"), (digests_all, "digests"), (first_occ, "first_occ"),
-                  (refcount, "refcount"), (l3_table, "l3_table"), (uniq_all, "uniq"), (sig_all, "sig"), (band_keys, "band_keys"), (base_all, "base"),
-                  (lsh_tables, "lsh_tables"), (kind_all, "kind"), (stream_off_all, "stream_off"), (out, "out"), (ws, "ws")):
-        _require_gpu(t, nm)
-    c = cfg.to_c()
     # data_origin: `data` holds the stream's bytes [data_origin, data_origin + data.numel()) — the resident WINDOW of a stream longer than
     # the buffer (stream.StreamIngest(window_bytes=)); the chain addresses bytes by stream offset, so it gets the buffer's address minus the origin
-    rc = _lib.hip_lib().hmse_stream_batch(data.data_ptr() - int(data_origin), int(data_origin) + data.numel(), int(batch_bytes), _ptr(seg_off), seg_off.numel() - 1, C.byref(c), _ptr(state),
-                                         _ptr(cuts_all), int(max_chunks), _ptr(digests_all), _ptr(first_occ), _ptr(refcount), _ptr(l3_table),
-                                         l3_table.numel(), _ptr(uniq_all), int(max_unique), _ptr(sig_all), _ptr(band_keys), _ptr(base_all),
-                                         _ptr(lsh_tables), lsh_tables.shape[1], _ptr(kind_all), _ptr(stream_off_all), _ptr(out), out.numel(),
-                                         ws.data_ptr(), ws.numel(), _stream())
-    _check(rc, "hmse_stream_batch")
+    _stream_call("hmse_stream_batch", data.data_ptr() - int(data_origin), int(data_origin) + data.numel(), int(batch_bytes), _ptr(seg_off),
+                 seg_off.numel() - 1, C.byref(cfg.to_c()), C.byref(s.c), data=data, seg_off=seg_off, ws=ws)
 
 
 def stream_row_bytes(cap_bytes: int, cfg: IngestConfig) -> int:
@@ -501,42 +510,21 @@ def stream_row_bytes(cap_bytes: int, cfg: IngestConfig) -> int:
     return int(_lib.hip_lib().hmse_stream_row_bytes(int(cap_bytes), C.byref(c)))
 
 
-def stream_piece_hash(data: torch.Tensor, piece_bytes: int, cap_bytes: int, seg_off: torch.Tensor | None, cfg: IngestConfig, state: torch.Tensor,
-                      cuts_all: torch.Tensor, max_chunks: int, row: torch.Tensor, ws: torch.Tensor) -> None:
+def stream_piece_hash(data: torch.Tensor, piece_bytes: int, cap_bytes: int, seg_off: torch.Tensor | None, cfg: IngestConfig, s: StreamArrays,
+                      row: torch.Tensor, ws: torch.Tensor) -> None:
     """hmse_stream_piece_hash: phase A of a multi-rank stream's batch (L2 + L3 hash of this rank's piece -> its exchange row).
     README.md:1519-1540."""
-    for t, nm in ((data, "data"), (state, "state"), (cuts_all, "cuts"), (row, "row"), (ws, "ws")):
-        _require_gpu(t, nm)
-    if seg_off is not None:
-        _require_gpu(seg_off, "seg_off")
-    c = cfg.to_c()
-    rc = _lib.hip_lib().hmse_stream_piece_hash(_ptr(data), data.numel(), int(piece_bytes), int(cap_bytes), _ptr(seg_off),
-                                              0 if seg_off is None else seg_off.numel() - 1, C.byref(c), _ptr(state), _ptr(cuts_all), int(max_chunks),
-                                              _ptr(row), ws.data_ptr(), ws.numel(), _stream())
-    _check(rc, "hmse_stream_piece_hash")
+    _stream_call("hmse_stream_piece_hash", _ptr(data), data.numel(), int(piece_bytes), int(cap_bytes), _ptr(seg_off),
+                 0 if seg_off is None else seg_off.numel() - 1, C.byref(cfg.to_c()), C.byref(s.c), _ptr(row), data=data, seg_off=seg_off, row=row, ws=ws)
 
 
-def stream_piece_encode(data: torch.Tensor, piece_bytes: int, cap_bytes: int, cfg: IngestConfig, state: torch.Tensor, rows: torch.Tensor, world: int,
-                        rank: int, cuts_all: torch.Tensor, gidx: torch.Tensor | None, digests_g: torch.Tensor, max_chunks_g: int,
-                        first_occ_g: torch.Tensor, refcount_g: torch.Tensor, l3_table: torch.Tensor, uniq_all: torch.Tensor, max_unique: int,
-                        sig_all: torch.Tensor, band_keys: torch.Tensor, base_all: torch.Tensor, lsh_tables: torch.Tensor, kind_all: torch.Tensor,
-                        stream_off_all: torch.Tensor, out: torch.Tensor, ws: torch.Tensor) -> None:
+def stream_piece_encode(data: torch.Tensor, piece_bytes: int, cap_bytes: int, cfg: IngestConfig, s: StreamArrays, rows: torch.Tensor,
+                        ws: torch.Tensor) -> None:
     """hmse_stream_piece_encode: phase B (gathered rows -> global index -> this rank's stored chunks -> L4 -> L1).  README.md:1538-1580."""
-    for t, nm in ((data, "data"), (state, "state"), (rows, "rows"), (cuts_all, "cuts"), (digests_g, "digests"), (first_occ_g, "first_occ"),
-                  (refcount_g, "refcount"), (l3_table, "l3_table"), (uniq_all, "uniq"), (sig_all, "sig"), (band_keys, "band_keys"), (base_all, "base"),
-                  (lsh_tables, "lsh_tables"), (kind_all, "kind"), (stream_off_all, "stream_off"), (out, "out"), (ws, "ws")):
-        _require_gpu(t, nm)
-    if gidx is not None:
-        _require_gpu(gidx, "gidx")
-    if rows.numel() != world * stream_row_bytes(cap_bytes, cfg):
+    if rows.numel() != s.c.world * stream_row_bytes(cap_bytes, cfg):
         raise HmseError(-1, "stream_piece_encode: rows must hold one exchange row per rank")
-    c = cfg.to_c()
-    rc = _lib.hip_lib().hmse_stream_piece_encode(_ptr(data), data.numel(), int(piece_bytes), int(cap_bytes), C.byref(c), _ptr(state), _ptr(rows), int(world),
-                                                int(rank), _ptr(cuts_all), _ptr(gidx), _ptr(digests_g), int(max_chunks_g), _ptr(first_occ_g),
-                                                _ptr(refcount_g), _ptr(l3_table), l3_table.numel(), _ptr(uniq_all), int(max_unique), _ptr(sig_all),
-                                                _ptr(band_keys), _ptr(base_all), _ptr(lsh_tables), lsh_tables.shape[1], _ptr(kind_all),
-                                                _ptr(stream_off_all), _ptr(out), out.numel(), ws.data_ptr(), ws.numel(), _stream())
-    _check(rc, "hmse_stream_piece_encode")
+    _stream_call("hmse_stream_piece_encode", _ptr(data), data.numel(), int(piece_bytes), int(cap_bytes), C.byref(cfg.to_c()), C.byref(s.c), _ptr(rows),
+                 data=data, rows=rows, ws=ws)
 
 
 # ---- global L4 of a multi-rank stream as captured phases (include/hmse.h: hmse_gl4) ---------------------------------------------
@@ -550,39 +538,22 @@ def stream_sig_row_bytes(cap_bytes: int, cfg: IngestConfig) -> int:
     return int(_lib.hip_lib().hmse_stream_sig_row_bytes(int(cap_bytes), C.byref(c)))
 
 
-def stream_piece_sign(data, piece_bytes, cap_bytes, cfg, state, rows, world, rank, cuts_all, gidx, digests_g, max_chunks_g, first_occ_g, refcount_g,
-                      l3_table, uniq_all, max_unique, sig_all, sig_row, ws) -> None:
+def stream_piece_sign(data, piece_bytes, cap_bytes, cfg, s: StreamArrays, rows, sig_row, ws) -> None:
     """hmse_stream_piece_sign: gathered digest rows -> global index -> this rank's new stored chunks -> MinHash -> its signature row."""
-    for t, nm in ((data, "data"), (state, "state"), (rows, "rows"), (cuts_all, "cuts"), (digests_g, "digests"), (first_occ_g, "first_occ"),
-                  (refcount_g, "refcount"), (l3_table, "l3_table"), (uniq_all, "uniq"), (sig_all, "sig"), (sig_row, "sig_row"), (ws, "ws")):
-        _require_gpu(t, nm)
-    c = cfg.to_c()
-    rc = _lib.hip_lib().hmse_stream_piece_sign(_ptr(data), data.numel(), int(piece_bytes), int(cap_bytes), C.byref(c), _ptr(state), _ptr(rows), int(world),
-                                              int(rank), _ptr(cuts_all), _ptr(gidx), _ptr(digests_g), int(max_chunks_g), _ptr(first_occ_g), _ptr(refcount_g),
-                                              _ptr(l3_table), l3_table.numel(), _ptr(uniq_all), int(max_unique), _ptr(sig_all), _ptr(sig_row),
-                                              ws.data_ptr(), ws.numel(), _stream())
-    _check(rc, "hmse_stream_piece_sign")
+    _stream_call("hmse_stream_piece_sign", _ptr(data), data.numel(), int(piece_bytes), int(cap_bytes), C.byref(cfg.to_c()), C.byref(s.c), _ptr(rows), _ptr(sig_row),
+                 data=data, rows=rows, sig_row=sig_row, ws=ws)
 
 
-def stream_piece_bases(cap_bytes, cfg, state, sig_rows, gl4, uniq_all, band_keys, base_all, ws) -> None:
+def stream_piece_bases(cap_bytes, cfg, s: StreamArrays, sig_rows, gl4, ws) -> None:
     """hmse_stream_piece_bases: gathered signature rows -> global band tables -> dictionaries of this rank's new stored chunks + requests.
     `gl4`: a _lib.HmseGl4 (kept alive by the caller together with the tensors it points to)."""
-    for t, nm in ((state, "state"), (sig_rows, "sig_rows"), (uniq_all, "uniq"), (band_keys, "band_keys"), (base_all, "base"), (ws, "ws")):
-        _require_gpu(t, nm)
-    c = cfg.to_c()
-    rc = _lib.hip_lib().hmse_stream_piece_bases(int(cap_bytes), C.byref(c), _ptr(state), _ptr(sig_rows), C.byref(gl4), _ptr(uniq_all), _ptr(band_keys),
-                                               _ptr(base_all), ws.data_ptr(), ws.numel(), _stream())
-    _check(rc, "hmse_stream_piece_bases")
+    _stream_call("hmse_stream_piece_bases", int(cap_bytes), C.byref(cfg.to_c()), C.byref(s.c), _ptr(sig_rows), C.byref(gl4), sig_rows=sig_rows, ws=ws)
 
 
-def stream_piece_encode_g(data, piece_bytes, cap_bytes, cfg, state, gstate, cuts_all, kind_all, stream_off_all, out, ws) -> None:
+def stream_piece_encode_g(data, piece_bytes, cap_bytes, cfg, s: StreamArrays, gstate, ws) -> None:
     """hmse_stream_piece_encode_g: DEFLATE of the new stored chunks with the dictionaries resolved by stream_piece_bases, tails, states advanced."""
-    for t, nm in ((data, "data"), (state, "state"), (gstate, "gstate"), (cuts_all, "cuts"), (kind_all, "kind"), (stream_off_all, "stream_off"), (out, "out"), (ws, "ws")):
-        _require_gpu(t, nm)
-    c = cfg.to_c()
-    rc = _lib.hip_lib().hmse_stream_piece_encode_g(_ptr(data), data.numel(), int(piece_bytes), int(cap_bytes), C.byref(c), _ptr(state), _ptr(gstate),
-                                                  _ptr(cuts_all), _ptr(kind_all), _ptr(stream_off_all), _ptr(out), out.numel(), ws.data_ptr(), ws.numel(), _stream())
-    _check(rc, "hmse_stream_piece_encode_g")
+    _stream_call("hmse_stream_piece_encode_g", _ptr(data), data.numel(), int(piece_bytes), int(cap_bytes), C.byref(cfg.to_c()), C.byref(s.c), _ptr(gstate),
+                 data=data, gstate=gstate, ws=ws)
 
 
 def band_tables_write(keys: torch.Tensor, sig: torch.Tensor | None, band_bits: int) -> torch.Tensor:

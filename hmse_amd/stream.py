@@ -18,8 +18,8 @@ import torch
 from . import ops
 from .config import LAYER_L1, LAYER_L2, LAYER_L3, LAYER_L4, IngestConfig
 from .ingest import ShardResult, shard_stats
-from .stream_common import (PhaseGraphs, SizeEntry, chain_status_error, default_max_chunks, default_stream_capacity, deflate_ws_bytes, issue_copy,
-                            max_stored)
+from .stream_common import (SB_G_OLD, SB_N_OLD, SB_OFF, SB_S_OLD, SB_STATUS, SB_U_OLD, SB_WORDS, PhaseGraphs, SizeEntry, chain_status_error,
+                            default_max_chunks, default_stream_capacity, deflate_ws_bytes, issue_copy, max_stored)
 
 
 class StreamIngest:
@@ -85,7 +85,8 @@ class StreamIngest:
         self._ws = None             # DEFLATE workspace, kept across batches
         self.graph = bool(graph)
         if self.graph:
-            self._state = torch.zeros(16, dtype=torch.int64, device=device)
+            self._state = torch.zeros(SB_WORDS, dtype=torch.int64, device=device)
+            self._arrays = None                     # ops.StreamArrays: built by the first chain call, from the arrays as they are then
             self._streams = torch.empty(int(stream_capacity or default_stream_capacity(capacity_bytes)), dtype=torch.uint8, device=device)
             # per batch size: segment offsets and a chain workspace; the one enqueue of a batch is captured at the size's second use
             self._graphs = PhaseGraphs(True, lambda n: SizeEntry(ops.segment_offsets(n, cfg.seg_size, device), ops.stream_workspace(n, cfg, device)))
@@ -219,14 +220,22 @@ class StreamIngest:
     def _read_state(self) -> None:
         """The ONE host read of the chain: counts after the batches enqueued so far."""
         st = self._state.tolist()
-        if st[7]:
-            raise chain_status_error(st[7], intact=f" ({st[0]} bytes / {st[1]} chunks are intact)")
-        self.n_done, self.n_chunks, self.n_unique, self.stream_bytes = st[0], st[1], st[3], st[5]
+        if st[SB_STATUS]:
+            raise chain_status_error(st[SB_STATUS], intact=f" ({st[SB_OFF]} bytes / {st[SB_N_OLD]} chunks are intact)")
+        self.n_done, self.n_chunks, self.n_unique, self.stream_bytes = st[SB_OFF], st[SB_N_OLD], st[SB_U_OLD], st[SB_S_OLD]
+
+    def _stream_arrays(self) -> ops.StreamArrays:
+        """The stream's descriptor for the library: one rank, whose chunk order is the global one."""
+        if self._arrays is None:
+            self._arrays = ops.StreamArrays(
+                world=1, rank=0, state=self._state, cuts=self._cuts, max_chunks=self.max_chunks, digests=self._digests, max_chunks_g=self.max_chunks,
+                first_occ=self._first_occ, refcount=self._refcount, l3_table=self._l3_table, l3_slots=self._l3_table.numel(), uniq=self._uniq,
+                max_unique=self.max_unique, sig=self._sig, band_keys=self._band_keys, base=self._base, lsh_tables=self._lsh_tables,
+                lsh_slots=self._lsh_tables.shape[1], kind=self._kind, stream_off=self._stream_off, out=self._streams, out_cap=self._streams.numel())
+        return self._arrays
 
     def _chain_call(self, n: int, seg_off: torch.Tensor, ws: torch.Tensor) -> None:
-        ops.stream_batch(self.data, n, seg_off, self.cfg, self._state, self._cuts, self.max_chunks, self._digests, self._first_occ, self._refcount,
-                         self._l3_table, self._uniq, self.max_unique, self._sig, self._band_keys, self._base, self._lsh_tables, self._kind,
-                         self._stream_off, self._streams, ws, data_origin=self._wproc0)
+        ops.stream_batch(self.data, n, seg_off, self.cfg, self._stream_arrays(), ws, data_origin=self._wproc0)
 
     def _process_chain(self, off: int, n: int, copied: torch.cuda.Event) -> None:
         if self._state_dirty:   # first chain call (possibly after resume()): host counters -> device state
@@ -234,7 +243,8 @@ class StreamIngest:
             if self.n_chunks == 0:
                 ops.l3_index_update(self._digests, 0, 0, self._first_occ, self._refcount, self._l3_table)      # clears the table
                 ops.l4_lsh_update(self._sig, 0, 0, self.cfg, self._band_keys, self._base, self._lsh_tables)     # clears the tables
-            self._state.copy_(torch.tensor([off, self.n_chunks, 0, self.n_unique, 0, self.stream_bytes, 0, 0, self.n_chunks] + [0] * 7, dtype=torch.int64))
+            words = {SB_OFF: off, SB_N_OLD: self.n_chunks, SB_U_OLD: self.n_unique, SB_S_OLD: self.stream_bytes, SB_G_OLD: self.n_chunks}
+            self._state.copy_(torch.tensor([words.get(i, 0) for i in range(SB_WORDS)], dtype=torch.int64))
             self._state_dirty = False
         torch.cuda.current_stream().wait_event(copied)
         if self._wstarts and off == self._wstarts[0]:
@@ -251,7 +261,7 @@ class StreamIngest:
         self._n_chain_batches += 1
         if self.poll_status_every and self._n_chain_batches % self.poll_status_every == 0:
             host = torch.zeros(1, dtype=torch.int64).pin_memory()
-            host.copy_(self._state[7:8], non_blocking=True)
+            host.copy_(self._state[SB_STATUS: SB_STATUS + 1], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
             self._polls.append((host, ev, self._n_chain_batches))

@@ -98,22 +98,39 @@ class PhaseGraphs:
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# the chain's sticky status word (state[7])
+# the chain's state block and its sticky status word: mirrors of HMSE_SB_*, HMSE_STREAM_ST_*, HMSE_GL4_REQ_* (include/hmse.h; tests/test_abi_layout.py)
 # ---------------------------------------------------------------------------------------------------------------------------
-HOST_REFUSED = 1 << 16      # state[7] bit 16: set by the HOST of a captured rank between two phases of a batch (CapturedRankStream._host_refuse)
+SB_OFF, SB_N_OLD, SB_N_NEW, SB_U_OLD, SB_U_NEW, SB_S_OLD, SB_S_NEW, SB_STATUS, SB_G_OLD, SB_G_NEW, SB_G_BASE = range(11)
+SB_WORDS = 16
+ST_CHUNK_CAP, ST_STORED_CAP, ST_L2, ST_ROW, ST_WS_INIT, ST_STATE, ST_PUSH_REFUSED, ST_SIG_ROW = (1 << i for i in range(8))
+ST_DEFLATE_SHIFT = 8
+ST_HOST_REFUSED = 1 << 16   # set by the HOST of a captured rank between two phases of a batch (CapturedRankStream._host_refuse)
+GL4_REQ_TOTAL, GL4_REQ_STORED, GL4_REQ_EXTRA = 0, 1, 2      # req_counts[world + ...]
+
+# (bit, its name behind HMSE_STREAM_ST_ in the header, what it tells the caller) — chain_status_error's text
+STATUS_BITS = (
+    (ST_CHUNK_CAP, "CHUNK_CAP", "chunk capacity"),
+    (ST_STORED_CAP, "STORED_CAP", "stored-chunk capacity"),
+    (ST_L2, "L2", "L2 (the batch holds more cut candidates than the chain's fixed candidate list, or more chunks than its cut list: bytes that dense "
+              "are ingested by ingest_shard or a graph=False stream, whose L2 call is run again with a larger list)"),
+    (ST_ROW, "ROW", "exchange row"),
+    (ST_WS_INIT, "WS_INIT", "workspace not initialised"),
+    (ST_STATE, "STATE", "state block inconsistent ([8] != [1] on one rank)"),
+    (ST_PUSH_REFUSED, "PUSH_REFUSED", "a piece refused by push()"),
+    (ST_SIG_ROW, "SIG_ROW", "more new stored chunks than a signature row holds (the row is sized for the worst-case chunk count of a piece: a row of "
+                     "another build)"),
+    (ST_HOST_REFUSED, "HOST_REFUSED", "a batch refused on the host between two phases (a remote dictionary a peer did not serve, the ghost area, a "
+                              "phase's error code)"),
+)
+DEFLATE_BITS = "bits 8..12 DEFLATE (0x100 stream capacity, 0x200 workspace)"
 
 
 def chain_status_error(status: int, where: str = "", host_error: str | None = None, intact: str = "") -> ValueError:
-    return ValueError(
-        f"streaming chain status {status:#x}{where}: bit0 chunk capacity, bit1 stored-chunk capacity, bit2 L2 (the batch holds more cut "
-        "candidates than the chain's fixed candidate list, or more chunks than its cut list: bytes that dense are ingested by ingest_shard or a "
-        "graph=False stream, whose L2 call is run again with a larger list), bit3 exchange row, bit4 workspace not initialised, bit5 state block "
-        "inconsistent ([8] != [1] on one rank), bit6 a piece refused by push()" + (f" (this rank: {host_error})" if host_error and not status & HOST_REFUSED else "")
-        + ", bit7 more new stored chunks than a signature row holds (the row is sized for the worst-case chunk count of a piece: a row of another "
-        "build), bits 8..12 DEFLATE (0x100 stream capacity, 0x200 workspace), bit16 a batch refused on the host between two phases (a remote "
-        "dictionary a peer did not serve, the ghost area, a phase's error code)" + (f" (this rank: {host_error})" if host_error and status & HOST_REFUSED else "")
-        + "; the failing batch "
-        "and every later one were dropped" + intact)
+    # the reason a rank gave itself goes behind the bit it set: HOST_REFUSED if that is up, else PUSH_REFUSED
+    mine = {(ST_HOST_REFUSED if status & ST_HOST_REFUSED else ST_PUSH_REFUSED): f" (this rank: {host_error})"} if host_error else {}
+    bits = [f"bit{bit.bit_length() - 1} {text}{mine.get(bit, '')}" for bit, _, text in STATUS_BITS]
+    bits.insert(-1, DEFLATE_BITS)
+    return ValueError(f"streaming chain status {status:#x}{where}: " + ", ".join(bits) + "; the failing batch and every later one were dropped" + intact)
 
 
 def agreed_status(status: int, world: int, group, dev, lockstep: bool) -> int:
@@ -278,7 +295,9 @@ class CapturedRankStream(RankStream):
         self._kind = z(mu, torch.uint8)
         self._stream_off = z(mu + 1, torch.int64)
         self._streams = torch.empty(int(stream_capacity or default_stream_capacity(self.capacity)), dtype=torch.uint8, device=device)
-        self._state = z(16, torch.int64)
+        self._lsh_tables = None                               # this rank's band tables, where a subclass keeps them per rank (stream_dist)
+        self._state = z(SB_WORDS, torch.int64)
+        self._arrays = None                                   # ops.StreamArrays, built at the first phase (_stream_arrays)
         self._host_error = None
         self._host_refused = False
         self._ws = ops.stream_workspace(self.cap_bytes, self.cfg, device)
@@ -299,7 +318,7 @@ class CapturedRankStream(RankStream):
         return bool(err)
 
     def _mark_refused(self) -> None:
-        self._state[7:8] |= 64
+        self._state[SB_STATUS: SB_STATUS + 1] |= ST_PUSH_REFUSED
 
     def _host_refuse(self, reason: str) -> None:
         """A rank-local failure BETWEEN two phases of a batch (the peers are at, or on their way to, the next collective): like
@@ -307,7 +326,18 @@ class CapturedRankStream(RankStream):
         every later batch is a no-op, the rank keeps taking part in every collective, and finish() raises on every rank."""
         self._host_error = self._host_error or reason
         self._host_refused = True
-        self._state[7:8] |= HOST_REFUSED
+        self._state[SB_STATUS: SB_STATUS + 1] |= ST_HOST_REFUSED
+
+    def _stream_arrays(self) -> ops.StreamArrays:
+        """This rank's descriptor for the library, built at the first phase: a subclass may allocate band tables of its own after __init__."""
+        if self._arrays is None:
+            self._arrays = ops.StreamArrays(
+                world=self.world, rank=self.rank, state=self._state, cuts=self._cuts, max_chunks=self.max_chunks, gidx=self._gidx,
+                digests=self._digests_g, max_chunks_g=self.max_chunks_g, first_occ=self._first_occ_g, refcount=self._refcount_g,
+                l3_table=self._l3_table, l3_slots=self._l3_table.numel(), uniq=self._uniq, max_unique=self.max_unique, sig=self._sig,
+                band_keys=self._band_keys, base=self._base, lsh_tables=self._lsh_tables, lsh_slots=None if self._lsh_tables is None else self._lsh_tables.shape[1],
+                kind=self._kind, stream_off=self._stream_off, out=self._streams, out_cap=self._streams.numel())
+        return self._arrays
 
     def _gather(self, row: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
         if self.world == 1 and not self._always_exchange:
@@ -324,7 +354,7 @@ class CapturedRankStream(RankStream):
 
     def read_state(self, check: bool = True) -> list:
         st = self._state.tolist()
-        status = agreed_status(st[7], self.world, self.group, self.dev, self.lockstep) if check else 0
+        status = agreed_status(st[SB_STATUS], self.world, self.group, self.dev, self.lockstep) if check else 0
         if status:
             raise chain_status_error(status, " on some rank", self._host_error)
         return st

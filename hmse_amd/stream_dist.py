@@ -30,7 +30,8 @@ from . import ops
 from .config import IngestConfig
 from .ingest import ShardResult
 from .stream_common import all_gather_rows, deal_batch  # noqa: F401  (part of this module's surface: tests/ and tools/ call them here)
-from .stream_common import CapturedRankStream, RankStream, deflate_ws_bytes, lockstep_ranks, max_stored, remote_base_rows, serve_chunks, serve_requests
+from .stream_common import (SB_G_OLD, SB_N_OLD, SB_OFF, SB_S_OLD, SB_U_OLD, CapturedRankStream, RankStream, deflate_ws_bytes, lockstep_ranks, max_stored,
+                            remote_base_rows, serve_chunks, serve_requests)
 
 _DEBUG_SYNC = os.environ.get("HMSE_STREAM_DEBUG_SYNC") == "1"
 
@@ -48,15 +49,6 @@ class DistStreamIngest(CapturedRankStream):
         ops.l4_lsh_update(self._sig, 0, 0, cfg, self._band_keys, self._base, self._lsh_tables)               # clears the tables
 
     # ------------------------------------------------------------------ the two phases (enqueue only)
-    def _call_hash(self, n: int, seg_off) -> None:
-        ops.stream_piece_hash(self.data, n, self.cap_bytes, seg_off, self.cfg, self._state, self._cuts, self.max_chunks, self._row, self._ws)
-
-    def _call_encode(self, n: int, rows: torch.Tensor) -> None:
-        ops.stream_piece_encode(self.data, n, self.cap_bytes, self.cfg, self._state, rows, self.world, self.rank, self._cuts, self._gidx,
-                                self._digests_g, self.max_chunks_g, self._first_occ_g, self._refcount_g, self._l3_table, self._uniq,
-                                self.max_unique, self._sig, self._band_keys, self._base, self._lsh_tables, self._kind, self._stream_off,
-                                self._streams, self._ws)
-
     def _debug_sync(self, phase: str, n: int) -> None:
         """HMSE_STREAM_DEBUG_SYNC=1: localise a device fault to (rank, batch, phase) — diagnostics only."""
         import sys
@@ -70,13 +62,13 @@ class DistStreamIngest(CapturedRankStream):
     def hash_piece(self, n: int) -> torch.Tensor:
         """Phase A for the next piece (its bytes are at data[state.off ..)): returns this rank's exchange row."""
         seg_off = self._graphs.entry(n).seg_off
-        self._graphs.run(n, "A", lambda: self._call_hash(n, seg_off))
+        self._graphs.run(n, "A", lambda: ops.stream_piece_hash(self.data, n, self.cap_bytes, seg_off, self.cfg, self._stream_arrays(), self._row, self._ws))
         return self._row
 
     def encode_piece(self, n: int, rows: torch.Tensor) -> None:
         """Phase B: `rows` = the rows of all ranks in rank order (a tensor whose address is stable across batches when graphs are on)."""
         rows = self._stable(rows, self._row, self._rows)
-        self._graphs.run(n, "B", lambda: self._call_encode(n, rows))
+        self._graphs.run(n, "B", lambda: ops.stream_piece_encode(self.data, n, self.cap_bytes, self.cfg, self._stream_arrays(), rows, self._ws))
         self._graphs.end_batch(n)
         self.n_batches += 1
 
@@ -89,9 +81,9 @@ class DistStreamIngest(CapturedRankStream):
     def finish(self, check: bool = True) -> ShardResult:
         self._drain()
         st = self.read_state(check)
-        n_unique = st[3]
-        return self._result(st[0], st[1], st[8], self._uniq[:n_unique], self._sig[:n_unique], self._band_keys[:n_unique], self._base[:n_unique],
-                            self._streams[: st[5]], self._stream_off[: n_unique + 1], self._kind[:n_unique])
+        n_unique = st[SB_U_OLD]
+        return self._result(st[SB_OFF], st[SB_N_OLD], st[SB_G_OLD], self._uniq[:n_unique], self._sig[:n_unique], self._band_keys[:n_unique],
+                            self._base[:n_unique], self._streams[: st[SB_S_OLD]], self._stream_off[: n_unique + 1], self._kind[:n_unique])
 
 
 def stream_shards_local(batches: list, cfg: IngestConfig, world: int, device, piece_bytes: int | None = None, graph: bool = True,

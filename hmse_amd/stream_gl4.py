@@ -28,8 +28,8 @@ import torch
 from . import _lib, ops
 from .config import IngestConfig
 from .ingest import ShardResult
-from .stream_common import (CapturedRankStream, chain_status_error, lockstep_ranks, max_stored, remote_base_rows, serve_chunks,
-                            serve_requests)
+from .stream_common import (GL4_REQ_EXTRA, GL4_REQ_STORED, GL4_REQ_TOTAL, SB_G_OLD, SB_N_OLD, SB_OFF, SB_S_OLD, SB_STATUS, SB_U_OLD, SB_WORDS,
+                            CapturedRankStream, chain_status_error, lockstep_ranks, max_stored, remote_base_rows, serve_chunks, serve_requests)
 
 
 class GraphGlobalL4StreamIngest(CapturedRankStream):
@@ -58,11 +58,11 @@ class GraphGlobalL4StreamIngest(CapturedRankStream):
         self._g_owner = z(mug, torch.int32)
         self._g_local = z(mug, torch.int64)
         ops.l4_lsh_update(self._sig_g, 0, 0, cfg, self._keys_g, self._base_g, self._lsh_tables_g)               # clears the tables
-        self._gstate = z(16, torch.int64)
+        self._gstate = z(SB_WORDS, torch.int64)
         self.sig_row_bytes = ops.stream_sig_row_bytes(self.cap_bytes, cfg)
         self._sig_row = z(self.sig_row_bytes, torch.uint8)
         self._sig_rows = z(self.world * self.sig_row_bytes, torch.uint8)
-        self._req_counts = z(self.world + 2, torch.int64)      # [world] = total, [world + 1] = this rank's stored chunks, this batch's included
+        self._req_counts = z(self.world + GL4_REQ_EXTRA, torch.int64)      # per rank, then the total and this rank's stored chunks, this batch's included
         self._req_slots = z(self.sig_cap, torch.int64)
         g = _lib.HmseGl4()
         g.struct_size = C.sizeof(_lib.HmseGl4); g.world = self.world; g.rank = self.rank; g.reserved = 0
@@ -79,23 +79,20 @@ class GraphGlobalL4StreamIngest(CapturedRankStream):
     # ------------------------------------------------------------------ the phases of one batch (enqueue only; captured at a size's second use)
     def phase_a(self, n: int) -> torch.Tensor:
         seg_off = self._graphs.entry(n).seg_off
-        self._graphs.run(n, "A", lambda: ops.stream_piece_hash(self.data, n, self.cap_bytes, seg_off, self.cfg, self._state, self._cuts, self.max_chunks, self._row, self._ws))
+        self._graphs.run(n, "A", lambda: ops.stream_piece_hash(self.data, n, self.cap_bytes, seg_off, self.cfg, self._stream_arrays(), self._row, self._ws))
         return self._row
 
     def phase_b1(self, n: int, rows: torch.Tensor) -> torch.Tensor:
         rows = self._stable(rows, self._row, self._rows)
-        self._graphs.run(n, "B1", lambda: ops.stream_piece_sign(self.data, n, self.cap_bytes, self.cfg, self._state, rows, self.world, self.rank, self._cuts, self._gidx,
-                                                                self._digests_g, self.max_chunks_g, self._first_occ_g, self._refcount_g, self._l3_table, self._uniq,
-                                                                self.max_unique, self._sig, self._sig_row, self._ws))
+        self._graphs.run(n, "B1", lambda: ops.stream_piece_sign(self.data, n, self.cap_bytes, self.cfg, self._stream_arrays(), rows, self._sig_row, self._ws))
         return self._sig_row
 
     def phase_b2(self, n: int, sig_rows: torch.Tensor) -> None:
         sig_rows = self._stable(sig_rows, self._sig_row, self._sig_rows)
-        self._graphs.run(n, "B2", lambda: ops.stream_piece_bases(self.cap_bytes, self.cfg, self._state, sig_rows, self._gl4, self._uniq, self._band_keys, self._base, self._ws))
+        self._graphs.run(n, "B2", lambda: ops.stream_piece_bases(self.cap_bytes, self.cfg, self._stream_arrays(), sig_rows, self._gl4, self._ws))
 
     def phase_b3(self, n: int) -> None:
-        self._graphs.run(n, "B3", lambda: ops.stream_piece_encode_g(self.data, n, self.cap_bytes, self.cfg, self._state, self._gstate, self._cuts, self._kind,
-                                                                    self._stream_off, self._streams, self._ws))
+        self._graphs.run(n, "B3", lambda: ops.stream_piece_encode_g(self.data, n, self.cap_bytes, self.cfg, self._stream_arrays(), self._gstate, self._ws))
         self._graphs.end_batch(n)
         self.n_batches += 1
 
@@ -104,10 +101,10 @@ class GraphGlobalL4StreamIngest(CapturedRankStream):
         """(requests per owner rank [world], the owners' stored slots grouped by owner) of the batch phase B2 just resolved — ONE host read,
         which also brings this rank's stored count (`n_stored_now`: what a peer may ask of it in this batch)."""
         c = self._req_counts.tolist()
-        self.n_stored_now = c[self.world + 1]
+        self.n_stored_now = c[self.world + GL4_REQ_STORED]
         if self._host_refused:          # this rank is out: it asks for nothing (the array may be a batch old), and goes on serving
             return [0] * self.world, self._req_slots[:0]
-        return c[: self.world], self._req_slots[: c[self.world]]
+        return c[: self.world], self._req_slots[: c[self.world + GL4_REQ_TOTAL]]
 
     def serve(self, local_slots: torch.Tensor):
         """Raw bytes of this rank's stored chunks `local_slots` (what a peer's fetch gets): (bytes, lens).  A chunk stored by THIS batch
@@ -163,9 +160,9 @@ class GraphGlobalL4StreamIngest(CapturedRankStream):
     def finish(self, check: bool = True) -> ShardResult:
         self._drain()
         st = self.read_state(check)
-        nu = st[3]
+        nu = st[SB_U_OLD]
         base, bg, kind = self._base[:nu], self._base_global[:nu], self._kind[:nu]
-        return self._result(st[0], st[1], st[8], self._uniq[:nu], self._sig[:nu], self._band_keys[:nu], base, self._streams[: st[5]],
+        return self._result(st[SB_OFF], st[SB_N_OLD], st[SB_G_OLD], self._uniq[:nu], self._sig[:nu], self._band_keys[:nu], base, self._streams[: st[SB_S_OLD]],
                             self._stream_off[: nu + 1], kind, base_global=bg, ug=self._ug[:nu],
                             remote_bases=remote_base_rows(bg, base, kind, self._g_owner, self._g_local))
 
@@ -206,7 +203,7 @@ def stream_shards_local_gl4_graph(batches: list, cfg: IngestConfig, world: int, 
     after GraphGlobalL4StreamIngest.finish() — which fails on EVERY rank if one rank dropped a batch (between processes: the all-reduce
     of the status; here the same rule by hand, for the peers of such a rank have indexed chunks that nobody stores)."""
     ranks = lockstep_gl4_graph(batches, cfg, world, device, **kw)
-    status = [int(s._state[7].item()) for s in ranks]
+    status = [int(s._state[SB_STATUS].item()) for s in ranks]
     if any(status):
         r = max(range(world), key=lambda i: status[i])
         raise chain_status_error(status[r], f" on rank {r}", ranks[r]._host_error)

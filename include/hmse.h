@@ -27,8 +27,8 @@
  *     and left as it was behind it (cuts beyond n_cuts, out beyond out_off[n_sel], the hmse_gc_plan arrays beyond counts[],
  *     ranges of hmse_scrub_attribute beyond counts[0] pairs): read the count, not the rest.  The two exceptions are state the
  *     caller carries from call to call and says so: the workspace of a stream between hmse_stream_workspace_init and its batches, and the persistent tables of hmse_l3_index_update / hmse_l4_lsh_update
- *     (cleared by the call with n_old == 0), with the arrays and the state block they index (of a stream's arrays the first
- *     batch reads cuts_all[0] and stream_off_all[0], the start of the first chunk and of the first record: 0);
+ *     (cleared by the call with n_old == 0), with the arrays and the state block they index (of a stream's arrays, hmse_stream, the
+ *     first batch reads cuts[0] and stream_off[0], the start of the first chunk and of the first record: 0);
  *   - nothing outside [p, p + declared size) is read with effect or written: the bytes behind n / streams_bytes / blob_bytes
  *     and around every output may be anything and are left as they are.
  */
@@ -42,11 +42,14 @@
 extern "C" {
 #endif
 
-/* 2 (round 4): contracts of existing entry points changed in round 3 — hmse_stream_batch / hmse_stream_piece_* need a workspace
- * prepared by hmse_stream_workspace_init (else status bit4) and take the global chunk count from state[8] (one rank: state[8] must
- * equal state[1]; a mismatch is status bit5); hmse_l1_deflate keeps ONE record per chunk in its workspace
- * (hmse_l1_deflate_record_bytes / _dict).  A caller built against version 1 must check hmse_abi_version() and refuse. */
-#define HMSE_ABI_VERSION 2
+/* 3: the streaming entry points (hmse_stream_batch, hmse_stream_piece_*) take a stream's persistent arrays as ONE descriptor
+ * (hmse_stream) instead of some twenty positional pointers and capacities, of which two of one type in swapped order compiled, loaded
+ * and ran; the words and status bits of the state block are named here (HMSE_SB_*, HMSE_STREAM_ST_*).  No layout or result changed.
+ * 2 (round 4): contracts of existing entry points changed in round 3 — hmse_stream_batch / hmse_stream_piece_* need a workspace
+ * prepared by hmse_stream_workspace_init (else HMSE_STREAM_ST_WS_INIT) and take the global chunk count from state[HMSE_SB_G_OLD] (one
+ * rank: it must equal state[HMSE_SB_N_OLD]; a mismatch is HMSE_STREAM_ST_STATE); hmse_l1_deflate keeps ONE record per chunk in its
+ * workspace (hmse_l1_deflate_record_bytes / _dict).  A caller built against another version must check hmse_abi_version() and refuse. */
+#define HMSE_ABI_VERSION 3
 
 enum {
   HMSE_OK      = 0,
@@ -308,34 +311,85 @@ int hmse_read_assemble(const uint64_t* cuts, uint64_t n_chunks, const uint64_t* 
                        uint32_t* status, void* stream);
 
 /*
- * One batch of the streaming front end as a single enqueue with NO host read (BASELINE.json configs[4]
+ * The streaming front end: one batch as a single enqueue with NO host read (BASELINE.json configs[4]
  * "hipGraph-captured per-batch pipeline"; the reference's batch loop README.md:1519-1580: request block -> L2 -> per chunk
- * L3 lookup/insert -> L4 probe -> delta or full).  The batch's bytes are already at data[state[0] .. + batch_bytes); every
- * stage takes its ranges from `state` (DEVICE u64[16]: [0] byte offset, [1] chunks so far, [2] chunks of this batch (out),
- * [3] stored chunks so far, [4] stored chunks of this batch (out), [5] stream bytes so far, [6] stream bytes of this batch
- * (out), [7] sticky status: bit0 chunk capacity, bit1 stored-chunk capacity, bit2 L2 status (the chain cannot run a batch twice: a batch with more cut candidates than its fixed list holds — see hmse_l2_cdc — is
- * refused here, no cut of it is published; such bytes go through hmse_l2_cdc with the larger workspace), bit3 malformed exchange row,
- * bit4 workspace not initialised (hmse_stream_workspace_init), bit5 state block inconsistent (one rank and [8] != [1]: e.g. a stream resumed with the
- * version-1 state layout, whose [8] is 0), bits 8.. DEFLATE status; [8] chunks of ALL ranks so far (== [1] for one rank), [9] chunks of all ranks in this batch (out),
- * [10] global index of this rank's first chunk of the batch (out)), grids and workspace are sized for batch_bytes / min_size
- * chunks, and the call ends by advancing [0], [1], [3], [5], [8] — so the chain can be captured into a hipGraph once per batch
- * size and replayed for every batch.  Once [7] is non-zero the failing batch has been dropped and every later call is a no-op
- * (counters frozen at the last good batch): nothing is ever appended to an index that is no longer consistent.  Appends to the
- * per-chunk arrays of the stream (cuts_all, digests_all, first_occ, refcount, uniq_all, sig_all, band_keys, base_all, kind_all,
- * stream_off_all), to the persistent L3 table / L4 band tables, and writes the batch's DEFLATE streams to out[state[5] ..).
+ * L3 lookup/insert -> L4 probe -> delta or full).
+ *
+ * The state block: DEVICE u64[HMSE_SB_WORDS], read by every stage of the chain instead of host-side counts and advanced by the chain
+ * itself, so a batch can be captured into a hipGraph once per batch size and replayed for every batch.  The caller writes it whole
+ * before the first batch (a fresh stream: zeros) and reads it when it wants the counts.
+ */
+enum {
+  HMSE_SB_OFF    = 0,   /* byte offset of this batch in the resident data (= bytes ingested before it) */
+  HMSE_SB_N_OLD  = 1,   /* this rank's chunks before this batch */
+  HMSE_SB_N_NEW  = 2,   /* ... of this batch (out) */
+  HMSE_SB_U_OLD  = 3,   /* this rank's stored chunks before this batch (a gstate block: of ALL ranks) */
+  HMSE_SB_U_NEW  = 4,   /* ... of this batch (out) */
+  HMSE_SB_S_OLD  = 5,   /* stream bytes before this batch */
+  HMSE_SB_S_NEW  = 6,   /* ... of this batch (out) */
+  HMSE_SB_STATUS = 7,   /* sticky HMSE_STREAM_ST_* bits */
+  /* the global chunk order of a multi-rank stream (batch, rank, local index); with one rank these mirror N_OLD / N_NEW */
+  HMSE_SB_G_OLD  = 8,   /* chunks of ALL ranks before this batch (one rank: must equal [HMSE_SB_N_OLD]) */
+  HMSE_SB_G_NEW  = 9,   /* ... in this batch (out) */
+  HMSE_SB_G_BASE = 10,  /* global index of this rank's first chunk of this batch (out; a gstate block: global STORED index of its first new chunk) */
+  HMSE_SB_WORDS  = 16
+};
+/*
+ * state[HMSE_SB_STATUS].  Once it is non-zero the failing batch has been dropped and every later call is a no-op (counters frozen at
+ * the last good batch): nothing is ever appended to an index that is no longer consistent.
+ */
+#define HMSE_STREAM_ST_CHUNK_CAP    1ull    /* chunk capacity (max_chunks, max_chunks_g, or more chunks than the batch's cut list holds) */
+#define HMSE_STREAM_ST_STORED_CAP   2ull    /* stored-chunk capacity (max_unique, g->max_stored_g) */
+#define HMSE_STREAM_ST_L2           4ull    /* L2 status: the chain cannot run a batch twice, so a batch with more cut candidates than its fixed
+                                               list holds (see hmse_l2_cdc) is refused, no cut of it is published; such bytes go through hmse_l2_cdc
+                                               with the larger workspace */
+#define HMSE_STREAM_ST_ROW          8ull    /* malformed exchange row (a count beyond the row's capacity) */
+#define HMSE_STREAM_ST_WS_INIT      16ull   /* workspace not initialised (hmse_stream_workspace_init) */
+#define HMSE_STREAM_ST_STATE        32ull   /* state block inconsistent: one rank and [HMSE_SB_G_OLD] != [HMSE_SB_N_OLD], e.g. a stream resumed with
+                                               the version-1 state layout, whose word 8 is 0 */
+#define HMSE_STREAM_ST_PUSH_REFUSED 64ull   /* set by the CALLER: a piece refused by its feeder */
+#define HMSE_STREAM_ST_SIG_ROW      128ull  /* more new stored chunks than a signature row holds */
+#define HMSE_STREAM_ST_DEFLATE_SHIFT 8      /* bits 8..: the status word of hmse_l1_deflate, shifted */
+#define HMSE_STREAM_ST_HOST_REFUSED (1ull << 16)  /* set by the CALLER: a refusal on the host between two phases of a batch */
+
+/*
+ * What is fixed for a stream's life: its persistent arrays and their capacities.  The struct is read on the HOST, during the call only;
+ * its pointers are copied into kernel arguments, so a captured graph keeps them.  The arrays must outlive the stream (and every graph
+ * captured from it), the struct need not.  Each entry point names the fields it requires; a required field that is NULL, a struct_size
+ * other than sizeof(hmse_stream), a world outside 1..256 or rank >= world is HMSE_EINVAL before anything is enqueued.
+ * With several ranks (hmse_stream_piece_*), cuts / uniq / sig / band_keys / base / lsh_tables / kind / stream_off / out are THIS RANK's
+ * arrays (chunk ids are local) and digests / first_occ / refcount / l3_table the GLOBAL ones, identical on every rank.  Of the arrays
+ * the first batch reads cuts[0] and stream_off[0], the start of the first chunk and of the first record: 0.
+ */
+typedef struct hmse_stream {
+  uint32_t struct_size, world, rank, reserved;   /* one-rank stream: world 1, rank 0 */
+  uint64_t* state;                               /* u64[HMSE_SB_WORDS] */
+  uint64_t* cuts;        uint64_t max_chunks;    /* u64[max_chunks + 1]: chunk bounds (stream offsets) */
+  uint64_t* gidx;                                /* local -> global chunk index; may be NULL when world == 1 */
+  uint8_t*  digests;     uint64_t max_chunks_g;  /* u8[max_chunks_g][32], global chunk order; one rank: == max_chunks */
+  uint64_t* first_occ;   uint32_t* refcount;     /* [max_chunks_g], as hmse_l3_index_update */
+  uint32_t* l3_table;    uint64_t l3_slots;      /* hmse_l3_index_slots(max_chunks_g), cleared by hmse_l3_index_update(n_old = n_new = 0) */
+  uint64_t* uniq;        uint64_t max_unique;    /* u64[max_unique]: chunk ids of the stored chunks, ascending */
+  uint32_t* sig;         uint32_t* band_keys;    int64_t* base;   /* [max_unique][128], [max_unique][bands], [max_unique]: stored slot of the dictionary, -1 none */
+  uint32_t* lsh_tables;  uint64_t lsh_slots;     /* u32[bands][lsh_slots], hmse_l4_lsh_slots(max_unique), cleared by hmse_l4_lsh_update(n_old = n_new = 0) */
+  uint8_t*  kind;        uint64_t* stream_off;   /* u8[max_unique], u64[max_unique + 1] */
+  uint8_t*  out;         uint64_t out_cap;       /* the DEFLATE streams, record k at out[stream_off[k] ..) */
+} hmse_stream;
+
+/*
+ * hmse_stream_batch: one batch of a ONE-RANK stream (s->world must be 1; requires every field of *s but gidx).  The batch's bytes are
+ * already at data[state[HMSE_SB_OFF] .. + batch_bytes); grids and workspace are sized for batch_bytes / min_size chunks, and the call
+ * ends by advancing the OFF, N_OLD, U_OLD, S_OLD and G_OLD words.  Appends to the per-chunk arrays of the stream, to the persistent L3
+ * table / L4 band tables, and writes the batch's DEFLATE streams to out[state[HMSE_SB_S_OLD] ..).
  * seg_off DEVICE u64[n_seg+1]: batch-local segment offsets.  ws: hmse_stream_batch_workspace_bytes(batch_bytes, cfg), prepared ONCE
  * with hmse_stream_workspace_init() and then handed to every batch of the stream unchanged: it holds the MinHash memo table, which
  * persists across the batches (a cache of a pure function of (shingle, cfg->seed_base); cleared per batch it cost every 1 GiB batch
- * its warm-up again).  A chain that finds the workspace untagged drops the batch with status bit4.
+ * its warm-up again).  A chain that finds the workspace untagged drops the batch with HMSE_STREAM_ST_WS_INIT.
  */
 uint64_t hmse_stream_batch_workspace_bytes(uint64_t batch_bytes, const hmse_cfg* cfg);
 int hmse_stream_workspace_init(void* ws, size_t ws_bytes, uint64_t batch_bytes, const hmse_cfg* cfg, void* stream);
 int hmse_stream_batch(uint8_t* data, uint64_t data_cap, uint64_t batch_bytes, const uint64_t* seg_off, uint32_t n_seg,
-                      const hmse_cfg* cfg, uint64_t* state, uint64_t* cuts_all, uint64_t max_chunks, uint8_t* digests_all,
-                      uint64_t* first_occ, uint32_t* refcount, uint32_t* l3_table, uint64_t l3_slots, uint64_t* uniq_all,
-                      uint64_t max_unique, uint32_t* sig_all, uint32_t* band_keys, int64_t* base_all, uint32_t* lsh_tables,
-                      uint64_t lsh_slots, uint8_t* kind_all, uint64_t* stream_off_all, uint8_t* out, uint64_t out_cap,
-                      void* ws, size_t ws_bytes, void* stream);
+                      const hmse_cfg* cfg, const hmse_stream* s, void* ws, size_t ws_bytes, void* stream);
 
 /*
  * The same chain for a stream that is sharded over several ranks (one process per GPU; BASELINE.json configs[4] "4 x 10 GB
@@ -351,25 +405,17 @@ int hmse_stream_batch(uint8_t* data, uint64_t data_cap, uint64_t batch_bytes, co
  *                that every rank's row has the same layout whatever its piece holds (a rank may get 0 bytes in the last batch)
  *   row          DEVICE u8[hmse_stream_row_bytes(cap_bytes)]: {u64 n_chunks, 24 B zero, n_chunks x 32 B digests, unused tail}
  *   rows         DEVICE u8[world][row bytes]: the all-gathered rows in rank order (world == 1: rows == row)
- *   cuts_all / uniq_all / sig_all / band_keys / base_all / kind_all / stream_off_all / out / lsh_tables: THIS RANK's arrays
- *                (chunk ids are local); gidx DEVICE u64[max local chunks]: global index of every local chunk (out; may be
- *                NULL when world == 1)
- *   digests_g / first_occ_g / refcount_g / l3_table: the GLOBAL arrays (max_chunks_g entries), identical on every rank
- *   state        as hmse_stream_batch: [1]..[6] count this rank's chunks / stored chunks / stream bytes, [8]..[10] the global ones
+ *   s            hmse_stream_piece_hash requires state and cuts; hmse_stream_piece_encode every field (gidx when world > 1).
+ *                state: N_OLD .. S_NEW count this rank's chunks / stored chunks / stream bytes, G_OLD .. G_BASE the global ones
  *   ws           hmse_stream_batch_workspace_bytes(cap_bytes, cfg); both phases of a batch take the SAME workspace
  * Both calls are stream-ordered and capturable; hmse_stream_batch == hash + encode with world 1 on the row in its workspace.
  */
 uint64_t hmse_stream_row_bytes(uint64_t cap_bytes, const hmse_cfg* cfg);
 int hmse_stream_piece_hash(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const uint64_t* seg_off,
-                           uint32_t n_seg, const hmse_cfg* cfg, uint64_t* state, uint64_t* cuts_all, uint64_t max_chunks,
-                           uint8_t* row, void* ws, size_t ws_bytes, void* stream);
+                           uint32_t n_seg, const hmse_cfg* cfg, const hmse_stream* s, uint8_t* row, void* ws, size_t ws_bytes,
+                           void* stream);
 int hmse_stream_piece_encode(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const hmse_cfg* cfg,
-                             uint64_t* state, const uint8_t* rows, uint32_t world, uint32_t rank, const uint64_t* cuts_all,
-                             uint64_t* gidx, uint8_t* digests_g, uint64_t max_chunks_g, uint64_t* first_occ_g,
-                             uint32_t* refcount_g, uint32_t* l3_table, uint64_t l3_slots, uint64_t* uniq_all,
-                             uint64_t max_unique, uint32_t* sig_all, uint32_t* band_keys, int64_t* base_all,
-                             uint32_t* lsh_tables, uint64_t lsh_slots, uint8_t* kind_all, uint64_t* stream_off_all,
-                             uint8_t* out, uint64_t out_cap, void* ws, size_t ws_bytes, void* stream);
+                             const hmse_stream* s, const uint8_t* rows, void* ws, size_t ws_bytes, void* stream);
 
 /*
  * Global L4 for a multi-rank stream as captured phases (round 4; SURVEY.md §8f-3: "cross-GPU base-chunk fetch over xGMI P2P for global L4
@@ -383,19 +429,26 @@ int hmse_stream_piece_encode(uint8_t* data, uint64_t data_cap, uint64_t piece_by
  *   -- all-gather of the signature rows (fixed size: hmse_stream_sig_row_bytes) --
  *   hmse_stream_piece_bases     sig rows -> global signature array + owner map -> global band tables -> for every new stored chunk of
  *                               this rank its dictionary: a chunk of this rank, or a REMOTE one -> request (owner, owner's stored slot);
- *                               g->req_counts[q] requests to rank q ([world] = total, [world + 1] = this rank's stored chunks including
- *                               this batch's: the bound of the slots a peer may ask of it now), g->req_slots grouped by owner
+ *                               g->req_counts[q] requests to rank q, then two more words (HMSE_GL4_REQ_*), g->req_slots grouped by owner
  *   -- the requested chunks are fetched (all-to-all; the caller writes the bytes behind its data and their bounds into
- *      cuts_all[g->ghost_chunk0 ..]: request j is chunk ghost_chunk0 + j) --
+ *      s->cuts[g->ghost_chunk0 ..]: request j is chunk ghost_chunk0 + j) --
  *   hmse_stream_piece_encode_g  DEFLATE of the new stored chunks with those dictionaries, tails, both state blocks advanced
- * gstate: DEVICE u64[16], word [3] = stored chunks of ALL ranks before this batch, [4] = of this batch (out), [10] = global stored index
- * of this rank's first new chunk (out).  Status bits as hmse_stream_batch, plus bit7: more new stored chunks than a signature row holds
- * (sig_cap is the worst-case chunk count of a piece, cap_bytes / min_size + segments + 2, so phase A's own bound fires first: a defence
- * against a row that another build wrote).  Bit6 (a piece refused by the caller's feeder) and bit16 (a refusal on the host between the
- * phases of a batch: the fetch of the remote dictionaries, the ghost area, a phase's return code) are set by the CALLER, before the next
- * phase is enqueued, to drop the batch through the chain instead of leaving the collectives alone.
+ * Required fields of *s: sign — state, cuts, digests, first_occ, refcount, l3_table, uniq, sig (gidx when world > 1); bases — state, uniq,
+ * band_keys, base (and s->world == g->world, s->rank == g->rank); encode_g — state, cuts, kind, stream_off, out.
+ * gstate: DEVICE u64[HMSE_SB_WORDS], word [HMSE_SB_U_OLD] = stored chunks of ALL ranks before this batch, [HMSE_SB_U_NEW] = of this batch
+ * (out), [HMSE_SB_G_BASE] = global stored index of this rank's first new chunk (out).  Status bits as hmse_stream_batch; HMSE_STREAM_ST_SIG_ROW
+ * is a defence against a row that another build wrote (sig_cap is the worst-case chunk count of a piece, cap_bytes / min_size + segments
+ * + 2, so phase A's own bound fires first).  HMSE_STREAM_ST_PUSH_REFUSED (a piece refused by the caller's feeder) and
+ * HMSE_STREAM_ST_HOST_REFUSED (a refusal on the host between the phases of a batch: the fetch of the remote dictionaries, the ghost area,
+ * a phase's return code) are set by the CALLER, before the next phase is enqueued, to drop the batch through the chain instead of
+ * leaving the collectives alone.
  * All arrays are the caller's; sizes in the struct.
  */
+enum {                       /* g->req_counts[world + ...], behind the per-rank counts */
+  HMSE_GL4_REQ_TOTAL  = 0,   /* requests of this batch to all ranks */
+  HMSE_GL4_REQ_STORED = 1,   /* this rank's stored chunks INCLUDING this batch's: the bound of the slots a peer may ask of it now */
+  HMSE_GL4_REQ_EXTRA  = 2
+};
 typedef struct hmse_gl4 {
   uint32_t struct_size, world, rank, reserved;
   uint64_t sig_cap;        /* hmse_stream_sig_cap(cap_bytes, cfg) */
@@ -410,21 +463,18 @@ typedef struct hmse_gl4 {
   uint64_t* g_local;       /* [max_stored_g] the owner's stored slot */
   uint64_t* ug;            /* [max_unique] this rank's stored chunks: global stored index (out, appended) */
   int64_t*  base_global;   /* [max_unique] this rank's stored chunks: base_g (out, appended) */
-  uint64_t* req_counts;    /* DEVICE u64[world + 2] (out) */
+  uint64_t* req_counts;    /* DEVICE u64[world + HMSE_GL4_REQ_EXTRA] (out) */
   uint64_t* req_slots;     /* DEVICE u64[cap chunks of a piece] (out) */
   uint64_t  ghost_chunk0;  /* chunk id of the batch's first fetched dictionary */
 } hmse_gl4;
 uint64_t hmse_stream_sig_cap(uint64_t cap_bytes, const hmse_cfg* cfg);
 uint64_t hmse_stream_sig_row_bytes(uint64_t cap_bytes, const hmse_cfg* cfg);
-int hmse_stream_piece_sign(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const hmse_cfg* cfg, uint64_t* state,
-                           const uint8_t* rows, uint32_t world, uint32_t rank, const uint64_t* cuts_all, uint64_t* gidx, uint8_t* digests_g,
-                           uint64_t max_chunks_g, uint64_t* first_occ_g, uint32_t* refcount_g, uint32_t* l3_table, uint64_t l3_slots,
-                           uint64_t* uniq_all, uint64_t max_unique, uint32_t* sig_all, uint8_t* sig_row, void* ws, size_t ws_bytes, void* stream);
-int hmse_stream_piece_bases(uint64_t cap_bytes, const hmse_cfg* cfg, uint64_t* state, const uint8_t* sig_rows, const hmse_gl4* g,
-                            const uint64_t* uniq_all, uint32_t* band_keys, int64_t* base_all, void* ws, size_t ws_bytes, void* stream);
-int hmse_stream_piece_encode_g(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const hmse_cfg* cfg, uint64_t* state,
-                               uint64_t* gstate, const uint64_t* cuts_all, uint8_t* kind_all, uint64_t* stream_off_all, uint8_t* out,
-                               uint64_t out_cap, void* ws, size_t ws_bytes, void* stream);
+int hmse_stream_piece_sign(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const hmse_cfg* cfg, const hmse_stream* s,
+                           const uint8_t* rows, uint8_t* sig_row, void* ws, size_t ws_bytes, void* stream);
+int hmse_stream_piece_bases(uint64_t cap_bytes, const hmse_cfg* cfg, const hmse_stream* s, const uint8_t* sig_rows, const hmse_gl4* g,
+                            void* ws, size_t ws_bytes, void* stream);
+int hmse_stream_piece_encode_g(uint8_t* data, uint64_t data_cap, uint64_t piece_bytes, uint64_t cap_bytes, const hmse_cfg* cfg,
+                               const hmse_stream* s, uint64_t* gstate, void* ws, size_t ws_bytes, void* stream);
 
 /*
  * Chunk manifest — the packed on-disk records, written on the GPU (README.md:1263-1270 ChunkIndex 40 B, 2182-2189

@@ -8,7 +8,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from hmse_amd import IngestConfig, corpus, stream_dist
+from hmse_amd import IngestConfig, corpus, ops, stream_dist
 
 variant = sys.argv[1] if len(sys.argv) > 1 else "base"
 dev = torch.device("cuda:0")
@@ -21,11 +21,11 @@ seg_off = s._graphs.entry(P).seg_off
 
 
 def A():
-    s._call_hash(P, seg_off)
+    ops.stream_piece_hash(s.data, P, s.cap_bytes, seg_off, cfg, s._stream_arrays(), s._row, s._ws)
 
 
 def B():
-    s._call_encode(P, s._row)
+    ops.stream_piece_encode(s.data, P, s.cap_bytes, cfg, s._stream_arrays(), s._row, s._ws)
 
 
 def check(tag, want_row, want_state):
