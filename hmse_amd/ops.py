@@ -19,7 +19,9 @@ STAGE_INFLATE, STAGE_ASSEMBLE, STAGE_MANIFEST = 16, 17, 18
 STAGE_GC_PLAN, STAGE_RECORD_GATHER = 24, 25
 STAGE_L4_INDEX, STAGE_L4_QUERY = 26, 27
 STAGE_SCRUB_RECORDS, STAGE_SCRUB_ATTRIBUTE = 28, 29
+STAGE_FIND_SCAN, STAGE_FIND_PLACE = 30, 31
 QUERY_EXCLUDE_SELF = 1
+FIND_MAX_PATTERNS, FIND_MAX_LEN, FIND_IGNORE_CASE = 32, 256, 1
 
 
 class HmseError(RuntimeError):
@@ -698,3 +700,99 @@ def scrub_attribute(status: torch.Tensor, dict_: torch.Tensor, ok: torch.Tensor,
                                              _ptr(out["ranges"]), _ptr(out["counts"]), ws.data_ptr(), ws.numel(), _stream())
     _check(rc, "hmse_scrub_attribute")
     return out
+
+
+def _find_bounds(pat: torch.Tensor, pat_off):
+    """The patterns' bounds as the HOST u32 array hmse_find_* read during the call."""
+    off = [int(v) for v in pat_off]
+    if len(off) < 1 or off[-1] > pat.numel() or any(v < 0 for v in off):
+        raise HmseError(-1, "find: pat_off does not lie inside pat")
+    return (C.c_uint32 * len(off))(*off), len(off) - 1
+
+
+def _find_hits(call, where: str, n_pat: int, hits_cap: int | None, dev):
+    """The calling convention hmse_find_scan and hmse_find_seams share: `call(hits, cap, meta, counts)` enqueues one; meta = [n_hits,
+    status].  hits_cap 0: count only; None: sized by a count-only call.  A list that ran out (status bit 0) is filled by ONE more call
+    with hits_cap = n_hits (as l2_cdc repeats with the larger candidate list).  -> (hits int64[n_hits], n_hits, counts int64[n_pat])."""
+    cap = hits_cap
+    for _ in range(3):
+        hits = _buf(max(int(cap or 0), 1), torch.int64, dev)
+        meta = _buf(2, torch.int64, dev, fill=0)      # [n_hits, status]
+        counts = _buf(n_pat, torch.int64, dev, fill=0)
+        _check(call(hits, int(cap or 0), meta, counts), where)
+        n_hits, status = (int(v) for v in meta.tolist())
+        status &= 0xFFFFFFFF
+        if status & 2:
+            raise HmseError(-1, f"{where}: inconsistent tables (device status {status:#x})")
+        if cap is None or (status & 1):
+            if cap is not None and cap >= n_hits:
+                break
+            cap = n_hits                              # exact: the second call cannot run out
+            if cap == 0:
+                return hits[:0], 0, counts
+            continue
+        return hits[:min(n_hits, int(cap))], n_hits, counts
+    raise HmseError(-2, f"{where}: the hit list ran out twice ({n_hits} hits, {cap} entries)")
+
+
+def find_scan(raw: torch.Tensor, raw_off: torch.Tensor, mult: torch.Tensor | None, pat: torch.Tensor, pat_off, ignore_case: bool = False,
+              hits_cap: int | None = None, raw_bytes: int | None = None):
+    """hmse_find_scan: every match of the patterns (`pat` uint8 on the device, `pat_off` host bounds) lying wholly inside one record
+    [raw_off[r], raw_off[r + 1]) of `raw`.  -> (hits int64[n] = position in raw << 8 | pattern, any order; n_hits; counts int64[P] =
+    per pattern the sum of mult[record] (int32, None: 1 each)).  hits_cap 0: count only (hits empty).  Replaces the read_store +
+    host bytes.find loop."""
+    for t, nm in ((raw, "raw"), (raw_off, "raw_off"), (pat, "pat")) + (((mult, "mult"),) if mult is not None else ()):
+        _require_gpu(t, nm)
+    n_rec = raw_off.numel() - 1
+    if n_rec < 0 or (mult is not None and mult.numel() != n_rec):
+        raise HmseError(-1, "find_scan: raw_off / mult do not match")
+    bounds, n_pat = _find_bounds(pat, pat_off)
+    nb = raw.numel() if raw_bytes is None else int(raw_bytes)
+    flags = FIND_IGNORE_CASE if ignore_case else 0
+    lib = _lib.hip_lib()
+    call = lambda hits, cap, meta, counts: lib.hmse_find_scan(_ptr(raw) if raw.numel() else None, nb, _ptr(raw_off), max(n_rec, 0), _ptr(mult),
+                                                              _ptr(pat), bounds, n_pat, flags, _ptr(hits) if cap else None, cap,
+                                                              meta.data_ptr(), _ptr(counts), meta.data_ptr() + 8, _stream())
+    return _find_hits(call, "hmse_find_scan", n_pat, hits_cap, raw_off.device)
+
+
+def find_seams(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, pat: torch.Tensor, pat_off,
+               ignore_case: bool = False, hits_cap: int | None = None):
+    """hmse_find_seams: the occurrences that start in a chunk and end behind it, read through the chunk map (`cuts` int64[n + 1],
+    `slot` int64[n]: the record of every chunk).  -> (hits int64[n] = corpus offset << 8 | pattern, any order; n_hits; counts)."""
+    for t, nm in ((raw, "raw"), (raw_off, "raw_off"), (cuts, "cuts"), (slot, "slot"), (pat, "pat")):
+        _require_gpu(t, nm)
+    n_chunks = slot.numel()
+    if cuts.numel() != n_chunks + 1 or raw_off.numel() < 1:
+        raise HmseError(-1, "find_seams: cuts / slot / raw_off do not match")
+    bounds, n_pat = _find_bounds(pat, pat_off)
+    flags = FIND_IGNORE_CASE if ignore_case else 0
+    lib = _lib.hip_lib()
+    keep = lambda t: _ptr(t) if t.numel() else None
+    call = lambda hits, cap, meta, counts: lib.hmse_find_seams(keep(raw), raw.numel(), _ptr(raw_off), raw_off.numel() - 1, _ptr(cuts), keep(slot),
+                                                               n_chunks, _ptr(pat), bounds, n_pat, flags, _ptr(hits) if cap else None, cap,
+                                                               meta.data_ptr(), _ptr(counts), meta.data_ptr() + 8, _stream())
+    return _find_hits(call, "hmse_find_seams", n_pat, hits_cap, cuts.device)
+
+
+def find_place(hits: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, chunk_out: torch.Tensor, n_out: int) -> torch.Tensor:
+    """hmse_find_place: the scan's hits, SORTED ascending, laid out at every chunk that maps to their record.  `chunk_out` int64
+    [n_chunks + 1]: exclusive prefix sum of the number of hits of record slot[k]; n_out = chunk_out[-1].  -> int64[n_out] =
+    corpus offset << 8 | pattern, ascending."""
+    for t, nm in ((hits, "hits"), (raw_off, "raw_off"), (cuts, "cuts"), (slot, "slot"), (chunk_out, "chunk_out")):
+        _require_gpu(t, nm)
+    n_chunks = slot.numel()
+    if cuts.numel() != n_chunks + 1 or chunk_out.numel() != n_chunks + 1 or raw_off.numel() < 1:
+        raise HmseError(-1, "find_place: cuts / slot / chunk_out do not match")
+    dev = cuts.device
+    out = _buf(max(int(n_out), 1), torch.int64, dev)
+    status = _buf(1, torch.int32, dev, fill=0)
+    keep = lambda t: _ptr(t) if t.numel() else None
+    rc = _lib.hip_lib().hmse_find_place(keep(hits), hits.numel(), _ptr(raw_off), raw_off.numel() - 1, _ptr(cuts), keep(slot), n_chunks,
+                                        _ptr(chunk_out), _ptr(out) if n_out else None, int(n_out), _ptr(status), _stream())
+    _check(rc, "hmse_find_place")
+    st = int(status.item())
+    if st:
+        raise HmseError(-2 if st == 1 else -1, f"hmse_find_place device status {st:#x}"
+                        + (": inconsistent tables" if st & 2 else ": chunk_out[-1] exceeds the output"))
+    return out[:int(n_out)]

@@ -78,7 +78,11 @@ enum {
   HMSE_STAGE_L4_QUERY      = 27,
   /* scrub of a store (hmse_scrub_records: no workspace, 0 bytes; hmse_scrub_attribute: n = max(records, chunks)) */
   HMSE_STAGE_SCRUB_RECORDS   = 28,
-  HMSE_STAGE_SCRUB_ATTRIBUTE = 29
+  HMSE_STAGE_SCRUB_ATTRIBUTE = 29,
+  /* exact search (hmse_find_*: no workspace, 0 bytes).  As profile slots 30 and 31 are shared with the DELTA encode kernels of
+   * hmse_l1_deflate (see hmse_profile_read): reset them before timing a search */
+  HMSE_STAGE_FIND_SCAN       = 30,
+  HMSE_STAGE_FIND_PLACE      = 31
 };
 
 /* layer-enable mask == the reference's ablation matrix / degradation modes
@@ -670,13 +674,79 @@ int hmse_scrub_attribute(uint64_t n, const uint8_t* status, const int64_t* dict,
                          void* ws, size_t ws_bytes, void* stream);
 
 /*
+ * Exact search (hmse_amd/find.py): where does a byte string occur in a store?  Replaces what the reference layout leaves a user to do:
+ * read the store back (README.md:1621-1675 per chunk), move the corpus to the host and loop over bytes.find() — which decodes and scans
+ * every duplicate chunk once per occurrence.  Here a pattern is looked for once per stored RECORD (hmse_find_scan over the decoded
+ * records of hmse_l1_inflate), every hit then belongs to every chunk that maps to that record (hmse_find_place), and only the
+ * max(m) - 1 bytes in front of each chunk boundary are looked at through the chunk map (hmse_find_seams).
+ *
+ * Patterns: pat DEVICE u8[pat_off[n_pat]], pattern j = pat[pat_off[j] .. pat_off[j+1]); pat_off is a HOST u32[n_pat+1], read during
+ * the call only (as the hmse_stream descriptor is): the lengths size the launch and are refused on the host.  1 <= n_pat <=
+ * HMSE_FIND_MAX_PATTERNS, 1 <= length <= HMSE_FIND_MAX_LEN; equal patterns may repeat, each is answered on its own.  flags:
+ * HMSE_FIND_IGNORE_CASE compares after folding the ASCII letters A-Z to a-z on both sides (every other value, >= 0x80 included,
+ * compares exactly).  Overlapping occurrences all count.  HMSE_EINVAL before anything is cleared or launched: n_pat of 0 or above 32,
+ * a pattern length of 0 or above 256, unknown flag bits, a NULL pointer to a non-empty array.
+ * A hit is one u64: position << 8 | pattern index.
+ *   hits    DEVICE u64[hits_cap] or NULL (hits == NULL or hits_cap == 0: count only); written in any order, up to min(n_hits, hits_cap)
+ *   n_hits  DEVICE u64[1]: the exact number of hits, also when it exceeds hits_cap
+ *   counts  DEVICE u64[n_pat]
+ *   status  DEVICE u32[1]: bit0 = the hit list ran out (hits_cap > 0 and n_hits > hits_cap; n_hits and counts are still exact),
+ *           bit1 = inconsistent tables: raw_off, cuts or chunk_out descending, raw_off[n_rec] > raw_bytes, slot[k] >= n_rec, a chunk
+ *           whose length is not its record's.  With bit1 nothing is read through the tables, no hit is written, n_hits and counts are 0.
+ * No workspace.  The three calls are stream-ordered, allocate nothing and never sync.
+ */
+#define HMSE_FIND_MAX_PATTERNS 32
+#define HMSE_FIND_MAX_LEN 256
+#define HMSE_FIND_IGNORE_CASE 1u
+
+/*
+ * Scan: every match lying wholly inside ONE record [raw_off[r], raw_off[r+1]).  Records that are neighbours in raw are not neighbours
+ * in the corpus: a match across raw_off[r+1] is no hit.  A record may have any length (the position in raw carries it).
+ *   raw     DEVICE u8[raw_bytes], any alignment;  raw_off DEVICE u64[n_rec+1] ascending, raw_off[n_rec] <= raw_bytes
+ *   mult    DEVICE u32[n_rec] or NULL: counts[j] = sum over the hits of pattern j of mult[record] (NULL: 1 each) — with the number of
+ *           chunks that map to each record, the in-record occurrences in the corpus
+ *   hits    position = offset in raw
+ */
+int hmse_find_scan(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* raw_off, uint64_t n_rec, const uint32_t* mult,
+                   const uint8_t* pat, const uint32_t* pat_off, uint32_t n_pat, uint32_t flags, uint64_t* hits,
+                   uint64_t hits_cap, uint64_t* n_hits, uint64_t* counts, uint32_t* status, void* stream);
+
+/*
+ * Seams: chunk k covers corpus bytes [cuts[k], cuts[k+1]); corpus byte p of chunk c is raw[raw_off[slot[c]] + p - cuts[c]].  An
+ * occurrence (o, m) that starts in chunk k is a seam hit of k iff o + m > cuts[k+1]; it may run over any number of following chunks
+ * (tiny and empty ones) and must end at or before N = cuts[n_chunks].  In-record hits of all chunks plus seam hits of all chunks are
+ * every occurrence exactly once.
+ *   cuts    DEVICE u64[n_chunks+1];  slot DEVICE u64[n_chunks]: the record of every chunk (a POINTER's: its target's)
+ *   hits    position = corpus offset;  counts[j] = seam hits of pattern j
+ */
+int hmse_find_seams(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* raw_off, uint64_t n_rec, const uint64_t* cuts,
+                    const uint64_t* slot, uint64_t n_chunks, const uint8_t* pat, const uint32_t* pat_off, uint32_t n_pat,
+                    uint32_t flags, uint64_t* hits, uint64_t hits_cap, uint64_t* n_hits, uint64_t* counts, uint32_t* status,
+                    void* stream);
+
+/*
+ * Place: the scan's hits, sorted ascending, laid out in the corpus.  For every chunk k in corpus order and every hit h of record
+ * slot[k] in ascending order: (cuts[k] + pos(h) - raw_off[slot[k]]) << 8 | pat(h) — ascending by corpus offset, then pattern.
+ *   hits      DEVICE u64[n_hits] ascending
+ *   chunk_out DEVICE u64[n_chunks+1]: exclusive prefix sum of the chunks' hit counts (the number of hits of record slot[k]);
+ *             chunk k's hits go to out[chunk_out[k] ..)
+ *   out       DEVICE u64[out_cap], written up to chunk_out[n_chunks]
+ *   status    DEVICE u32[1]: bit0 = chunk_out[n_chunks] > out_cap, bit1 = inconsistent tables (as above, or chunk_out is not the
+ *             count of its records' hits in the list)
+ */
+int hmse_find_place(const uint64_t* hits, uint64_t n_hits, const uint64_t* raw_off, uint64_t n_rec, const uint64_t* cuts,
+                    const uint64_t* slot, uint64_t n_chunks, const uint64_t* chunk_out, uint64_t* out, uint64_t out_cap,
+                    uint32_t* status, void* stream);
+
+/*
  * Diagnostics (bench.py's roofline leg): when enabled, every entry point brackets its DOMINANT
  * kernel launch with a HIP event pair on the caller's stream.  hmse_profile_read() waits for the
  * recorded events (a host sync — never call it inside a capture), adds their durations to the
  * stage's running total and returns it.  Off by default; not part of the data path.
  * Slots: the HMSE_STAGE_* ids (0..31); the six DEFLATE match-kernel size classes report in slots 8..13
  * (S, SG2, SG3, B, S2, SG), their dictionary jobs in 18..23, and the two encode-kernel instantiations in 14 and 15 (FULL
- * records) and 30 and 31 (DELTA records) (hmse_amd/csrc/l1_deflate.hip).
+ * records) and 30 and 31 (DELTA records) (hmse_amd/csrc/l1_deflate.hip); hmse_find_scan also reports in 30, hmse_find_seams and
+ * hmse_find_place in 31.
  * hmse_profile_counter(): work counted on the device while profiling is on — the DEFLATE match kernels add the TOKENS they
  * write to their slot (8..13, 18..23), the encode kernels the tokens they read (14, 15, 30, 31):
  * bench.py's algorithmic bytes come from these counts, not from an assumed token density.  A host sync; diagnostics only.
