@@ -101,6 +101,7 @@ extern "C" size_t hmse_workspace_bytes(int stage, uint64_t n, const hmse_cfg* cf
     case HMSE_STAGE_L4_INDEX: return hmse_l4_index_workspace_bytes_impl(n);
     case HMSE_STAGE_L4_QUERY: return hmse_l4_query_workspace_bytes_impl(n, cfg);
     case HMSE_STAGE_SCRUB_RECORDS: return 0;      /* takes no workspace */
+    case HMSE_STAGE_SYNC_MATCH: return 0;         /* takes no workspace */
     case HMSE_STAGE_SCRUB_ATTRIBUTE: return hmse_scrub_attribute_workspace_bytes_impl(n, n);
     default: return 0;
   }

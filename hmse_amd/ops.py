@@ -20,6 +20,7 @@ STAGE_GC_PLAN, STAGE_RECORD_GATHER = 24, 25
 STAGE_L4_INDEX, STAGE_L4_QUERY = 26, 27
 STAGE_SCRUB_RECORDS, STAGE_SCRUB_ATTRIBUTE = 28, 29
 STAGE_FIND_SCAN, STAGE_FIND_PLACE = 30, 31
+STAGE_SYNC_MATCH = 19
 QUERY_EXCLUDE_SELF = 1
 FIND_MAX_PATTERNS, FIND_MAX_LEN, FIND_IGNORE_CASE = 32, 256, 1
 
@@ -460,6 +461,30 @@ def record_gather(src0: torch.Tensor, src1: torch.Tensor | None, src_off: torch.
     if n and int(status.item()):
         raise HmseError(-2, "hmse_record_gather: a record lies outside its source or the destination")
     return out
+
+
+def sync_match(a: torch.Tensor, a_off: torch.Tensor, a_len: torch.Tensor, b: torch.Tensor, b_off: torch.Tensor, b_len: torch.Tensor,
+               cand: torch.Tensor):
+    """hmse_sync_match: same[k] = 1 iff record k of a — bytes [a_off[k], + a_len[k]) — and record cand[k] of b are byte-identical
+    (cand < 0: no candidate, 0).  a, b uint8; a_off, b_off int64; a_len, b_len int32; cand int64.  Returns (same uint8[n], status):
+    status bit 0 = a candidate >= len(b_off) or a record that reaches outside its blob (same is 0 there; nothing outside is read)."""
+    for t, nm in ((a, "a"), (a_off, "a_off"), (a_len, "a_len"), (b, "b"), (b_off, "b_off"), (b_len, "b_len"), (cand, "cand")):
+        _require_gpu(t, nm)
+    for t, nm, dt in ((a, "a", torch.uint8), (b, "b", torch.uint8), (a_off, "a_off", torch.int64), (b_off, "b_off", torch.int64),
+                      (a_len, "a_len", torch.int32), (b_len, "b_len", torch.int32), (cand, "cand", torch.int64)):
+        if t.dtype != dt:
+            raise HmseError(-1, f"sync_match: {nm} must be {dt}")
+    n, n_b = cand.numel(), b_off.numel()
+    if a_off.numel() != n or a_len.numel() != n or b_len.numel() != n_b:
+        raise HmseError(-1, "sync_match: a_off / a_len / cand or b_off / b_len do not match")
+    dev = cand.device
+    same = _buf(n, torch.uint8, dev)
+    status = _buf(1, torch.int32, dev, fill=0)
+    keep = lambda t: _ptr(t) if t.numel() else None
+    rc = _lib.hip_lib().hmse_sync_match(keep(a), a.numel(), keep(a_off), keep(a_len), n, keep(b), b.numel(), keep(b_off), keep(b_len), n_b,
+                                        keep(cand), keep(same), _ptr(status), _stream())
+    _check(rc, "hmse_sync_match")
+    return same, int(status.item())
 
 
 def stream_batch_workspace_bytes(batch_bytes: int, cfg: IngestConfig) -> int:

@@ -70,6 +70,9 @@ enum {
   HMSE_STAGE_L1_INFLATE    = 16,
   HMSE_STAGE_READ_ASSEMBLE = 17,
   HMSE_STAGE_MANIFEST_PACK = 18,
+  /* replication (hmse_sync_match: no workspace, 0 bytes).  As a profile slot 19 is shared with the dictionary jobs of one DEFLATE
+   * match-kernel class (see hmse_profile_read): reset it before timing a comparison */
+  HMSE_STAGE_SYNC_MATCH    = 19,
   /* garbage collection of dropped segments (hmse_gc_plan; hmse_record_gather's profiling slot) */
   HMSE_STAGE_GC_PLAN       = 24,
   HMSE_STAGE_RECORD_GATHER = 25,
@@ -739,6 +742,29 @@ int hmse_find_place(const uint64_t* hits, uint64_t n_hits, const uint64_t* raw_o
                     uint32_t* status, void* stream);
 
 /*
+ * Replication (hmse_amd/sync.py): the byte proof behind a digest join of two stores.  Record k of store a (the wanted one) has the
+ * stored stream a[a_off[k] .. a_off[k] + a_len[k]) and the candidate cand[k], a record of store b (the one the replica holds) with the
+ * stream b[b_off[c] .. b_off[c] + b_len[c]).  Equal digests say the decoded chunks are equal, not the streams: the same chunk may be
+ * FULL in one store and DELTA in the other, or DELTA against another dictionary.
+ *   same[k] = 1 iff 0 <= cand[k] < n_b, a_len[k] == b_len[cand[k]] and the two byte ranges are equal (length 0 on both sides: 1).
+ *   same[k] is WRITTEN FOR EVERY k < n: the caller clears nothing.
+ *   cand[k] < 0: no candidate — same[k] = 0, no status bit, record k's range is not looked at.
+ *   cand[k] >= n_b, or a range of either side that reaches outside its blob (off > bytes or len > bytes - off): same[k] = 0 and
+ *   status bit 0; nothing outside a[0 .. a_bytes) and b[0 .. b_bytes) is read.  Ranges are checked before lengths are compared;
+ *   unequal lengths give 0 without reading a stream byte.
+ *   a, b    DEVICE u8, any alignment (lba_unit may be 1: the two sides are misaligned independently); NULL only with 0 bytes
+ *   a_off   DEVICE u64[n];  a_len DEVICE u32[n];  b_off DEVICE u64[n_b];  b_len DEVICE u32[n_b] (NULL only with n_b == 0)
+ *   cand    DEVICE i64[n];  same DEVICE u8[n];  status DEVICE u32[1]
+ * n == 0 clears the status word and returns HMSE_OK.  HMSE_EINVAL before anything is cleared or launched: status NULL, n >= 2^33,
+ * with n > 0 a NULL pointer to a non-empty array.  No workspace (hmse_workspace_bytes(HMSE_STAGE_SYNC_MATCH, ...) is 0);
+ * stream-ordered, allocates nothing, never syncs.  One wavefront per record, 16 bytes per lane and side and trip; the record is left
+ * at the first 1 KiB trip that differs.  Reads at most 2 x the compared bytes.
+ */
+int hmse_sync_match(const uint8_t* a, uint64_t a_bytes, const uint64_t* a_off, const uint32_t* a_len, uint64_t n, const uint8_t* b,
+                    uint64_t b_bytes, const uint64_t* b_off, const uint32_t* b_len, uint64_t n_b, const int64_t* cand, uint8_t* same,
+                    uint32_t* status, void* stream);
+
+/*
  * Diagnostics (bench.py's roofline leg): when enabled, every entry point brackets its DOMINANT
  * kernel launch with a HIP event pair on the caller's stream.  hmse_profile_read() waits for the
  * recorded events (a host sync — never call it inside a capture), adds their durations to the
@@ -746,7 +772,7 @@ int hmse_find_place(const uint64_t* hits, uint64_t n_hits, const uint64_t* raw_o
  * Slots: the HMSE_STAGE_* ids (0..31); the six DEFLATE match-kernel size classes report in slots 8..13
  * (S, SG2, SG3, B, S2, SG), their dictionary jobs in 18..23, and the two encode-kernel instantiations in 14 and 15 (FULL
  * records) and 30 and 31 (DELTA records) (hmse_amd/csrc/l1_deflate.hip); hmse_find_scan also reports in 30, hmse_find_seams and
- * hmse_find_place in 31.
+ * hmse_find_place in 31, hmse_sync_match in 19.
  * hmse_profile_counter(): work counted on the device while profiling is on — the DEFLATE match kernels add the TOKENS they
  * write to their slot (8..13, 18..23), the encode kernels the tokens they read (14, 15, 30, 31):
  * bench.py's algorithmic bytes come from these counts, not from an assumed token density.  A host sync; diagnostics only.
