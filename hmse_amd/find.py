@@ -15,6 +15,10 @@ Definitions (tests/find_ref.py restates them in plain Python):
   * result: counts int64[P], and in CSR form ptr int64[P + 1], offsets int64[ptr[P]] — ascending per pattern, no offset twice.
 Sorting, prefix sums and searchsorted go through torch (plumbing, as SimilarityIndex.locate does); the byte work runs in the HIP kernels
 of hmse_amd/csrc/find.hip.  There is no CPU path.
+
+A whole dictionary (up to 2^20 distinct patterns) is compiled once into a PatternSet and answered by StoreFinder.count_set / find_set with
+ONE scan and ONE seam pass (hmse_amd/csrc/findset.hip; include/hmse.h hmse_findset_*): the same definitions, the same Found.  count and
+find do not route there.
 """
 from __future__ import annotations
 
@@ -28,6 +32,7 @@ from .read import StoreReader
 
 MAX_PATTERN_LEN = ops.FIND_MAX_LEN
 GROUP = ops.FIND_MAX_PATTERNS      # patterns per launch; more are answered in groups
+HMSE_FINDSET_MAX_PATTERNS = ops.FINDSET_MAX_PATTERNS     # distinct patterns of a PatternSet
 
 
 @dataclass
@@ -59,6 +64,82 @@ def pack_patterns(patterns):
         parts.append(b)
         off.append(off[-1] + len(b))
     return np.frombuffer(b"".join(parts), np.uint8), off
+
+
+class PatternSet:
+    """A dictionary of patterns compiled once for StoreFinder.count_set / find_set (include/hmse.h `hmse_findset`), usable against any
+    number of stores and finders.  Accepts and refuses what pack_patterns does.  Equal patterns (after folding, when ignore_case) are
+    stored once; `index` maps the caller's pattern j to its unique pattern and the results are expanded back through it.
+
+    The unique patterns of 4 bytes or more are keyed by their first four bytes (u32, little endian), sorted by (h(key), key, length,
+    bytes) with h(key) = key * 0x9E3779B1 mod 2^32 and stored back to back (upat / uoff / ukey / uid); `dir` (u32[2^b + 1], 2^b >= 2 U)
+    maps the top b bits of h to their range of the sorted list and `bitmap` has bit (h >> 13) for every key.  Built on the host with
+    sorts and searchsorted only: deterministic.  The unique patterns of 1..3 bytes have no four-byte key; they are kept aside
+    (`short_ids`, `short_patterns`) and answered by the grouped kernels, 32 per launch.  device=None keeps the numpy arrays only."""
+
+    def __init__(self, patterns, ignore_case: bool = False, device=None):
+        flat, off = pack_patterns(patterns)
+        self.ignore_case = bool(ignore_case)
+        self.n_patterns = len(off) - 1
+        blob = flat.tobytes()
+        if self.ignore_case:
+            blob = blob.lower()
+        seen, uniq, index = {}, [], np.zeros(self.n_patterns, np.int64)
+        for j in range(self.n_patterns):
+            b = blob[off[j]: off[j + 1]]
+            u = seen.get(b)
+            if u is None:
+                u = seen[b] = len(uniq)
+                uniq.append(b)
+            index[j] = u
+        if len(uniq) > HMSE_FINDSET_MAX_PATTERNS:
+            raise ValueError(f"find: {len(uniq)} distinct patterns; a PatternSet holds up to HMSE_FINDSET_MAX_PATTERNS = {HMSE_FINDSET_MAX_PATTERNS}")
+        self.n_unique = len(uniq)
+        self.index = index                                                       # int64 [P]: unique pattern of the caller's pattern j
+        self.unique = uniq                                                       # the unique patterns (folded when ignore_case)
+        self.short_ids = np.array([u for u, b in enumerate(uniq) if len(b) < ops.FINDSET_MIN_LEN], np.int64)
+        self.short_patterns = [uniq[u] for u in self.short_ids]
+        long_ids = np.array([u for u, b in enumerate(uniq) if len(b) >= ops.FINDSET_MIN_LEN], np.int64)
+        key = np.array([int.from_bytes(uniq[u][:4], "little") for u in long_ids], np.uint64)
+        h = (key * np.uint64(ops.FINDSET_HASH)) & np.uint64(0xFFFFFFFF)
+        hl, kl, pl = h.tolist(), key.tolist(), [uniq[u] for u in long_ids]
+        order = sorted(range(len(pl)), key=lambda i: (hl[i], kl[i], len(pl[i]), pl[i]))
+        order = np.array(order, np.int64)
+        n = len(order)
+        self.n_entries = n
+        self.uid = long_ids[order].astype(np.uint32)
+        self.ukey = key[order].astype(np.uint32)
+        ents = [uniq[u] for u in self.uid]
+        self.uoff = np.zeros(n + 1, np.uint32)
+        self.uoff[1:] = np.cumsum([len(b) for b in ents], dtype=np.int64)
+        self.upat = np.frombuffer(b"".join(ents), np.uint8).copy()
+        self.max_len = max([len(b) for b in ents], default=0)
+        self.dir_bits = max(1, int(2 * n - 1).bit_length()) if n else 1          # 2^b >= 2 n
+        hs = h[order]
+        self.dir = np.searchsorted(hs >> np.uint64(32 - self.dir_bits), np.arange((1 << self.dir_bits) + 1, dtype=np.uint64), "left").astype(np.uint32)
+        bit = (hs >> np.uint64(32 - ops.FINDSET_BITMAP_BITS)).astype(np.int64)
+        self.bitmap = np.zeros(1 << (ops.FINDSET_BITMAP_BITS - 5), np.uint32)
+        np.bitwise_or.at(self.bitmap, bit >> 5, (np.uint32(1) << (bit & 31).astype(np.uint32)))
+        self.dev = None if device is None else torch.device(device)
+        self.set = None
+        self.resident_bytes = 0
+        if self.dev is not None:
+            t = lambda a: torch.from_numpy(a.view(np.int32 if a.dtype == np.uint32 else a.dtype).copy()).to(self.dev)
+            self.set = ops.FindSet(t(self.upat), t(self.uoff), t(self.ukey), t(self.uid), t(self.dir), t(self.bitmap), self.n_unique,
+                                   self.dir_bits, self.max_len, self.ignore_case)
+            self.index_d = torch.from_numpy(index).to(self.dev)
+            self.short_ids_d = torch.from_numpy(self.short_ids).to(self.dev)
+            self.short_pat = torch.from_numpy(np.frombuffer(b"".join(self.short_patterns), np.uint8).copy()).to(self.dev)
+            self.resident_bytes = sum(x.numel() * x.element_size() for x in (self.set.upat, self.set.uoff, self.set.ukey, self.set.uid, self.set.dir,
+                                                                              self.set.bitmap, self.index_d, self.short_ids_d, self.short_pat))
+
+    def short_groups(self):
+        """The bounds of the 1..3-byte patterns inside short_pat, 32 per group: [(first short pattern, bounds list)]."""
+        off = [0]
+        for b in self.short_patterns:
+            off.append(off[-1] + len(b))
+        n = len(self.short_patterns)
+        return [(g, off[g: min(g + GROUP, n) + 1]) for g in range(0, n, GROUP)]
 
 
 class StoreFinder:
@@ -137,6 +218,97 @@ class StoreFinder:
         if offsets.numel() != total:
             raise ops.HmseError(-1, f"find: {offsets.numel()} occurrences located, {total} counted")
         return Found(ptr, offsets, counts)
+
+
+    # ------------------------------------------------------------------ a whole dictionary in one pass
+    def _set_of(self, pset: PatternSet):
+        if not isinstance(pset, PatternSet):
+            raise ValueError("find: count_set / find_set take a PatternSet (PatternSet(patterns, ignore_case, device))")
+        if pset.dev is None or pset.dev != self.dev:
+            raise ValueError(f"find: the PatternSet lives on {pset.dev}, the finder on {self.dev}")
+        return pset
+
+    def _count_unique(self, ps: PatternSet):
+        """-> (occurrences int64[n_unique], in-record hits of the set's scan, its seam hits, [(group, in-record, seam) of the short ones])."""
+        counts = torch.zeros(ps.n_unique, dtype=torch.int64, device=self.dev)
+        n_scan = n_seam = 0
+        if ps.n_entries:
+            _, n_scan, c_scan = ops.findset_scan(self.raw, self.raw_off, self.mult, ps.set, hits_cap=0)
+            _, n_seam, c_seam = ops.findset_seams(self.raw, self.raw_off, self.cuts, self.slot, ps.set, hits_cap=0)
+            counts += c_scan + c_seam
+        short = []
+        for g, off in ps.short_groups():
+            c, a, b = self._count_group(ps.short_pat, off, ps.ignore_case)
+            counts[ps.short_ids_d[g: g + len(off) - 1]] = c
+            short.append((g, off, a, b))
+        return counts, n_scan, n_seam, short
+
+    def count_set(self, pset: PatternSet) -> torch.Tensor:
+        """Occurrences per pattern of the set, int64[P] on the device: one scan and one seam pass for all patterns of 4 bytes or more
+        (plus two count-only launches per 32 distinct patterns of 1..3 bytes); nothing is materialised."""
+        ps = self._set_of(pset)
+        if ps.n_patterns == 0 or self.n_records == 0:
+            return torch.zeros(ps.n_patterns, dtype=torch.int64, device=self.dev)
+        return self._count_unique(ps)[0][ps.index_d]
+
+    def find_set(self, pset: PatternSet, max_hits: int = 1 << 24) -> Found:
+        """Every occurrence of every pattern of the set.  Counts first: ValueError naming the total and the ten largest counts if the
+        total exceeds max_hits."""
+        ps = self._set_of(pset)
+        dev, n = self.dev, ps.n_patterns
+        if n == 0 or self.n_records == 0:
+            z = torch.zeros(n, dtype=torch.int64, device=dev)
+            return Found(torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int64, device=dev), z)
+        cu, n_scan, n_seam, short = self._count_unique(ps)
+        counts = cu[ps.index_d]
+        total = int(counts.sum())
+        if total > int(max_hits):
+            top = torch.topk(counts, min(10, n))
+            worst = ", ".join(f"pattern {int(j)}: {int(c)}" for c, j in zip(top.values.tolist(), top.indices.tolist()))
+            raise ValueError(f"find: {total} occurrences exceed max_hits = {max_hits}; the largest counts: {worst}")
+        B, ID = ops.FINDSET_ID_BITS, (1 << ops.FINDSET_ID_BITS) - 1
+        keys = []                                                               # unique pattern << 40 | corpus offset
+        if n_scan:
+            hits, _, c_scan = ops.findset_scan(self.raw, self.raw_off, self.mult, ps.set, hits_cap=n_scan)
+            hits = torch.sort(hits)[0]                                           # by position in raw, then id (positions stay below 2^39)
+            rec_lo = torch.searchsorted(hits, self.raw_off << B)                 # first hit of every record
+            per_chunk = (rec_lo[1:] - rec_lo[:-1])[self.slot]
+            chunk_out = torch.zeros(self.slot.numel() + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(per_chunk, 0, out=chunk_out[1:])
+            h = ops.findset_place(hits, self.raw_off, self.cuts, self.slot, chunk_out, int(c_scan.sum()))
+            keys.append(((h & ID) << 40) | (h >> B))
+        if n_seam:
+            h = ops.findset_seams(self.raw, self.raw_off, self.cuts, self.slot, ps.set, hits_cap=n_seam)[0]
+            keys.append(((h & ID) << 40) | (h >> B))
+        for g, off, a, b in short:                                               # the 1..3-byte patterns: the grouped kernels
+            ids = ps.short_ids_d[g: g + len(off) - 1]
+            if a:
+                hits, _, c_scan = ops.find_scan(self.raw, self.raw_off, self.mult, ps.short_pat, off, ps.ignore_case, hits_cap=a)
+                hits = torch.sort(hits)[0]
+                rec_lo = torch.searchsorted(hits, self.raw_off << 8)
+                per_chunk = (rec_lo[1:] - rec_lo[:-1])[self.slot]
+                chunk_out = torch.zeros(self.slot.numel() + 1, dtype=torch.int64, device=dev)
+                torch.cumsum(per_chunk, 0, out=chunk_out[1:])
+                h = ops.find_place(hits, self.raw_off, self.cuts, self.slot, chunk_out, int(c_scan.sum()))
+                keys.append((ids[h & 0xFF] << 40) | (h >> 8))
+            if b:
+                h = ops.find_seams(self.raw, self.raw_off, self.cuts, self.slot, ps.short_pat, off, ps.ignore_case, hits_cap=b)[0]
+                keys.append((ids[h & 0xFF] << 40) | (h >> 8))
+        found = torch.sort(torch.cat(keys))[0] & ((1 << 40) - 1) if keys else torch.zeros(0, dtype=torch.int64, device=dev)
+        if found.numel() != int(cu.sum()):
+            raise ops.HmseError(-1, f"find: {found.numel()} occurrences located, {int(cu.sum())} counted")
+        # expand the unique patterns' lists back to the caller's patterns
+        ptr_u = torch.zeros(ps.n_unique + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(cu, 0, out=ptr_u[1:])
+        ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(counts, 0, out=ptr[1:])
+        src = torch.repeat_interleave(ptr_u[:-1][ps.index_d] - ptr[:-1], counts) + torch.arange(total, dtype=torch.int64, device=dev)
+        return Found(ptr, found[src], counts)
+
+
+def find_set(store, patterns, device, ignore_case: bool = False, max_hits: int = 1 << 24, verify: bool = True) -> Found:
+    """One-off form of StoreFinder(store, device, verify).find_set(PatternSet(patterns, ignore_case, device), max_hits)."""
+    return StoreFinder(store, device, verify).find_set(PatternSet(patterns, ignore_case, device), max_hits)
 
 
 def find(store, patterns, device, ignore_case: bool = False, max_hits: int = 1 << 24, verify: bool = True) -> Found:

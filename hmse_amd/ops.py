@@ -8,6 +8,7 @@ on a non-zero status — there is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 
 import torch
 
@@ -23,6 +24,7 @@ STAGE_FIND_SCAN, STAGE_FIND_PLACE = 30, 31
 STAGE_SYNC_MATCH = 19
 QUERY_EXCLUDE_SELF = 1
 FIND_MAX_PATTERNS, FIND_MAX_LEN, FIND_IGNORE_CASE = 32, 256, 1
+FINDSET_MAX_PATTERNS, FINDSET_MIN_LEN, FINDSET_ID_BITS, FINDSET_BITMAP_BITS, FINDSET_HASH = 1 << 20, 4, 24, 19, 0x9E3779B1
 
 
 class HmseError(RuntimeError):
@@ -819,5 +821,93 @@ def find_place(hits: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, sl
     st = int(status.item())
     if st:
         raise HmseError(-2 if st == 1 else -1, f"hmse_find_place device status {st:#x}"
+                        + (": inconsistent tables" if st & 2 else ": chunk_out[-1] exceeds the output"))
+    return out[:int(n_out)]
+
+
+@dataclass
+class FindSet:
+    """The device arrays and the header of a compiled pattern set (include/hmse.h `hmse_findset`; built by find.PatternSet)."""
+    upat: torch.Tensor           # uint8: the entries' bytes back to back
+    uoff: torch.Tensor           # int32 [n + 1]
+    ukey: torch.Tensor           # int32 [n]: the first four bytes of every entry (bit pattern of the u32)
+    uid: torch.Tensor            # int32 [n]: the id reported for every entry
+    dir: torch.Tensor            # int32 [2^dir_bits + 1]
+    bitmap: torch.Tensor         # int32 [16384]
+    n_ids: int
+    dir_bits: int
+    max_len: int
+    ignore_case: bool
+
+    def header(self) -> "_lib.HmseFindset":
+        n = self.ukey.numel()
+        keep = lambda t: _ptr(t) if t.numel() else None
+        return _lib.HmseFindset(C.sizeof(_lib.HmseFindset), FIND_IGNORE_CASE if self.ignore_case else 0, n, int(self.n_ids), int(self.dir_bits),
+                                int(self.max_len), self.upat.numel(), keep(self.upat), keep(self.uoff), keep(self.ukey), keep(self.uid),
+                                keep(self.dir), keep(self.bitmap))
+
+
+def _findset_args(fs: FindSet):
+    for t, nm in ((fs.upat, "upat"), (fs.uoff, "uoff"), (fs.ukey, "ukey"), (fs.uid, "uid"), (fs.dir, "dir"), (fs.bitmap, "bitmap")):
+        _require_gpu(t, nm)
+    n = fs.ukey.numel()
+    if n and (fs.uoff.numel() != n + 1 or fs.uid.numel() != n or fs.dir.numel() != (1 << int(fs.dir_bits)) + 1
+              or fs.bitmap.numel() != 1 << (FINDSET_BITMAP_BITS - 5) or any(t.element_size() != 4 for t in (fs.uoff, fs.ukey, fs.uid, fs.dir, fs.bitmap))):
+        raise HmseError(-1, "findset: the set's arrays do not match its header")
+    return fs.header(), FIND_IGNORE_CASE if fs.ignore_case else 0
+
+
+def findset_scan(raw: torch.Tensor, raw_off: torch.Tensor, mult: torch.Tensor | None, fs: FindSet, hits_cap: int | None = None,
+                 raw_bytes: int | None = None):
+    """hmse_findset_scan: every match of the set's patterns lying wholly inside one record of `raw` (find_scan's contract).
+    -> (hits int64[n] = position in raw << 24 | id, any order; n_hits; counts int64[n_ids] weighted by mult)."""
+    for t, nm in ((raw, "raw"), (raw_off, "raw_off")) + (((mult, "mult"),) if mult is not None else ()):
+        _require_gpu(t, nm)
+    n_rec = raw_off.numel() - 1
+    if n_rec < 0 or (mult is not None and mult.numel() != n_rec):
+        raise HmseError(-1, "findset_scan: raw_off / mult do not match")
+    hdr, flags = _findset_args(fs)
+    nb = raw.numel() if raw_bytes is None else int(raw_bytes)
+    lib = _lib.hip_lib()
+    call = lambda hits, cap, meta, counts: lib.hmse_findset_scan(_ptr(raw) if raw.numel() else None, nb, _ptr(raw_off), max(n_rec, 0), _ptr(mult),
+                                                                 C.byref(hdr), flags, _ptr(hits) if cap else None, cap, meta.data_ptr(),
+                                                                 _ptr(counts) if fs.n_ids else None, meta.data_ptr() + 8, _stream())
+    return _find_hits(call, "hmse_findset_scan", int(fs.n_ids), hits_cap, raw_off.device)
+
+
+def findset_seams(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, fs: FindSet, hits_cap: int | None = None):
+    """hmse_findset_seams: the set's occurrences that start in a chunk and end behind it (find_seams' contract).
+    -> (hits int64[n] = corpus offset << 24 | id, any order; n_hits; counts int64[n_ids])."""
+    for t, nm in ((raw, "raw"), (raw_off, "raw_off"), (cuts, "cuts"), (slot, "slot")):
+        _require_gpu(t, nm)
+    n_chunks = slot.numel()
+    if cuts.numel() != n_chunks + 1 or raw_off.numel() < 1:
+        raise HmseError(-1, "findset_seams: cuts / slot / raw_off do not match")
+    hdr, flags = _findset_args(fs)
+    lib = _lib.hip_lib()
+    keep = lambda t: _ptr(t) if t.numel() else None
+    call = lambda hits, cap, meta, counts: lib.hmse_findset_seams(keep(raw), raw.numel(), _ptr(raw_off), raw_off.numel() - 1, _ptr(cuts), keep(slot),
+                                                                  n_chunks, C.byref(hdr), flags, _ptr(hits) if cap else None, cap, meta.data_ptr(),
+                                                                  _ptr(counts) if fs.n_ids else None, meta.data_ptr() + 8, _stream())
+    return _find_hits(call, "hmse_findset_seams", int(fs.n_ids), hits_cap, cuts.device)
+
+
+def findset_place(hits: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, chunk_out: torch.Tensor, n_out: int) -> torch.Tensor:
+    """hmse_findset_place: find_place for the hit word position << 24 | id.  -> int64[n_out] = corpus offset << 24 | id, ascending."""
+    for t, nm in ((hits, "hits"), (raw_off, "raw_off"), (cuts, "cuts"), (slot, "slot"), (chunk_out, "chunk_out")):
+        _require_gpu(t, nm)
+    n_chunks = slot.numel()
+    if cuts.numel() != n_chunks + 1 or chunk_out.numel() != n_chunks + 1 or raw_off.numel() < 1:
+        raise HmseError(-1, "findset_place: cuts / slot / chunk_out do not match")
+    dev = cuts.device
+    out = _buf(max(int(n_out), 1), torch.int64, dev)
+    status = _buf(1, torch.int32, dev, fill=0)
+    keep = lambda t: _ptr(t) if t.numel() else None
+    rc = _lib.hip_lib().hmse_findset_place(keep(hits), hits.numel(), _ptr(raw_off), raw_off.numel() - 1, _ptr(cuts), keep(slot), n_chunks,
+                                           _ptr(chunk_out), _ptr(out) if n_out else None, int(n_out), _ptr(status), _stream())
+    _check(rc, "hmse_findset_place")
+    st = int(status.item())
+    if st:
+        raise HmseError(-2 if st == 1 else -1, f"hmse_findset_place device status {st:#x}"
                         + (": inconsistent tables" if st & 2 else ": chunk_out[-1] exceeds the output"))
     return out[:int(n_out)]

@@ -742,6 +742,75 @@ int hmse_find_place(const uint64_t* hits, uint64_t n_hits, const uint64_t* raw_o
                     uint32_t* status, void* stream);
 
 /*
+ * Dictionary search (hmse_amd/find.py PatternSet): the question of hmse_find_* for a whole SET of patterns in one pass — up to
+ * HMSE_FINDSET_MAX_PATTERNS of HMSE_FINDSET_MIN_LEN..HMSE_FIND_MAX_LEN bytes each.  hmse_find_scan's work per position grows with the
+ * patterns and its ABI ends at 32 of them; here the set is compiled ONCE into the structure below and a position whose four-byte
+ * window no pattern starts with costs one hash and one bit lookup, whatever the size of the set.  (Patterns of 1..3 bytes have no
+ * four-byte key: they are not part of a set and go through hmse_find_*.)
+ *
+ * The compiled set is plain device arrays, so any caller can build it (hmse_amd/find.py does, on the host, with sorts only):
+ *   key(p)  = the first four bytes of pattern p as a little-endian u32;  h(key) = key * HMSE_FINDSET_HASH mod 2^32
+ *   entries = the n_entries patterns sorted by (h(key), key, length, bytes); entry i is upat[uoff[i] .. uoff[i+1]), ukey[i] = its key,
+ *             uid[i] < n_ids = the id reported for it (any map: several entries may not share an id unless the caller wants their
+ *             hits and counts merged)
+ *   dir     = u32[2^dir_bits + 1]: the entries whose h has the top dir_bits bits c are dir[c] .. dir[c+1]; dir[0] = 0,
+ *             dir[2^dir_bits] = n_entries.  1 <= dir_bits <= 21; 2^dir_bits >= 2 * n_entries keeps a cell at half an entry on average
+ *   bitmap  = u32[2^(HMSE_FINDSET_BITMAP_BITS - 5)] (64 KiB): bit (h(key) >> 13) is set for every entry (the scan keeps it in LDS)
+ *   flags   = HMSE_FIND_IGNORE_CASE iff the patterns were folded (A-Z -> a-z) before they were keyed and sorted; a call's flags
+ *             must equal the set's
+ *   max_len >= every entry's length (it sizes the seam launch)
+ * Nothing has a capacity: any number of entries may share a key or a cell — the walk gets longer, no pattern is dropped.
+ * The kernels do not trust the set: a validate kernel runs first in every call and sets status bit 1 (nothing is then read through the
+ * set or the tables, no hit is written, n_hits and counts are 0) for a directory that descends or does not cover [0, n_entries), an
+ * id >= n_ids, a byte range that descends, leaves upat or is not MIN_LEN..max_len long, a key that is not the first four bytes of its
+ * pattern (or not folded in a folded set), an entry outside its directory cell or without its bit in the bitmap.  The header (a HOST
+ * struct, read during the call only) is checked on the host: HMSE_EINVAL, before anything is cleared or launched, for struct_size,
+ * unknown flag bits, flags that differ from the call's, n_entries or n_ids above HMSE_FINDSET_MAX_PATTERNS, and with n_entries > 0:
+ * n_ids == 0, dir_bits outside 1..21, max_len outside 4..256, pat_bytes outside 4 .. 256 bytes per entry, a NULL array.
+ * n_entries == 0 is a legal, empty set (the arrays may be NULL): the outputs are cleared, nothing is launched.
+ *
+ * A hit is one u64: position << HMSE_FINDSET_ID_BITS | id.  Ids are below 2^20, positions below 2^40: raw_bytes >= 2^40 is
+ * HMSE_EINVAL; cuts lives on the device, so cuts[n_chunks] >= 2^40 is status bit 1 (the calls never sync).
+ *   hits, hits_cap, n_hits, status as for hmse_find_*;  counts DEVICE u64[n_ids] (NULL only with n_ids == 0)
+ * The three calls mirror hmse_find_scan / _seams / _place argument by argument, with (set, flags) in the place of
+ * (pat, pat_off, n_pat, flags); scan and seams, in-record and seam hits, mult and the chunk map mean what they mean there.
+ * hmse_findset_place is hmse_find_place for this hit word (hits sorted ascending; out = corpus offset << 24 | id).
+ * No workspace; stream-ordered, allocate nothing, never sync.  Profile slots: hmse_findset_scan reports in 30, hmse_findset_seams
+ * and hmse_findset_place in 31 — the slots hmse_find_* and the DELTA encode kernels already share (see Diagnostics below).
+ */
+#define HMSE_FINDSET_MAX_PATTERNS (1u << 20)
+#define HMSE_FINDSET_MIN_LEN 4
+#define HMSE_FINDSET_ID_BITS 24
+#define HMSE_FINDSET_BITMAP_BITS 19
+#define HMSE_FINDSET_HASH 0x9E3779B1u
+
+typedef struct hmse_findset {
+  uint32_t struct_size;   /* sizeof(hmse_findset) */
+  uint32_t flags;         /* HMSE_FIND_IGNORE_CASE: the patterns are folded */
+  uint32_t n_entries;
+  uint32_t n_ids;
+  uint32_t dir_bits;
+  uint32_t max_len;
+  uint64_t pat_bytes;     /* bytes of upat */
+  const uint8_t* upat;    /* DEVICE u8[pat_bytes] */
+  const uint32_t* uoff;   /* DEVICE u32[n_entries + 1] */
+  const uint32_t* ukey;   /* DEVICE u32[n_entries] */
+  const uint32_t* uid;    /* DEVICE u32[n_entries] */
+  const uint32_t* dir;    /* DEVICE u32[2^dir_bits + 1] */
+  const uint32_t* bitmap; /* DEVICE u32[16384] */
+} hmse_findset;
+
+int hmse_findset_scan(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* raw_off, uint64_t n_rec, const uint32_t* mult,
+                      const hmse_findset* set, uint32_t flags, uint64_t* hits, uint64_t hits_cap, uint64_t* n_hits,
+                      uint64_t* counts, uint32_t* status, void* stream);
+int hmse_findset_seams(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* raw_off, uint64_t n_rec, const uint64_t* cuts,
+                       const uint64_t* slot, uint64_t n_chunks, const hmse_findset* set, uint32_t flags, uint64_t* hits,
+                       uint64_t hits_cap, uint64_t* n_hits, uint64_t* counts, uint32_t* status, void* stream);
+int hmse_findset_place(const uint64_t* hits, uint64_t n_hits, const uint64_t* raw_off, uint64_t n_rec, const uint64_t* cuts,
+                       const uint64_t* slot, uint64_t n_chunks, const uint64_t* chunk_out, uint64_t* out, uint64_t out_cap,
+                       uint32_t* status, void* stream);
+
+/*
  * Replication (hmse_amd/sync.py): the byte proof behind a digest join of two stores.  Record k of store a (the wanted one) has the
  * stored stream a[a_off[k] .. a_off[k] + a_len[k]) and the candidate cand[k], a record of store b (the one the replica holds) with the
  * stream b[b_off[c] .. b_off[c] + b_len[c]).  Equal digests say the decoded chunks are equal, not the streams: the same chunk may be
@@ -772,7 +841,7 @@ int hmse_sync_match(const uint8_t* a, uint64_t a_bytes, const uint64_t* a_off, c
  * Slots: the HMSE_STAGE_* ids (0..31); the six DEFLATE match-kernel size classes report in slots 8..13
  * (S, SG2, SG3, B, S2, SG), their dictionary jobs in 18..23, and the two encode-kernel instantiations in 14 and 15 (FULL
  * records) and 30 and 31 (DELTA records) (hmse_amd/csrc/l1_deflate.hip); hmse_find_scan also reports in 30, hmse_find_seams and
- * hmse_find_place in 31, hmse_sync_match in 19.
+ * hmse_find_place in 31, hmse_sync_match in 19; hmse_findset_scan reports in 30 as well, hmse_findset_seams and hmse_findset_place in 31.
  * hmse_profile_counter(): work counted on the device while profiling is on — the DEFLATE match kernels add the TOKENS they
  * write to their slot (8..13, 18..23), the encode kernels the tokens they read (14, 15, 30, 31):
  * bench.py's algorithmic bytes come from these counts, not from an assumed token density.  A host sync; diagnostics only.
