@@ -19,6 +19,13 @@ of hmse_amd/csrc/find.hip.  There is no CPU path.
 A whole dictionary (up to 2^20 distinct patterns) is compiled once into a PatternSet and answered by StoreFinder.count_set / find_set with
 ONE scan and ONE seam pass (hmse_amd/csrc/findset.hip; include/hmse.h hmse_findset_*): the same definitions, the same Found.  count and
 find do not route there.
+
+From a hit to its line: StoreFinder.lines turns the offsets of a Found into the extents of the lines (delimited records) they lie in,
+with context and counts, StoreFinder.text returns their bytes, grep = lines(find(...)) (hmse_amd/csrc/lines.hip; include/hmse.h
+hmse_lines_* has the definitions, tests/lines_ref.py restates them in plain Python).  The walk goes through the chunk map on the device:
+nothing is read back, and a record that several chunks map to is looked at with the neighbours of each of its places.  Out of scope:
+delimiters of more than one byte, CR stripping, merging the overlapping context of neighbouring hits (grep's "--" groups), regular
+expressions.
 """
 from __future__ import annotations
 
@@ -40,6 +47,31 @@ class Found:
     ptr: torch.Tensor            # int64 [P + 1]: pattern j's occurrences are offsets[ptr[j]:ptr[j + 1]]
     offsets: torch.Tensor        # int64 corpus offsets, ascending per pattern
     counts: torch.Tensor         # int64 [P] occurrences per pattern
+
+
+@dataclass
+class Lines:
+    ptr: torch.Tensor            # int64 [P + 1]: pattern j's extents are [ptr[j] : ptr[j + 1])
+    start: torch.Tensor          # int64 [L] corpus offsets; per pattern ascending by (start, end), no (start, end) pair twice
+    end: torch.Tensor            # int64 [L]
+    flags: torch.Tensor          # uint8 [L]  HMSE_LINES_START_CUT | HMSE_LINES_END_CUT (of any of the extent's occurrences)
+    hits: torch.Tensor           # int64 [L]  occurrences of the pattern that fell into this extent
+    counts: torch.Tensor         # int64 [P]  extents per pattern (with before = after = 0 and no cut: matching lines, grep -c)
+
+
+HMSE_LINES_START_CUT, HMSE_LINES_END_CUT, HMSE_LINES_MAX_REACH = ops.LINES_START_CUT, ops.LINES_END_CUT, ops.LINES_MAX_REACH
+
+
+def _lines_args(delim, before, after, reach):
+    """The arguments lines and grep share -> (delimiter byte value, before, after, reach); ValueError before any device work."""
+    if isinstance(delim, str) or not isinstance(delim, (bytes, bytearray, memoryview)) or len(bytes(delim)) != 1:
+        raise ValueError(f"lines: delim is exactly one byte (bytes of length 1), got {delim!r}")
+    before, after, reach = int(before), int(after), int(reach)
+    if before < 0 or after < 0:
+        raise ValueError(f"lines: before = {before} and after = {after} must not be negative")
+    if not 1 <= reach <= HMSE_LINES_MAX_REACH:
+        raise ValueError(f"lines: reach = {reach} lies outside 1..HMSE_LINES_MAX_REACH = {HMSE_LINES_MAX_REACH}")
+    return bytes(delim)[0], min(before, 0xFFFFFFFF), min(after, 0xFFFFFFFF), reach
 
 
 def pack_patterns(patterns):
@@ -220,6 +252,86 @@ class StoreFinder:
         return Found(ptr, offsets, counts)
 
 
+    # ------------------------------------------------------------------ from a hit to its line
+    def lines(self, found, delim: bytes = b"\n", before: int = 0, after: int = 0, reach: int = 1 << 16) -> Lines:
+        """The extents of the lines the occurrences lie in (module docstring; include/hmse.h hmse_lines_extent): per occurrence the
+        line it lies in with `before` lines in front and `after` behind, looking at most `reach` bytes each way; per pattern the
+        distinct (start, end) pairs, ascending, with the number of occurrences that gave each.  `found`: a Found, or an int64 device
+        tensor of corpus offsets taken as one pattern (any order, equal ones count).  ONE hmse_lines_extent call over all offsets; the
+        grouping is torch sorts.  ValueError for a delim that is not one byte, a negative before / after, a reach outside
+        1..HMSE_LINES_MAX_REACH, an offset that is not below n_bytes."""
+        d, before, after, reach = _lines_args(delim, before, after, reach)
+        if isinstance(found, Found):
+            offsets, counts = found.offsets, found.counts
+        elif isinstance(found, torch.Tensor):
+            offsets, counts = found.reshape(-1), None
+        else:
+            raise ValueError(f"lines: found is a Found or an int64 tensor of offsets, got a {type(found).__name__}")
+        dev = self.dev
+        if offsets.dtype != torch.int64 or offsets.device != self.raw.device or (counts is not None and counts.device != self.raw.device):
+            raise ValueError(f"lines: the offsets are {offsets.dtype} on {offsets.device}; they are int64 on the finder's device {self.raw.device}")
+        n = offsets.numel()
+        if counts is None:
+            counts = torch.full((1,), n, dtype=torch.int64, device=dev)
+        P = counts.numel()
+        if int(counts.sum()) != n:
+            raise ValueError(f"lines: found.counts sum to {int(counts.sum())}, found.offsets has {n} entries")
+        z = lambda k, dt=torch.int64: torch.zeros(k, dtype=dt, device=dev)
+        if n == 0:
+            return Lines(z(P + 1), z(0), z(0), z(0, torch.uint8), z(0), z(P))
+        if self.n_bytes == 0:
+            raise ValueError(f"lines: offset {int(offsets[0])} is not below n_bytes = 0")
+        start, end, flags, st = ops.lines_extent(self.raw, self.raw_off, self.cuts, self.slot, offsets.contiguous(), d, before, after, reach)
+        if st & 1:
+            bad = offsets[(flags & ops.LINES_BAD) != 0]
+            raise ValueError(f"lines: offset {int(bad[0])} is not below n_bytes = {self.n_bytes} ({bad.numel()} of {n} offsets are not)")
+        pat = torch.repeat_interleave(torch.arange(P, dtype=torch.int64, device=dev), counts)
+        order = torch.sort(end, stable=True)[1]                                  # by (pattern, start, end): three stable sorts
+        order = order[torch.sort(start[order], stable=True)[1]]
+        order = order[torch.sort(pat[order], stable=True)[1]]
+        pat, start, end, flags = pat[order], start[order], end[order], flags[order]
+        new = torch.ones(n, dtype=torch.bool, device=dev)
+        new[1:] = (pat[1:] != pat[:-1]) | (start[1:] != start[:-1]) | (end[1:] != end[:-1])
+        first = torch.nonzero(new).reshape(-1)
+        L = first.numel()
+        gid = torch.cumsum(new, 0) - 1
+        hits = torch.diff(first, append=torch.full((1,), n, dtype=torch.int64, device=dev))
+        cut = lambda bit: (z(L).index_add_(0, gid, (flags & bit).to(torch.int64)) > 0).to(torch.uint8) * bit
+        per = torch.bincount(pat[first], minlength=P)
+        ptr = z(P + 1)
+        torch.cumsum(per, 0, out=ptr[1:])
+        return Lines(ptr, start[first], end[first], cut(ops.LINES_START_CUT) | cut(ops.LINES_END_CUT), hits, per)
+
+    def text(self, lines, max_bytes: int = 1 << 30):
+        """The bytes of every extent back to back -> (uint8 tensor, int64 off[L + 1]: extent i is bytes[off[i] : off[i + 1]]).  `lines`:
+        a Lines, or a (start, end) pair of int64 device tensors (any ranges of the corpus; they may overlap and be empty).  One
+        hmse_lines_gather call.  ValueError naming the total if it exceeds max_bytes."""
+        if isinstance(lines, Lines):
+            start, end = lines.start, lines.end
+        elif isinstance(lines, (tuple, list)) and len(lines) == 2 and all(isinstance(t, torch.Tensor) for t in lines):
+            start, end = (t.reshape(-1) for t in lines)
+        else:
+            raise ValueError(f"text: lines is a Lines or a (start, end) pair of tensors, got a {type(lines).__name__}")
+        if start.dtype != torch.int64 or end.dtype != torch.int64 or start.numel() != end.numel() or start.device != end.device or start.device != self.raw.device:
+            raise ValueError(f"text: start and end are int64 tensors of one length on the finder's device {self.raw.device}")
+        n, dev = start.numel(), self.dev
+        off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        if n == 0:
+            return torch.zeros(0, dtype=torch.uint8, device=dev), off
+        if bool((end < start).any()):
+            raise ValueError("text: an extent ends in front of its start")
+        torch.cumsum(end - start, 0, out=off[1:])
+        total = int(off[-1])
+        if total > int(max_bytes):
+            raise ValueError(f"text: the extents hold {total} bytes, which exceeds max_bytes = {max_bytes}")
+        return ops.lines_gather(self.raw, self.raw_off, self.cuts, self.slot, start.contiguous(), end.contiguous(), off, total), off
+
+    def grep(self, patterns, ignore_case: bool = False, delim: bytes = b"\n", before: int = 0, after: int = 0, reach: int = 1 << 16,
+             max_hits: int = 1 << 24) -> Lines:
+        """lines(find(patterns, ignore_case, max_hits), delim, before, after, reach): per pattern the lines that hold it."""
+        _lines_args(delim, before, after, reach)
+        return self.lines(self.find(patterns, ignore_case, max_hits), delim, before, after, reach)
+
     # ------------------------------------------------------------------ a whole dictionary in one pass
     def _set_of(self, pset: PatternSet):
         if not isinstance(pset, PatternSet):
@@ -314,3 +426,10 @@ def find_set(store, patterns, device, ignore_case: bool = False, max_hits: int =
 def find(store, patterns, device, ignore_case: bool = False, max_hits: int = 1 << 24, verify: bool = True) -> Found:
     """One-off form of StoreFinder(store, device, verify).find(patterns, ignore_case, max_hits)."""
     return StoreFinder(store, device, verify).find(patterns, ignore_case, max_hits)
+
+
+def grep(store, patterns, device, ignore_case: bool = False, delim: bytes = b"\n", before: int = 0, after: int = 0, reach: int = 1 << 16,
+         max_hits: int = 1 << 24, verify: bool = True) -> Lines:
+    """One-off form of StoreFinder(store, device, verify).grep(patterns, ignore_case, delim, before, after, reach, max_hits)."""
+    _lines_args(delim, before, after, reach)
+    return StoreFinder(store, device, verify).grep(patterns, ignore_case, delim, before, after, reach, max_hits)

@@ -24,6 +24,7 @@ STAGE_FIND_SCAN, STAGE_FIND_PLACE = 30, 31
 STAGE_SYNC_MATCH = 19
 QUERY_EXCLUDE_SELF = 1
 FIND_MAX_PATTERNS, FIND_MAX_LEN, FIND_IGNORE_CASE = 32, 256, 1
+LINES_START_CUT, LINES_END_CUT, LINES_BAD, LINES_MAX_REACH = 1, 2, 128, 1 << 24
 FINDSET_MAX_PATTERNS, FINDSET_MIN_LEN, FINDSET_ID_BITS, FINDSET_BITMAP_BITS, FINDSET_HASH = 1 << 20, 4, 24, 19, 0x9E3779B1
 
 
@@ -822,6 +823,63 @@ def find_place(hits: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, sl
     if st:
         raise HmseError(-2 if st == 1 else -1, f"hmse_find_place device status {st:#x}"
                         + (": inconsistent tables" if st & 2 else ": chunk_out[-1] exceeds the output"))
+    return out[:int(n_out)]
+
+
+def _lines_tables(where: str, raw, raw_off, cuts, slot, more):
+    for t, nm in ((raw, "raw"), (raw_off, "raw_off"), (cuts, "cuts"), (slot, "slot")) + more:
+        _require_gpu(t, nm)
+    for t, nm in ((raw_off, "raw_off"), (cuts, "cuts"), (slot, "slot")) + more:
+        if t.dtype != torch.int64:
+            raise HmseError(-1, f"{where}: {nm} must be torch.int64 (the bits of the u64 array)")
+    if raw.dtype != torch.uint8:
+        raise HmseError(-1, f"{where}: raw must be torch.uint8")
+    if cuts.numel() != slot.numel() + 1 or raw_off.numel() < 1:
+        raise HmseError(-1, f"{where}: cuts / slot / raw_off do not match")
+
+
+def lines_extent(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, pos: torch.Tensor, delim: int = 0x0A,
+                 before: int = 0, after: int = 0, reach: int = 1 << 16):
+    """hmse_lines_extent: for every corpus offset pos[i] the extent [start, end) of the line it lies in, with `before` lines in front
+    and `after` behind, looking at most `reach` bytes each way (include/hmse.h has the definitions).  The tables are find_seams'.
+    -> (start int64[n], end int64[n], flags uint8[n] = LINES_START_CUT | LINES_END_CUT, or LINES_BAD with start = end = 0 for a
+    pos[i] >= cuts[-1]; status: bit 0 = some position was bad).  Inconsistent tables (status bit 1) raise HmseError."""
+    _lines_tables("lines_extent", raw, raw_off, cuts, slot, ((pos, "pos"),))
+    n, dev = pos.numel(), cuts.device
+    start, end, flags = _buf(n, torch.int64, dev), _buf(n, torch.int64, dev), _buf(n, torch.uint8, dev)
+    status = _buf(1, torch.int32, dev, fill=0)
+    keep = lambda t: _ptr(t) if t.numel() else None
+    rc = _lib.hip_lib().hmse_lines_extent(keep(raw), raw.numel(), _ptr(raw_off), raw_off.numel() - 1, _ptr(cuts), keep(slot), slot.numel(),
+                                          keep(pos), n, int(delim), int(before), int(after), int(reach), keep(start), keep(end), keep(flags),
+                                          _ptr(status), _stream())
+    _check(rc, "hmse_lines_extent")
+    st = int(status.item()) & 0xFFFFFFFF
+    if st & 2:
+        raise HmseError(-1, f"hmse_lines_extent device status {st:#x}: inconsistent tables")
+    return start, end, flags, st
+
+
+def lines_gather(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, start: torch.Tensor, end: torch.Tensor,
+                 out_off: torch.Tensor, n_out: int) -> torch.Tensor:
+    """hmse_lines_gather: the corpus bytes [start[i], end[i]) of every range back to back.  `out_off` int64[n + 1]: exclusive prefix sum
+    of end - start; n_out = out_off[-1].  -> uint8[n_out].  HmseError for an out_off[-1] above n_out (status bit 0), for inconsistent
+    tables, a range that descends or leaves the corpus, or an out_off that is not the prefix sum (bit 1); nothing was written then."""
+    _lines_tables("lines_gather", raw, raw_off, cuts, slot, ((start, "start"), (end, "end"), (out_off, "out_off")))
+    n, dev = start.numel(), cuts.device
+    if end.numel() != n or out_off.numel() != n + 1:
+        raise HmseError(-1, "lines_gather: start / end / out_off do not match")
+    out = _buf(max(int(n_out), 1), torch.uint8, dev)
+    status = _buf(1, torch.int32, dev, fill=0)
+    keep = lambda t: _ptr(t) if t.numel() else None
+    rc = _lib.hip_lib().hmse_lines_gather(keep(raw), raw.numel(), _ptr(raw_off), raw_off.numel() - 1, _ptr(cuts), keep(slot), slot.numel(),
+                                          keep(start), keep(end), _ptr(out_off), n, _ptr(out) if n_out else None, int(n_out), _ptr(status),
+                                          _stream())
+    _check(rc, "hmse_lines_gather")
+    st = int(status.item()) & 0xFFFFFFFF
+    if st:
+        raise HmseError(-1 if st & 2 else -2, f"hmse_lines_gather device status {st:#x}"
+                        + (": inconsistent tables, a range that descends or leaves the corpus, or out_off is not the prefix sum of the lengths"
+                           if st & 2 else ": out_off[-1] exceeds the output"))
     return out[:int(n_out)]
 
 

@@ -6,6 +6,7 @@ scaffold that drives several ranks in lock step on one GPU.
 """
 from __future__ import annotations
 
+import gc
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -73,8 +74,20 @@ class PhaseGraphs:
         if phase not in e.graphs:
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                fn()
+            # No finaliser may run between capture_begin and capture_end.  A front end and its PhaseGraphs refer to each other, so a
+            # dropped stream — its buffers and its captured graphs — is freed by the cycle collector only, whenever an allocation count
+            # trips it; inside a capture that destroys another graph and frees its pool, which the runtime answers with an abort.
+            # torch.cuda.graph no longer collects before it begins (torch.compiler.config.force_cudagraph_gc): collect here, then hold
+            # the collector off until the capture has ended.
+            gc.collect()
+            was_enabled = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(g):
+                    fn()
+            finally:
+                if was_enabled:
+                    gc.enable()
             e.graphs[phase] = g
         e.graphs[phase].replay()
 

@@ -834,6 +834,63 @@ int hmse_sync_match(const uint8_t* a, uint64_t a_bytes, const uint64_t* a_off, c
                     uint32_t* status, void* stream);
 
 /*
+ * Lines (hmse_amd/find.py lines / text / grep): from a hit to the line — the delimited record — it lies in, with context, and its text.
+ * Replaces the detour a user of hmse_find_* is left with today: read the store back, move the corpus to the host and run bytes.rfind /
+ * bytes.find per hit.  The tables (raw, raw_off, cuts, slot) mean what they mean for hmse_find_seams: corpus byte p of chunk c is
+ * raw[raw_off[slot[c]] + p - cuts[c]], C is the N = cuts[n_chunks] bytes of the corpus.  A line does not stop at a chunk boundary, a
+ * record that several chunks map to has other neighbours at each of its places, and chunks may be 0, 1 or 2 bytes long.
+ *
+ * Definitions, for a corpus offset o < N, the delimiter d = delim (one byte value), before = b, after = a, reach = R:
+ *   start  look at positions o-1, o-2, ..., max(o-R, 0) in that order: start = 1 + the position of the (b+1)-th byte equal to d met
+ *          on the way.  Fewer are met: start = max(o-R, 0), and HMSE_LINES_START_CUT is set iff o-R > 0 (reaching the corpus's first
+ *          byte is no cut).
+ *   end    look at positions o, o+1, ..., min(o+R, N)-1: end = the position of the (a+1)-th byte equal to d.  Fewer are met:
+ *          end = min(o+R, N), and HMSE_LINES_END_CUT is set iff o+R < N.
+ * The extent is C[start .. end): it never holds the closing delimiter, it holds b + a inner delimiters when nothing was cut, and a
+ * delimiter AT o closes o's own line (end = o when a = 0).  With no cut this is what splitting C at d gives: start of line
+ * max(i-b, 0), end of line i+a (N if there is none), i the line with L_i <= o <= R_i — the trailing empty line of a corpus that ends
+ * in d included.  Out of scope: delimiters of more than one byte, CR stripping, merging the overlapping context of neighbouring
+ * hits (grep's "--" groups), regular expressions.
+ *
+ * A validate kernel runs first in each call: status bit 1 = inconsistent tables, by hmse_find_*'s rules (raw_off or cuts descending,
+ * raw_off[n_rec] > raw_bytes, slot[k] >= n_rec, a chunk whose length is not its record's) and for cuts[0] != 0 (the positions come
+ * from the caller here).  With bit 1 nothing is read through the tables.
+ * No workspace, no stage id of their own; both calls report in profile slot 31 (see Diagnostics below).  Stream-ordered, allocate
+ * nothing, never sync.  HMSE_EINVAL before anything is cleared or launched: status NULL, n >= 2^33, with n > 0 a NULL pointer to a
+ * non-empty array (raw: raw_bytes > 0; raw_off: n_rec or n_chunks > 0; cuts, slot: n_chunks > 0).  n == 0 clears the status word and
+ * returns HMSE_OK.
+ *
+ * hmse_lines_extent — one wavefront per position; per trip it looks at 64 bytes (one per lane), clipped to the chunk and to reach:
+ *   pos     DEVICE u64[n]: corpus offsets, any order, equal ones allowed
+ *   start, end DEVICE u64[n];  flags DEVICE u8[n]: WRITTEN FOR EVERY i < n, the caller clears nothing
+ *   pos[i] >= N (N == 0, n_chunks == 0: every position): start = end = 0, flags = HMSE_LINES_BAD, status bit 0; the others are answered
+ *   status bit 1: every i gets 0 / 0 / HMSE_LINES_BAD
+ *   delim <= 255, 1 <= reach <= HMSE_LINES_MAX_REACH (else HMSE_EINVAL); before and after are any u32 — reach bounds the work: at
+ *   most 2 * reach bytes are looked at per position.
+ * hmse_lines_gather — one wavefront per range; 16 bytes per lane between the ends of every chunk piece:
+ *   start, end DEVICE u64[n]: ranges of the corpus, start[i] <= end[i] <= N, empty ones are legal, they may overlap
+ *   out_off DEVICE u64[n+1]: the caller's exclusive prefix sum of end[i] - start[i];  out DEVICE u8[out_cap], any alignment, NULL only
+ *           with out_cap == 0 (else HMSE_EINVAL)
+ *   out[out_off[i] .. out_off[i] + end[i] - start[i]) = C[start[i] .. end[i]) for every i
+ *   status bit 0: out_off[n] > out_cap.  bit 1: inconsistent tables, some start[i] > end[i], some end[i] > N, or
+ *   out_off[i+1] - out_off[i] != end[i] - start[i].  With either bit NOTHING is written to out.
+ */
+#define HMSE_LINES_START_CUT 1u
+#define HMSE_LINES_END_CUT   2u
+#define HMSE_LINES_BAD       128u
+#define HMSE_LINES_MAX_REACH (1u << 24)
+
+int hmse_lines_extent(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* raw_off, uint64_t n_rec,
+                      const uint64_t* cuts, const uint64_t* slot, uint64_t n_chunks,
+                      const uint64_t* pos, uint64_t n, uint32_t delim, uint32_t before, uint32_t after, uint32_t reach,
+                      uint64_t* start, uint64_t* end, uint8_t* flags, uint32_t* status, void* stream);
+
+int hmse_lines_gather(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* raw_off, uint64_t n_rec,
+                      const uint64_t* cuts, const uint64_t* slot, uint64_t n_chunks,
+                      const uint64_t* start, const uint64_t* end, const uint64_t* out_off, uint64_t n,
+                      uint8_t* out, uint64_t out_cap, uint32_t* status, void* stream);
+
+/*
  * Diagnostics (bench.py's roofline leg): when enabled, every entry point brackets its DOMINANT
  * kernel launch with a HIP event pair on the caller's stream.  hmse_profile_read() waits for the
  * recorded events (a host sync — never call it inside a capture), adds their durations to the
@@ -842,6 +899,7 @@ int hmse_sync_match(const uint8_t* a, uint64_t a_bytes, const uint64_t* a_off, c
  * (S, SG2, SG3, B, S2, SG), their dictionary jobs in 18..23, and the two encode-kernel instantiations in 14 and 15 (FULL
  * records) and 30 and 31 (DELTA records) (hmse_amd/csrc/l1_deflate.hip); hmse_find_scan also reports in 30, hmse_find_seams and
  * hmse_find_place in 31, hmse_sync_match in 19; hmse_findset_scan reports in 30 as well, hmse_findset_seams and hmse_findset_place in 31.
+ * hmse_lines_extent and hmse_lines_gather report in 31 as well (reset the slot before reading one of them: it is shared).
  * hmse_profile_counter(): work counted on the device while profiling is on — the DEFLATE match kernels add the TOKENS they
  * write to their slot (8..13, 18..23), the encode kernels the tokens they read (14, 15, 30, 31):
  * bench.py's algorithmic bytes come from these counts, not from an assumed token density.  A host sync; diagnostics only.
