@@ -24,8 +24,14 @@ From a hit to its line: StoreFinder.lines turns the offsets of a Found into the 
 with context and counts, StoreFinder.text returns their bytes, grep = lines(find(...)) (hmse_amd/csrc/lines.hip; include/hmse.h
 hmse_lines_* has the definitions, tests/lines_ref.py restates them in plain Python).  The walk goes through the chunk map on the device:
 nothing is read back, and a record that several chunks map to is looked at with the neighbours of each of its places.  Out of scope:
-delimiters of more than one byte, CR stripping, merging the overlapping context of neighbouring hits (grep's "--" groups), regular
-expressions.
+delimiters of more than one byte, CR stripping, merging the overlapping context of neighbouring hits (grep's "--" groups).
+
+Regular expressions: a regex.Regex (compiled on the host into a bounded DFA, hmse_amd/regex.py has the syntax and the definitions) is
+answered by StoreFinder.count_regex / find_regex / grep_regex with the same three steps — scan of the unique records, place, seams
+(hmse_amd/csrc/regex.hip; include/hmse.h hmse_regex_*) — split by START: a start whose record still holds `reach` bytes is a scan
+start, the last reach - 1 starts of every chunk are seam starts.  The result is a RegexFound: a Found with the lengths of the matches.
+Out of scope: anchors and \\b, captures, lazy matching, matches over 256 bytes, Unicode classes, several regexes fused into one
+automaton, multi-byte line delimiters, routing find / find_set through the DFA.
 """
 from __future__ import annotations
 
@@ -36,6 +42,7 @@ import torch
 
 from . import ops
 from .read import StoreReader
+from .regex import Regex, RegexError  # noqa: F401
 
 MAX_PATTERN_LEN = ops.FIND_MAX_LEN
 GROUP = ops.FIND_MAX_PATTERNS      # patterns per launch; more are answered in groups
@@ -47,6 +54,11 @@ class Found:
     ptr: torch.Tensor            # int64 [P + 1]: pattern j's occurrences are offsets[ptr[j]:ptr[j + 1]]
     offsets: torch.Tensor        # int64 corpus offsets, ascending per pattern
     counts: torch.Tensor         # int64 [P] occurrences per pattern
+
+
+@dataclass
+class RegexFound(Found):
+    lengths: torch.Tensor = None  # int64, aligned with offsets: occurrence i is corpus[offsets[i] : offsets[i] + lengths[i]]
 
 
 @dataclass
@@ -416,6 +428,109 @@ class StoreFinder:
         torch.cumsum(counts, 0, out=ptr[1:])
         src = torch.repeat_interleave(ptr_u[:-1][ps.index_d] - ptr[:-1], counts) + torch.arange(total, dtype=torch.int64, device=dev)
         return Found(ptr, found[src], counts)
+
+
+    # ------------------------------------------------------------------ regular expressions
+    def _regexes(self, rx):
+        rxs = [rx] if isinstance(rx, Regex) else list(rx)
+        for r in rxs:
+            if not isinstance(r, Regex):
+                raise ValueError(f"find: count_regex / find_regex take a Regex or a list of them (regex.Regex(pattern, device=...)), got a {type(r).__name__}")
+            if r.dev is None or r.dev != self.dev:
+                raise ValueError(f"find: the Regex lives on {r.dev}, the finder on {self.dev}")
+        return rxs
+
+    def _count_regex(self, r: Regex):
+        """-> (occurrences int64[1], scan hits, seam hits): two count-only launches."""
+        _, n_scan, c_scan = ops.regex_scan(self.raw, self.raw_off, self.mult, r.rx, hits_cap=0)
+        _, n_seam, c_seam = ops.regex_seams(self.raw, self.raw_off, self.cuts, self.slot, r.rx, hits_cap=0)
+        return c_scan + c_seam, n_scan, n_seam
+
+    def count_regex(self, rx) -> torch.Tensor:
+        """Occurrences per regex, int64[P] on the device (`rx`: a Regex, or a list of them, answered one after the other): two
+        count-only launches per regex, nothing is materialised."""
+        rxs = self._regexes(rx)
+        if not rxs or self.n_records == 0:
+            return torch.zeros(len(rxs), dtype=torch.int64, device=self.dev)
+        return torch.cat([self._count_regex(r)[0] for r in rxs])
+
+    def find_regex(self, rx, max_hits: int = 1 << 24) -> RegexFound:
+        """Every occurrence of every regex, with its length.  Counts first: ValueError naming the counts if their sum exceeds max_hits."""
+        rxs = self._regexes(rx)
+        n, dev = len(rxs), self.dev
+        z = lambda k: torch.zeros(k, dtype=torch.int64, device=dev)
+        if n == 0 or self.n_records == 0:
+            return RegexFound(z(n + 1), z(0), z(n), z(0))
+        counted = [self._count_regex(r) for r in rxs]
+        counts = torch.cat([c[0] for c in counted])
+        total = int(counts.sum())
+        if total > int(max_hits):
+            raise ValueError(f"find: {total} occurrences exceed max_hits = {max_hits}; counts per pattern: {counts.tolist()}")
+        parts = []
+        for r, (c, n_scan, n_seam) in zip(rxs, counted):
+            found = []
+            if n_scan:
+                hits, _, c_scan = ops.regex_scan(self.raw, self.raw_off, self.mult, r.rx, hits_cap=n_scan)
+                hits = torch.sort(hits)[0]                                   # by position in raw
+                rec_lo = torch.searchsorted(hits, self.raw_off << 8)         # first hit of every record
+                per_chunk = (rec_lo[1:] - rec_lo[:-1])[self.slot]
+                chunk_out = torch.zeros(self.slot.numel() + 1, dtype=torch.int64, device=dev)
+                torch.cumsum(per_chunk, 0, out=chunk_out[1:])
+                found.append(ops.find_place(hits, self.raw_off, self.cuts, self.slot, chunk_out, int(c_scan.sum())))
+            if n_seam:
+                found.append(ops.regex_seams(self.raw, self.raw_off, self.cuts, self.slot, r.rx, hits_cap=n_seam)[0])
+            if found:
+                parts.append(torch.sort(torch.cat(found))[0])                # by corpus offset: one length per start
+        h = torch.cat(parts) if parts else z(0)
+        ptr = z(n + 1)
+        torch.cumsum(counts, 0, out=ptr[1:])
+        if h.numel() != total:
+            raise ops.HmseError(-1, f"find: {h.numel()} occurrences located, {total} counted")
+        return RegexFound(ptr, h >> 8, counts, (h & 0xFF) + 1)
+
+    def grep_regex(self, rx, delim: bytes = b"\n", before: int = 0, after: int = 0, reach: int = 1 << 16, max_hits: int = 1 << 24) -> Lines:
+        """lines(find_regex(rx, max_hits), delim, before, after, reach): per regex the lines that hold a match's start."""
+        _lines_args(delim, before, after, reach)
+        return self.lines(self.find_regex(rx, max_hits), delim, before, after, reach)
+
+    nonoverlapping = staticmethod(lambda found: nonoverlapping(found))
+
+
+def nonoverlapping(found: RegexFound) -> RegexFound:
+    """Per pattern the first occurrence, then each next one that starts at or behind the previous kept one's end: leftmost-longest,
+    like grep -o.  Torch plumbing on the tensors' device: searchsorted for every occurrence's successor, then pointer doubling from
+    each pattern's first occurrence — no host loop over the occurrences."""
+    off, ln = found.offsets, found.lengths
+    n, dev, P = off.numel(), off.device, found.counts.numel()
+    if n == 0:
+        return found
+    pat = torch.repeat_interleave(torch.arange(P, dtype=torch.int64, device=dev), found.counts)
+    key = (pat << 56) | off                                                      # ascending: by pattern, then offset (offsets stay below 2^56)
+    nxt = torch.searchsorted(key, key + ln)                                      # the first occurrence of the pattern at or behind the end
+    nxt = torch.where(nxt < found.ptr[1:][pat], nxt, torch.full_like(nxt, n))    # none in this pattern: the sink n
+    nxt = torch.cat([nxt, torch.full((1,), n, dtype=torch.int64, device=dev)])
+    kept = torch.zeros(n + 1, dtype=torch.bool, device=dev)
+    kept[found.ptr[:-1][found.counts > 0]] = True
+    for _ in range(max(1, int(n).bit_length())):                                 # after k trips: everything within 2^k - 1 hops of a start is marked
+        kept[nxt[torch.nonzero(kept).reshape(-1)]] = True
+        nxt = nxt[nxt]
+    kept = kept[:n]
+    counts = torch.bincount(pat[kept], minlength=P)
+    ptr = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=ptr[1:])
+    return RegexFound(ptr, off[kept], counts, ln[kept])
+
+
+def find_regex(store, rx, device, max_hits: int = 1 << 24, verify: bool = True) -> RegexFound:
+    """One-off form of StoreFinder(store, device, verify).find_regex(rx, max_hits)."""
+    return StoreFinder(store, device, verify).find_regex(rx, max_hits)
+
+
+def grep_regex(store, rx, device, delim: bytes = b"\n", before: int = 0, after: int = 0, reach: int = 1 << 16, max_hits: int = 1 << 24,
+               verify: bool = True) -> Lines:
+    """One-off form of StoreFinder(store, device, verify).grep_regex(rx, delim, before, after, reach, max_hits)."""
+    _lines_args(delim, before, after, reach)
+    return StoreFinder(store, device, verify).grep_regex(rx, delim, before, after, reach, max_hits)
 
 
 def find_set(store, patterns, device, ignore_case: bool = False, max_hits: int = 1 << 24, verify: bool = True) -> Found:

@@ -969,3 +969,89 @@ def findset_place(hits: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor,
         raise HmseError(-2 if st == 1 else -1, f"hmse_findset_place device status {st:#x}"
                         + (": inconsistent tables" if st & 2 else ": chunk_out[-1] exceeds the output"))
     return out[:int(n_out)]
+
+
+REGEX_MAX_LEN, REGEX_MAX_TABLE, REGEX_ACCEPT = 256, 16384, 0x8000
+
+
+@dataclass
+class Regex:
+    """The device arrays and the header of a compiled regular expression (include/hmse.h `hmse_regex`; built by regex.Regex)."""
+    table: torch.Tensor          # int16 [n_states * n_classes]: the bits of the u16 entries
+    classmap: torch.Tensor       # uint8 [256]
+    n_states: int
+    n_classes: int
+    reach: int
+
+    def header(self) -> "_lib.HmseRegex":
+        return _lib.HmseRegex(C.sizeof(_lib.HmseRegex), int(self.n_states), int(self.n_classes), int(self.reach), _ptr(self.table), _ptr(self.classmap))
+
+
+def _regex_args(rx: Regex):
+    for t, nm in ((rx.table, "table"), (rx.classmap, "classmap")):
+        _require_gpu(t, nm)
+    if (rx.table.element_size() != 2 or rx.table.numel() != int(rx.n_states) * int(rx.n_classes) or rx.classmap.numel() != 256
+            or rx.classmap.element_size() != 1):
+        raise HmseError(-1, "regex: the automaton's arrays do not match its header")
+    return rx.header()
+
+
+def _regex_hits(call, where: str, hits_cap, dev):
+    """_find_hits for the one count and the three status bits of hmse_regex_*: a list that ran out (bit 0) is filled by ONE more call
+    with hits_cap = n_hits.  -> (hits int64[n_hits], n_hits, count int64[1])."""
+    cap = hits_cap
+    for _ in range(3):
+        hits = _buf(max(int(cap or 0), 1), torch.int64, dev)
+        meta = _buf(2, torch.int64, dev, fill=0)      # [n_hits, status]
+        count = _buf(1, torch.int64, dev, fill=0)
+        _check(call(hits, int(cap or 0), meta, count), where)
+        n_hits, status = (int(v) for v in meta.tolist())
+        status &= 0xFFFFFFFF
+        if status & 6:
+            raise HmseError(-1, f"{where}: {'inconsistent tables' if status & 2 else 'bad automaton'} (device status {status:#x})")
+        if cap is None or (status & 1):
+            if cap is not None and cap >= n_hits:
+                break
+            cap = n_hits                              # exact: the second call cannot run out
+            if cap == 0:
+                return hits[:0], 0, count
+            continue
+        return hits[:min(n_hits, int(cap))], n_hits, count
+    raise HmseError(-2, f"{where}: the hit list ran out twice ({n_hits} hits, {cap} entries)")
+
+
+def regex_scan(raw: torch.Tensor, raw_off: torch.Tensor, mult: torch.Tensor | None, rx: Regex, hits_cap: int | None = None,
+               raw_bytes: int | None = None):
+    """hmse_regex_scan: the occurrence of the regex at every SCAN start p of every record (raw_off[r + 1] - p >= reach).
+    -> (hits int64[n] = position in raw << 8 | (length - 1), any order; n_hits; count int64[1] = the sum of mult[record] over the hits
+    (int32, None: 1 each)).  hits_cap 0: count only; None: sized by a count-only call.  HmseError for inconsistent tables (device
+    status bit 1) or a bad automaton (bit 2)."""
+    for t, nm in ((raw, "raw"), (raw_off, "raw_off")) + (((mult, "mult"),) if mult is not None else ()):
+        _require_gpu(t, nm)
+    n_rec = raw_off.numel() - 1
+    if n_rec < 0 or (mult is not None and mult.numel() != n_rec):
+        raise HmseError(-1, "regex_scan: raw_off / mult do not match")
+    hdr = _regex_args(rx)
+    nb = raw.numel() if raw_bytes is None else int(raw_bytes)
+    lib = _lib.hip_lib()
+    call = lambda hits, cap, meta, counts: lib.hmse_regex_scan(_ptr(raw) if raw.numel() else None, nb, _ptr(raw_off), max(n_rec, 0), _ptr(mult),
+                                                               C.byref(hdr), _ptr(hits) if cap else None, cap, meta.data_ptr(), _ptr(counts),
+                                                               meta.data_ptr() + 8, _stream())
+    return _regex_hits(call, "hmse_regex_scan", hits_cap, raw_off.device)
+
+
+def regex_seams(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, rx: Regex, hits_cap: int | None = None):
+    """hmse_regex_seams: the occurrence of the regex at every SEAM start o of every chunk (cuts[k + 1] - o < reach), walked through
+    the chunk map.  -> (hits int64[n] = corpus offset << 8 | (length - 1), any order; n_hits; count int64[1] = n_hits)."""
+    for t, nm in ((raw, "raw"), (raw_off, "raw_off"), (cuts, "cuts"), (slot, "slot")):
+        _require_gpu(t, nm)
+    n_chunks = slot.numel()
+    if cuts.numel() != n_chunks + 1 or raw_off.numel() < 1:
+        raise HmseError(-1, "regex_seams: cuts / slot / raw_off do not match")
+    hdr = _regex_args(rx)
+    lib = _lib.hip_lib()
+    keep = lambda t: _ptr(t) if t.numel() else None
+    call = lambda hits, cap, meta, counts: lib.hmse_regex_seams(keep(raw), raw.numel(), _ptr(raw_off), raw_off.numel() - 1, _ptr(cuts), keep(slot),
+                                                                n_chunks, C.byref(hdr), _ptr(hits) if cap else None, cap, meta.data_ptr(),
+                                                                _ptr(counts), meta.data_ptr() + 8, _stream())
+    return _regex_hits(call, "hmse_regex_seams", hits_cap, cuts.device)

@@ -1,0 +1,490 @@
+"""Regular expressions compiled on the host into the bounded DFA that hmse_regex_scan / hmse_regex_seams walk (include/hmse.h `hmse_regex`).
+
+numpy only: importable and usable without a GPU (device=None keeps the numpy arrays).  Definitions (tests/regex_ref.py restates them in
+plain Python with the standard `re` module as the oracle):
+  * a regex r denotes a set of byte strings L(r); start o of a buffer is an OCCURRENCE iff some l with 1 <= l <= min(reach, n - o) has
+    buf[o : o + l] in L(r); its LENGTH is the largest such l.  Empty matches are never reported, every start counts (overlapping ones
+    included), and a match is at most HMSE_REGEX_MAX_LEN = 256 bytes: `x.*y` reports the longest match within 256 bytes.
+  * syntax (bytes only): literal bytes; the metacharacters \\ . [ ] ( ) | ? * + { } ^ $ escaped to be literal; \\n \\r \\t \\f \\v, \\xHH,
+    \\d \\D \\w \\W \\s \\S (ASCII), \\ plus ASCII punctuation; `.` (any byte but 0x0A; dotall: any byte); classes [...] and [^...] with
+    ranges and those escapes ([ ] ^ - \\ escaped inside); groups ( ) and (?: ) (nothing is captured); alternation (an empty alternative
+    is allowed); ? * + {m} {m,} {m,n} with m <= n <= 256.  What is accepted means what it means to `re` in bytes mode; everything else
+    (anchors, \\b, back-references, octal, lazy and possessive forms, a quantifier on a quantifier or on nothing, other (? forms,
+    {,n}) is refused with a RegexError naming the byte offset.
+  * ignore_case closes every literal and class under ASCII case BEFORE a class is negated (re.IGNORECASE on bytes); bytes >= 0x80
+    are untouched; the data is never folded.
+Compiled form (deterministic): Glushkov position automaton -> subset construction -> minimal DFA.  State 0 is the dead state (its row
+is all 0), state 1 the start, the others in BFS order from the start over the classes in ascending order; `classmap` u8[256] (bytes with
+equal columns share a class, classes numbered by their smallest byte); `table` u16[n_states * n_classes] = next state, OR-ed with
+HMSE_REGEX_ACCEPT iff the next state accepts; `reach` = the longest path from the start through live states if that graph is acyclic,
+else 256.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+HMSE_REGEX_MAX_LEN = 256
+HMSE_REGEX_MAX_TABLE = 16384
+HMSE_REGEX_ACCEPT = 0x8000
+MAX_STATES = 32767
+_MAX_POSITIONS = 4096          # literal / class positions after expanding the counted repeats
+_MAX_SUBSETS = 1 << 16         # states of the subset construction (before it is minimised)
+
+_ALL = (1 << 256) - 1
+_PUNCT = frozenset(b"!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~")
+_HEX = frozenset(b"0123456789abcdefABCDEF")
+
+
+def _mask(values) -> int:
+    m = 0
+    for v in values:
+        m |= 1 << v
+    return m
+
+
+_DIGIT = _mask(range(0x30, 0x3A))
+_WORD = _DIGIT | _mask(range(0x41, 0x5B)) | _mask(range(0x61, 0x7B)) | (1 << 0x5F)
+_SPACE = _mask(b" \t\n\r\f\v")
+_CATEGORY = {ord("d"): _DIGIT, ord("D"): _ALL & ~_DIGIT, ord("w"): _WORD, ord("W"): _ALL & ~_WORD, ord("s"): _SPACE, ord("S"): _ALL & ~_SPACE}
+_CONTROL = {ord("n"): 0x0A, ord("r"): 0x0D, ord("t"): 0x09, ord("f"): 0x0C, ord("v"): 0x0B}
+_UPPER, _LOWER = _mask(range(0x41, 0x5B)), _mask(range(0x61, 0x7B))
+
+
+def _close_case(m: int) -> int:
+    return m | ((m & _UPPER) << 32) | ((m & _LOWER) >> 32)
+
+
+class RegexError(ValueError):
+    """A pattern outside the syntax or above a cap; `offset` is the byte offset in the pattern (None for a cap)."""
+
+    def __init__(self, what: str, offset=None):
+        super().__init__(f"regex: {what}" + (f" at offset {offset}" if offset is not None else ""))
+        self.offset = offset
+
+
+# ---- parser: pattern -> tree of ("set", mask) | ("cat", [..]) | ("alt", [..]) | ("rep", node, m, n or None) ------------------------------
+class _Parser:
+    def __init__(self, pat: bytes, ignore_case: bool, dotall: bool):
+        self.p, self.i, self.ic, self.dotall = pat, 0, ignore_case, dotall
+
+    def parse(self):
+        node = self.alt()
+        if self.i < len(self.p):                                    # only an unmatched ')' stops alt() early
+            raise RegexError("unbalanced ')'", self.i)
+        return node
+
+    def alt(self):
+        alts = [self.cat()]
+        while self.i < len(self.p) and self.p[self.i] == 0x7C:      # |
+            self.i += 1
+            alts.append(self.cat())
+        return alts[0] if len(alts) == 1 else ("alt", alts)
+
+    def cat(self):
+        items = []
+        while self.i < len(self.p) and self.p[self.i] not in b"|)":
+            items.append(self.quantified())
+        return ("cat", items)
+
+    def quantified(self):
+        at = self.i
+        c = self.p[at]
+        if c in b"?*+{":
+            raise RegexError("a quantifier with nothing in front", at)
+        if c in b"}]":
+            raise RegexError(f"an unescaped {chr(c)!r}", at)
+        if c in b"^$":
+            raise RegexError(f"the anchor {chr(c)!r} (line anchors are out of scope)", at)
+        node = self.atom()
+        q = self.quantifier()
+        if q is None:
+            return node
+        if self.i < len(self.p) and self.p[self.i] in b"?+":
+            raise RegexError("a lazy or possessive quantifier", self.i)
+        if self.i < len(self.p) and self.p[self.i] in b"*{":
+            raise RegexError("a quantifier on a quantifier", self.i)
+        return ("rep", node, q[0], q[1])
+
+    def quantifier(self):
+        if self.i >= len(self.p):
+            return None
+        c, at = self.p[self.i], self.i
+        if c == 0x3F:
+            self.i += 1
+            return 0, 1
+        if c == 0x2A:
+            self.i += 1
+            return 0, None
+        if c == 0x2B:
+            self.i += 1
+            return 1, None
+        if c != 0x7B:
+            return None
+        j = self.p.find(b"}", at)
+        body = self.p[at + 1: j] if j >= 0 else b""
+        lo, comma, hi = body.partition(b",")
+        if j < 0 or not lo.isdigit() or (hi and not hi.isdigit()) or len(lo) > 4 or len(hi) > 4:
+            raise RegexError("an unescaped '{' that is no {m}, {m,} or {m,n}", at)
+        m = int(lo)
+        n = m if not comma else (int(hi) if hi else None)
+        if m > HMSE_REGEX_MAX_LEN or (n is not None and (n > HMSE_REGEX_MAX_LEN or n < m)):
+            raise RegexError(f"a repeat count outside m <= n <= {HMSE_REGEX_MAX_LEN}", at)
+        self.i = j + 1
+        return m, n
+
+    def atom(self):
+        at = self.i
+        c = self.p[at]
+        if c == 0x28:                                               # (
+            self.i += 1
+            if self.i < len(self.p) and self.p[self.i] == 0x3F:
+                if self.p[self.i + 1: self.i + 2] != b":":
+                    raise RegexError("a (? form other than (?:", at)
+                self.i += 2
+            node = self.alt()
+            if self.i >= len(self.p):
+                raise RegexError("unbalanced '('", at)
+            self.i += 1                                             # )
+            return node
+        if c == 0x5B:
+            return ("set", self.klass())
+        if c == 0x2E:
+            self.i += 1
+            return ("set", _ALL if self.dotall else _ALL & ~(1 << 0x0A))
+        if c == 0x5C:
+            kind, v = self.escape()
+            m = v if kind == "set" else 1 << v
+        else:
+            self.i += 1
+            m = 1 << c
+        return ("set", _close_case(m) if self.ic else m)
+
+    def escape(self):
+        """At a backslash -> ("byte", value) or ("set", mask)."""
+        at = self.i
+        if at + 1 >= len(self.p):
+            raise RegexError("a backslash at the end", at)
+        c = self.p[at + 1]
+        self.i = at + 2
+        if c in _CONTROL:
+            return "byte", _CONTROL[c]
+        if c in _CATEGORY:
+            return "set", _CATEGORY[c]
+        if c == 0x78:                                               # \xHH
+            h = self.p[at + 2: at + 4]
+            if len(h) != 2 or h[0] not in _HEX or h[1] not in _HEX:
+                raise RegexError("\\x without two hex digits", at)
+            self.i = at + 4
+            return "byte", int(h, 16)
+        if c in _PUNCT:
+            return "byte", c
+        raise RegexError(f"the escape \\{chr(c) if 0x20 < c < 0x7F else hex(c)}", at)
+
+    def klass(self):
+        at = self.i
+        self.i += 1
+        neg = self.i < len(self.p) and self.p[self.i] == 0x5E
+        if neg:
+            self.i += 1
+        m = 0
+        while True:
+            if self.i >= len(self.p):
+                raise RegexError("a class without its ']'", at)
+            c, here = self.p[self.i], self.i
+            if c == 0x5D:
+                self.i += 1
+                break
+            if c in b"[^-":
+                raise RegexError(f"an unescaped {chr(c)!r} inside a class", here)
+            if c == 0x5C:
+                kind, v = self.escape()
+            else:
+                kind, v = "byte", c
+                self.i += 1
+            if self.p[self.i: self.i + 1] == b"-":                  # a range (a '-' must be escaped to be literal)
+                dash = self.i
+                nxt = self.p[dash + 1: dash + 2]
+                if kind == "set" or not nxt or nxt in (b"]", b"[", b"^", b"-"):
+                    raise RegexError("an unescaped '-' inside a class that forms no range", dash)
+                self.i = dash + 1
+                if nxt == b"\\":
+                    kind2, hi = self.escape()
+                    if kind2 == "set":
+                        raise RegexError("a range that ends in a class escape", dash + 1)
+                else:
+                    hi = nxt[0]
+                    self.i += 1
+                if hi < v:
+                    raise RegexError("a descending range", here)
+                m |= _mask(range(v, hi + 1))
+            else:
+                m |= v if kind == "set" else 1 << v
+        if self.ic:
+            m = _close_case(m)
+        if m == 0 or (neg and m == _ALL):
+            raise RegexError("an empty class", at)
+        return _ALL & ~m if neg else m
+
+
+# ---- tree -> Glushkov automaton ---------------------------------------------------------------------------------------------------------
+def _positions(node) -> int:
+    k = node[0]
+    if k == "set":
+        return 1
+    if k == "rep":
+        m, n = node[2], node[3]
+        return _positions(node[1]) * max(m + 1 if n is None else n, 1)
+    return sum(_positions(c) for c in node[1])
+
+
+def _glushkov(node, sym, follow):
+    """-> (nullable, first, last) as position bit sets; appends to sym (the byte set of every position) and follow."""
+    k = node[0]
+    if k == "set":
+        p = len(sym)
+        sym.append(node[1])
+        follow.append(0)
+        return False, 1 << p, 1 << p
+    if k == "alt":
+        nu, fi, la = False, 0, 0
+        for c in node[1]:
+            a, b, d = _glushkov(c, sym, follow)
+            nu, fi, la = nu or a, fi | b, la | d
+        return nu, fi, la
+    if k == "cat":
+        nu, fi, la = True, 0, 0
+        for c in node[1]:
+            nu, fi, la = _concat((nu, fi, la), _glushkov(c, sym, follow), follow)
+        return nu, fi, la
+    _, body, m, n = node                                            # rep: m copies, then a star or n - m optional copies
+    acc = (True, 0, 0)
+    for _ in range(m):
+        acc = _concat(acc, _glushkov(body, sym, follow), follow)
+    if n is None:
+        _, fi, la = _glushkov(body, sym, follow)
+        _link(la, fi, follow)
+        acc = _concat(acc, (True, fi, la), follow)
+    else:
+        for _ in range(n - m):
+            _, fi, la = _glushkov(body, sym, follow)
+            acc = _concat(acc, (True, fi, la), follow)
+    return acc
+
+
+def _link(last: int, first: int, follow):
+    p = 0
+    while last:
+        if last & 1:
+            follow[p] |= first
+        last >>= 1
+        p += 1
+
+
+def _concat(a, b, follow):
+    _link(a[2], b[1], follow)
+    return a[0] and b[0], a[1] | (b[1] if a[0] else 0), b[2] | (a[2] if b[0] else 0)
+
+
+class Regex:
+    """A compiled regular expression (module docstring).  .n_states, .n_classes, .reach, .min_len; .table (uint16 numpy), .classmap
+    (uint8 numpy); .match_at(buf, o) simulates the table on the host.  With a device: .rx (ops.Regex: the arrays in HBM and the
+    `hmse_regex` header) and .resident_bytes."""
+
+    def __init__(self, pattern, ignore_case: bool = False, dotall: bool = False, device=None):
+        if isinstance(pattern, str) or not isinstance(pattern, (bytes, bytearray, memoryview)):
+            raise RegexError(f"a pattern is bytes, got a {type(pattern).__name__} (encode it)")
+        self.pattern, self.ignore_case, self.dotall = bytes(pattern), bool(ignore_case), bool(dotall)
+        tree = _Parser(self.pattern, self.ignore_case, self.dotall).parse()
+        n_pos = _positions(tree)
+        if n_pos > _MAX_POSITIONS:
+            raise RegexError(f"{n_pos} literal / class positions after expanding the counted repeats; the compiler takes {_MAX_POSITIONS}")
+        sym, follow = [], []
+        nullable, first, last = _glushkov(tree, sym, follow)
+        trans, accept, cols = self._subsets(sym, follow, nullable, first, last)
+        self._minimise(trans, accept, cols)
+        self.dev, self.rx, self.resident_bytes, self._lists = None, None, 0, None
+        if device is not None:
+            import torch
+            from . import ops
+            self.dev = torch.device(device)
+            self.rx = ops.Regex(torch.from_numpy(self.table.view(np.int16).copy()).to(self.dev), torch.from_numpy(self.classmap.copy()).to(self.dev),
+                                self.n_states, self.n_classes, self.reach)
+            self.resident_bytes = self.table.nbytes + self.classmap.nbytes
+
+    # -- subset construction over the byte classes of the positions' sets: state 0 = dead, 1 = start --
+    @staticmethod
+    def _subsets(sym, follow, nullable, first, last):
+        pos_of = [0] * 256                                          # positions whose set holds byte b
+        for p, m in enumerate(sym):
+            bit, b = 1 << p, 0
+            while m:
+                if m & 1:
+                    pos_of[b] |= bit
+                m >>= 1
+                b += 1
+        cols, col_of = [], {}                                       # distinct pos_of values in order of their smallest byte
+        byte_col = []
+        for b in range(256):
+            c = col_of.setdefault(pos_of[b], len(cols))
+            if c == len(cols):
+                cols.append(pos_of[b])
+            byte_col.append(c)
+        ids = {(0, False): 0, (0, True): 1}                          # (positions just read, at the start)
+        order = [(0, False), (0, True)]
+        trans = [[0] * len(cols)]
+        accept = [False, nullable]
+        s = 1
+        while s < len(order):
+            ps, init = order[s]
+            nxt, p = first if init else 0, 0
+            while ps:
+                if ps & 1:
+                    nxt |= follow[p]
+                ps >>= 1
+                p += 1
+            row = []
+            for c in cols:
+                t = nxt & c
+                if t == 0:
+                    row.append(0)
+                    continue
+                j = ids.get((t, False))
+                if j is None:
+                    j = ids[(t, False)] = len(order)
+                    if j >= _MAX_SUBSETS:
+                        raise RegexError(f"the subset construction exceeds {_MAX_SUBSETS} states (the table holds {HMSE_REGEX_MAX_TABLE} entries)")
+                    order.append((t, False))
+                    accept.append((t & last) != 0)
+                row.append(j)
+            trans.append(row)
+            s += 1
+        return trans, accept, byte_col
+
+    def _minimise(self, trans, accept, byte_col):
+        n, k = len(trans), len(trans[0])
+        # states from which no accepting state is reachable fold into the dead state
+        back = [[] for _ in range(n)]
+        for s, row in enumerate(trans):
+            for t in set(row):
+                back[t].append(s)
+        live = [False] * n
+        stack = [s for s in range(n) if accept[s]]
+        for s in stack:
+            live[s] = True
+        while stack:
+            for q in back[stack.pop()]:
+                if not live[q]:
+                    live[q] = True
+                    stack.append(q)
+        live[0] = False
+        trans = [[t if live[t] else 0 for t in row] if live[s] else [0] * k for s, row in enumerate(trans)]
+        if not any(trans[1]):
+            raise RegexError("the pattern matches nothing but the empty string")
+        # Moore: refine {dead} {accepting} {the others} until no block splits
+        block = [0 if not live[s] else (2 if accept[s] else 1) for s in range(n)]
+        n_blocks = len(set(block))
+        while True:
+            sig = {}
+            new = [sig.setdefault((block[s], tuple(block[t] for t in trans[s])), len(sig)) for s in range(n)]
+            block = new
+            if len(sig) == n_blocks:
+                break
+            n_blocks = len(sig)
+        rep = {}
+        for s in range(n):
+            rep.setdefault(block[s], s)
+        dead = block[0]
+        # number the blocks: dead 0, start 1, the others in BFS order over the columns in ascending order
+        num, queue = {dead: 0, block[1]: 1}, [block[1]]
+        if block[1] == dead:
+            raise RegexError("the pattern matches nothing but the empty string")
+        for b in queue:
+            for t in trans[rep[b]]:
+                if block[t] not in num:
+                    num[block[t]] = len(num)
+                    queue.append(block[t])
+        m = len(num)
+        rows = [[0] * k for _ in range(m)]
+        acc = [False] * m
+        for b, i in num.items():
+            rows[i] = [num[block[t]] for t in trans[rep[b]]]
+            acc[i] = accept[rep[b]] and b != dead
+        # classes: bytes with equal columns, numbered by their smallest byte
+        full = np.array(rows, np.int64)[:, np.array(byte_col)]      # [m, 256]
+        seen, classmap, keep = {}, np.zeros(256, np.uint8), []
+        for b in range(256):
+            key = full[:, b].tobytes()
+            c = seen.get(key)
+            if c is None:
+                c = seen[key] = len(keep)
+                keep.append(b)
+            classmap[b] = c
+        nc = len(keep)
+        if m > MAX_STATES or m * nc > HMSE_REGEX_MAX_TABLE:
+            raise RegexError(f"the minimal DFA has {m} states x {nc} classes = {m * nc} table entries; the caps are {MAX_STATES} states and "
+                             f"HMSE_REGEX_MAX_TABLE = {HMSE_REGEX_MAX_TABLE} entries")
+        nxt = full[:, keep]                                          # [m, nc]
+        accb = np.array(acc, bool)
+        self.n_states, self.n_classes = m, nc
+        self.classmap = classmap
+        self.table = (nxt | np.where(accb[nxt], HMSE_REGEX_ACCEPT, 0)).astype(np.uint16).reshape(-1)
+        self.accepting = accb
+        # shortest non-empty match; longest path through the live states (256 if they hold a cycle)
+        dist, frontier, self.min_len = {1}, [1], 0
+        for step in range(1, m + 1):
+            frontier = sorted({int(t) for s in frontier for t in nxt[s] if t})
+            if any(accb[t] for t in frontier):
+                self.min_len = step
+                break
+            frontier = [t for t in frontier if t not in dist]
+            dist.update(frontier)
+        if self.min_len == 0 or self.min_len > HMSE_REGEX_MAX_LEN:
+            raise RegexError(f"the shortest non-empty match has more than HMSE_REGEX_MAX_LEN = {HMSE_REGEX_MAX_LEN} bytes")
+        succ = [sorted({int(t) for t in nxt[s] if t}) for s in range(m)]
+        indeg = [0] * m
+        for s in range(1, m):
+            for t in succ[s]:
+                indeg[t] += 1
+        depth, ready, done = [0] * m, [s for s in range(1, m) if indeg[s] == 0], 0
+        while ready:
+            s = ready.pop()
+            done += 1
+            for t in succ[s]:
+                depth[t] = max(depth[t], depth[s] + 1)
+                indeg[t] -= 1
+                if indeg[t] == 0:
+                    ready.append(t)
+        self.reach = min(max(depth), HMSE_REGEX_MAX_LEN) if done == m - 1 else HMSE_REGEX_MAX_LEN
+
+    def match_at(self, buf, o: int) -> int:
+        """The length of the occurrence at buf[o] (the longest match of 1..min(reach, len(buf) - o) bytes), or 0."""
+        if self._lists is None:                                      # (plain lists: indexing a numpy array element by element is slow)
+            self._lists = self.table.tolist(), self.classmap.tolist()
+        s, best, nc, (tab, cm) = 1, 0, self.n_classes, self._lists
+        for i in range(min(self.reach, len(buf) - o)):
+            e = tab[s * nc + cm[buf[o + i]]]
+            s = e & 0x7FFF
+            if s == 0:
+                break
+            if e & HMSE_REGEX_ACCEPT:
+                best = i + 1
+        return best
+
+    def match_all(self, buf) -> np.ndarray:
+        """match_at for every start of buf at once -> int64[len(buf)] (numpy: one step of all live walks per trip)."""
+        cls = self.classmap[np.frombuffer(bytes(buf), np.uint8)].astype(np.int64)
+        n = cls.size
+        best = np.zeros(n, np.int64)
+        idx, state = np.arange(n), np.ones(n, np.int64)
+        tab = self.table.astype(np.int64)
+        for i in range(self.reach):
+            keep = idx + i < n
+            idx, state = idx[keep], state[keep]
+            if idx.size == 0:
+                break
+            e = tab[state * self.n_classes + cls[idx + i]]
+            state = e & 0x7FFF
+            best[idx[(e & HMSE_REGEX_ACCEPT) != 0]] = i + 1
+            alive = state != 0
+            idx, state = idx[alive], state[alive]
+        return best

@@ -850,7 +850,7 @@ int hmse_sync_match(const uint8_t* a, uint64_t a_bytes, const uint64_t* a_off, c
  * delimiter AT o closes o's own line (end = o when a = 0).  With no cut this is what splitting C at d gives: start of line
  * max(i-b, 0), end of line i+a (N if there is none), i the line with L_i <= o <= R_i — the trailing empty line of a corpus that ends
  * in d included.  Out of scope: delimiters of more than one byte, CR stripping, merging the overlapping context of neighbouring
- * hits (grep's "--" groups), regular expressions.
+ * hits (grep's "--" groups).
  *
  * A validate kernel runs first in each call: status bit 1 = inconsistent tables, by hmse_find_*'s rules (raw_off or cuts descending,
  * raw_off[n_rec] > raw_bytes, slot[k] >= n_rec, a chunk whose length is not its record's) and for cuts[0] != 0 (the positions come
@@ -891,6 +891,61 @@ int hmse_lines_gather(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* ra
                       uint8_t* out, uint64_t out_cap, uint32_t* status, void* stream);
 
 /*
+ * Regular-expression search (hmse_amd/regex.py compiles, hmse_amd/find.py StoreFinder.find_regex runs): the question of hmse_find_*
+ * for a regular expression — every ISO date, every IPv4 address, `(error|warn)[a-z ]*id=`.  Replaces read_store -> host -> re.finditer.
+ * The matcher is a DFA compiled on the host; the kernels walk its transition table.
+ *
+ * Definitions.  C is the N bytes of the corpus, L(r) the byte strings the regex denotes, R = reach (below).  Start o is an OCCURRENCE
+ * iff some l with 1 <= l <= min(R, N - o) has C[o .. o + l) in L(r); its LENGTH is the largest such l.  Empty matches are never
+ * reported; every start counts, overlapping ones included (`a+` has four occurrences in `aaaa`, of 4, 3, 2 and 1 bytes).  A match is
+ * at most HMSE_REGEX_MAX_LEN bytes: `x.*y` reports the longest match within 256 bytes — this is the definition, not a defect.
+ *
+ * The compiled form is plain device arrays, so any caller can build it:
+ *   state 0 is the dead state (its row is all 0), state 1 the start; n_states <= 32767
+ *   classmap = u8[256]: the class of every byte value, < n_classes
+ *   table    = u16[n_states * n_classes]: table[s * n_classes + c] = the next state, OR-ed with HMSE_REGEX_ACCEPT iff that state accepts
+ *   reach    = 1..256: no match is longer (the longest path through the live states if they hold no cycle, else 256)
+ *   n_states * n_classes <= HMSE_REGEX_MAX_TABLE (32 KiB: the kernels keep the table in LDS beside a tile of data)
+ * The header is a HOST struct, read during the call only.  HMSE_EINVAL before anything is cleared or launched: struct_size,
+ * n_states < 2 or > 32767, n_classes outside 1..256, a table over the cap, reach outside 1..256, a NULL pointer to a non-empty array,
+ * raw_bytes >= 2^56.
+ *
+ * Partition by START (a longest match may or may not cross a boundary): start p of record r is a SCAN start iff
+ * raw_off[r+1] - p >= reach — its answer depends on the record only and holds for every chunk that maps to r (hmse_regex_scan, laid
+ * out by hmse_find_place, which passes the low byte through); start o of chunk k is a SEAM start iff cuts[k+1] - o < reach — the
+ * last min(reach - 1, chunk length) positions of the chunk, walked through the chunk map over any number of tiny or empty chunks and
+ * clipped to N (hmse_regex_seams).  Scan starts placed plus seam starts of all chunks are every occurrence exactly once.
+ *
+ * A hit is one u64: position << 8 | (length - 1); position = offset in raw (scan), corpus offset (seams).
+ *   hits, hits_cap, n_hits as for hmse_find_*;  count DEVICE u64[1]: scan = the sum of mult[record] over the hits, seams = the hits
+ *   status  DEVICE u32[1]: bit0 = the hit list ran out (n_hits and count stay exact), bit1 = inconsistent tables (hmse_find_*'s rules),
+ *           bit2 = bad automaton: a table entry whose low 15 bits are >= n_states, a non-zero dead row, a classmap value >= n_classes.
+ *           With bit1 or bit2 nothing is read through the tables or the automaton, no hit is written, n_hits and count are 0.
+ * The other arguments mean what they mean for hmse_find_scan / hmse_find_seams.  No workspace; stream-ordered, allocate nothing, never
+ * sync.  Profile slots: hmse_regex_scan reports in 30, hmse_regex_seams in 31 (see Diagnostics below).
+ * Out of scope: anchors and \b, captures, lazy matching, matches over 256 bytes, Unicode classes, several regexes in one automaton.
+ */
+#define HMSE_REGEX_MAX_LEN   256
+#define HMSE_REGEX_MAX_TABLE 16384
+#define HMSE_REGEX_ACCEPT    0x8000u
+
+typedef struct hmse_regex {
+  uint32_t struct_size;      /* sizeof(hmse_regex) */
+  uint32_t n_states;
+  uint32_t n_classes;
+  uint32_t reach;
+  const uint16_t* table;     /* DEVICE u16[n_states * n_classes] */
+  const uint8_t* classmap;   /* DEVICE u8[256] */
+} hmse_regex;
+
+int hmse_regex_scan(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* raw_off, uint64_t n_rec, const uint32_t* mult,
+                    const hmse_regex* rx, uint64_t* hits, uint64_t hits_cap, uint64_t* n_hits, uint64_t* count, uint32_t* status,
+                    void* stream);
+int hmse_regex_seams(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* raw_off, uint64_t n_rec, const uint64_t* cuts,
+                     const uint64_t* slot, uint64_t n_chunks, const hmse_regex* rx, uint64_t* hits, uint64_t hits_cap,
+                     uint64_t* n_hits, uint64_t* count, uint32_t* status, void* stream);
+
+/*
  * Diagnostics (bench.py's roofline leg): when enabled, every entry point brackets its DOMINANT
  * kernel launch with a HIP event pair on the caller's stream.  hmse_profile_read() waits for the
  * recorded events (a host sync — never call it inside a capture), adds their durations to the
@@ -900,6 +955,7 @@ int hmse_lines_gather(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* ra
  * records) and 30 and 31 (DELTA records) (hmse_amd/csrc/l1_deflate.hip); hmse_find_scan also reports in 30, hmse_find_seams and
  * hmse_find_place in 31, hmse_sync_match in 19; hmse_findset_scan reports in 30 as well, hmse_findset_seams and hmse_findset_place in 31.
  * hmse_lines_extent and hmse_lines_gather report in 31 as well (reset the slot before reading one of them: it is shared).
+ * hmse_regex_scan reports in 30 and hmse_regex_seams in 31, too.
  * hmse_profile_counter(): work counted on the device while profiling is on — the DEFLATE match kernels add the TOKENS they
  * write to their slot (8..13, 18..23), the encode kernels the tokens they read (14, 15, 30, 31):
  * bench.py's algorithmic bytes come from these counts, not from an assumed token density.  A host sync; diagnostics only.

@@ -1,0 +1,217 @@
+// regex_emu.cpp — the kernels of hmse_amd/csrc/regex.hip run on the CPU, one std::thread per lane and a barrier for __syncthreads,
+// against a brute-force walk of the same automaton: random corpora with tiny and empty chunks, deduplicated into records with junk
+// around them in raw, runs of one byte over tile edges, full / short / no hit lists; then find_place_kernel (cut from find.hip) over
+// the sorted scan hits and the seams over the same chunk map, and a damaged automaton that the validate kernel must refuse.  No GPU:
+// this checks the kernels' LOGIC and their bounds (build it with a sanitizer), not their code objects.  Driven by tools/regex_emu.py,
+// which cuts the kernels out and writes the automata (compiled by hmse_amd/regex.py) into a file.
+#include <algorithm>
+#include <barrier>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+#include <map>
+#include <random>
+#include <string>
+#include <thread>
+#include <vector>
+#include "hmse.h"
+#define __global__
+#define __device__
+#define __host__
+#define __forceinline__ inline
+#define __shared__ static
+#define __restrict__
+#define __launch_bounds__(...)
+struct Idx { uint32_t x; };
+static thread_local Idx threadIdx, blockIdx;
+static Idx gridDim;
+static std::barrier<>* g_bar;
+static inline void __syncthreads() { g_bar->arrive_and_wait(); }
+static inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
+static inline uint32_t atomicOr(uint32_t* p, uint32_t v) { return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST); }
+#define __builtin_amdgcn_readfirstlane(x) (x)
+struct uint4 { uint32_t x, y, z, w; };
+static inline uint4 make_uint4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return uint4{a, b, c, d}; }
+static inline uint4 load_u4_unaligned(const uint8_t* p) { uint4 v; memcpy(&v, p, 16); return v; }
+template <int NT> static inline uint32_t block_exclusive_scan(uint32_t v, uint32_t*, uint32_t* total) {
+  static uint32_t arr[NT];
+  arr[threadIdx.x] = v;
+  __syncthreads();
+  uint32_t pre = 0, tot = 0;
+  for (int i = 0; i < NT; i++) { if ((uint32_t)i < threadIdx.x) pre += arr[i]; tot += arr[i]; }
+  __syncthreads();
+  *total = tot;
+  return pre;
+}
+#include "regex_kernels.inc"
+#include "place_kernel.inc"
+
+static void launch(uint32_t grid, const std::function<void()>& f) {
+  gridDim.x = grid;
+  for (uint32_t b = 0; b < grid; b++) {
+    std::barrier<> bar(RX_NT);
+    g_bar = &bar;
+    std::vector<std::thread> th;
+    for (int t = 0; t < RX_NT; t++) th.emplace_back([&, t, b] { threadIdx.x = t; blockIdx.x = b; f(); bar.arrive_and_drop(); });
+    for (auto& x : th) x.join();
+  }
+}
+typedef unsigned long long ull;
+static std::mt19937_64 rng(12345);
+static uint64_t R(uint64_t n) { return n ? rng() % n : 0; }
+static const uint8_t ALPHA[] = {'a', 'b', 'c', '\n', 'A', 'q', ' ', 'B'};
+
+struct Auto { uint32_t ns, nc, reach; std::vector<uint8_t> cm; std::vector<uint16_t> tab; };
+// the definition: the longest match of 1 .. min(reach, end - o) bytes from o, or 0
+static uint32_t walk(const Auto& A, const uint8_t* d, uint64_t o, uint64_t end) {
+  uint32_t s = 1, best = 0;
+  for (uint32_t i = 0; i < A.reach && o + i < end; i++) {
+    const uint32_t e = A.tab[s * A.nc + A.cm[d[o + i]]];
+    s = e & 0x7FFFu;
+    if (!s) break;
+    if (e & HMSE_REGEX_ACCEPT) best = i + 1;
+  }
+  return best;
+}
+
+int main(int argc, char** argv) {
+  int iters = argc > 1 ? atoi(argv[1]) : 20;
+  if (argc > 2) rng.seed(strtoull(argv[2], nullptr, 10));
+  std::vector<Auto> autos;
+  {
+    FILE* f = fopen(argc > 3 ? argv[3] : "automata.txt", "r");
+    int n = 0;
+    if (!f || fscanf(f, "%d", &n) != 1) { printf("no automata\n"); return 2; }
+    for (int a = 0; a < n; a++) {
+      Auto A; unsigned v;
+      if (fscanf(f, "%u %u %u", &A.ns, &A.nc, &A.reach) != 3) return 2;
+      for (int i = 0; i < 256; i++) { if (fscanf(f, "%u", &v) != 1) return 2; A.cm.push_back(v); }
+      for (uint32_t i = 0; i < A.ns * A.nc; i++) { if (fscanf(f, "%u", &v) != 1) return 2; A.tab.push_back(v); }
+      autos.push_back(A);
+    }
+    fclose(f);
+  }
+  int fails = 0, ran = 0;
+  for (int it = 0; it < iters && !fails; it++) {
+    const Auto& A = autos[it < (int)autos.size() ? it : R(autos.size())];
+    const int nalpha = 2 + R(sizeof ALPHA - 1);
+    uint64_t n = R(3) == 0 ? R(400) : (R(3) == 0 ? RX_TILE + R(RX_TILE) : R(6000));
+    std::vector<uint8_t> corpus(n);
+    for (auto& c : corpus) c = ALPHA[R(nalpha)];
+    if (n > 700 && R(2)) { uint64_t o = R(n - 700); for (uint64_t i = 0; i < 300 + R(400); i++) corpus[o + i] = R(2) ? 'a' : 'b'; }
+    if (n > RX_TILE + 700 && R(2)) for (uint64_t i = RX_TILE - 300; i < RX_TILE + 300; i++) corpus[i] = 'b';   // a run over a tile edge
+    std::vector<uint64_t> cuts{0};
+    while (cuts.back() < n) {
+      static const uint64_t L[] = {0, 1, 2, 3, 1, 7, 30, 200, 255, 256, 257, 3000, 40000};
+      cuts.push_back(std::min(n, cuts.back() + L[R(n > 10000 ? 13 : 11)]));
+    }
+    for (int k = R(3); k > 0; k--) cuts.push_back(n);
+    const uint64_t n_chunks = cuts.size() - 1;
+    std::map<std::string, uint64_t> seen;
+    std::vector<std::string> recs;
+    std::vector<uint64_t> slot;
+    for (uint64_t k = 0; k < n_chunks; k++) {
+      std::string c(corpus.begin() + cuts[k], corpus.begin() + cuts[k + 1]);
+      auto f = seen.find(c);
+      if (f == seen.end()) { seen[c] = recs.size(); slot.push_back(recs.size()); recs.push_back(c); } else slot.push_back(f->second);
+    }
+    if (R(2)) recs.push_back(std::string(R(50), 'a'));
+    const uint64_t lead = R(2) ? R(300) : 0, tail = R(2) ? R(300) : 0;
+    std::vector<uint8_t> raw(lead, 'a');
+    std::vector<uint64_t> raw_off{lead};
+    for (auto& r : recs) { raw.insert(raw.end(), r.begin(), r.end()); raw_off.push_back(raw.size()); }
+    for (uint64_t i = 0; i < tail; i++) raw.push_back(ALPHA[R(nalpha)]);
+    const uint64_t raw_bytes = raw.size(), n_rec = recs.size();
+    std::vector<uint32_t> mult(n_rec, 0);
+    for (auto s : slot) mult[s]++;
+    const RxDev X{A.tab.data(), A.cm.data(), A.ns, A.nc, A.reach};
+    const uint64_t nv = std::max<uint64_t>({n_rec, n_chunks, (uint64_t)A.ns * A.nc, 256});
+    // ---- scan: the scan starts of every record ----
+    std::vector<ull> want;
+    ull wc = 0;
+    for (uint64_t r = 0; r < n_rec; r++)
+      for (uint64_t p = raw_off[r]; p + A.reach <= raw_off[r + 1]; p++) {
+        const uint32_t l = walk(A, raw.data(), p, raw_off[r + 1]);
+        if (l) { want.push_back((p << 8) | (l - 1)); wc += mult[r]; }
+      }
+    const uint64_t cap = R(3) == 0 ? 0 : (R(2) ? want.size() : R(want.size() + 1));
+    std::vector<ull> hits(cap + 8, ~0ull);
+    ull nh = 0, cnt = 0; uint32_t status = 0;
+    launch(2, [&] { regex_validate_kernel(raw_off.data(), n_rec, raw_bytes, nullptr, nullptr, 0, X, nv, &status); });
+    if (status) { printf("it %d: validate status %u\n", it, status); fails++; break; }
+    const uint64_t n_tiles = (raw_bytes + RX_TILE - 1) / RX_TILE;
+    auto scan = [&](const RxDev& G, ull* h, uint64_t c, ull* pn, ull* cn, uint32_t* st) {
+      launch((uint32_t)std::min<uint64_t>(n_tiles, 1 + R(2)), [&] { regex_scan_kernel(raw.data(), raw_bytes, raw_off.data(), n_rec, R(4) ? mult.data() : mult.data(), G, c ? h : nullptr, c, pn, cn, st, n_tiles); });
+    };
+    if (n_rec && raw_bytes) scan(X, hits.data(), cap, &nh, &cnt, &status);
+    bool ok = nh == want.size() && cnt == wc && ((status & 1) != 0) == (cap && want.size() > cap) && !(status & 6);
+    for (uint64_t i = cap; i < cap + 8; i++) ok = ok && hits[i] == ~0ull;
+    std::vector<ull> got(hits.begin(), hits.begin() + std::min<uint64_t>(cap, nh));
+    std::sort(got.begin(), got.end());
+    if (cap >= want.size() && cap) ok = ok && got == want;
+    else for (auto g : got) ok = ok && std::binary_search(want.begin(), want.end(), g);
+    if (!ok) { printf("it %d: SCAN mismatch n=%llu reach=%u nh=%llu want=%zu cnt=%llu/%llu status=%u cap=%llu\n", it, (ull)n, A.reach, nh, want.size(), cnt, wc, status, (ull)cap); fails++; break; }
+    // ---- a damaged automaton: refused by the validate kernel, the scan behind it writes nothing ----
+    if (n_rec && raw_bytes) {
+      Auto D = A;
+      const int what = R(3);
+      if (what == 0) D.tab[R(D.tab.size())] = (uint16_t)(D.ns + R(100)) | (R(2) ? 0x8000u : 0u);
+      else if (what == 1) D.tab[R(D.nc)] = R(2) ? 1 : 0x8000u;
+      else D.cm[R(256)] = (uint8_t)std::min<uint32_t>(255, D.nc + R(5));
+      if (what == 2 && D.nc == 256) D = A, D.tab[0] = 1;
+      const RxDev Y{D.tab.data(), D.cm.data(), D.ns, D.nc, D.reach};
+      uint32_t st = 0; ull dn = 0, dc = 0;
+      std::vector<ull> dh(want.size() + 8, ~0ull);
+      launch(1, [&] { regex_validate_kernel(raw_off.data(), n_rec, raw_bytes, nullptr, nullptr, 0, Y, nv, &st); });
+      scan(Y, dh.data(), want.size(), &dn, &dc, &st);
+      bool dok = st == 4 && dn == 0 && dc == 0;
+      for (auto v : dh) dok = dok && v == ~0ull;
+      if (!dok) { printf("it %d: DAMAGED automaton (%d) not refused: status=%u nh=%llu\n", it, what, st, dn); fails++; break; }
+    }
+    // ---- the corpus: scan starts placed + seam starts = every occurrence once ----
+    std::vector<ull> win, wseam;
+    for (uint64_t k = 0; k < n_chunks; k++)
+      for (uint64_t o = cuts[k]; o < cuts[k + 1]; o++) {
+        const uint32_t l = walk(A, corpus.data(), o, n);
+        if (l) (cuts[k + 1] - o < A.reach ? wseam : win).push_back((o << 8) | (l - 1));
+      }
+    if (n_chunks) {
+      const uint64_t scap = R(4) == 0 ? R(wseam.size() + 1) : wseam.size();
+      std::vector<ull> sh(scap + 8, ~0ull);
+      ull snh = 0, sc = 0; status = 0;
+      launch(2, [&] { regex_validate_kernel(raw_off.data(), n_rec, raw_bytes, cuts.data(), slot.data(), n_chunks, X, nv, &status); });
+      if (status) { printf("it %d: validate(seams) status %u\n", it, status); fails++; break; }
+      if (A.reach > 1) {
+        const uint64_t nt = n_chunks * (A.reach - 1);
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((nt + RX_NT - 1) / RX_NT, 1 + R(3));
+        launch(grid, [&] { regex_seams_kernel(raw.data(), raw_off.data(), cuts.data(), slot.data(), n_chunks, X, scap ? sh.data() : nullptr, scap, &snh, &sc, &status, nt); });
+      }
+      std::vector<ull> gs(sh.begin(), sh.begin() + std::min<uint64_t>(snh, scap));
+      std::sort(gs.begin(), gs.end());
+      bool sok = snh == wseam.size() && sc == snh && ((status & 1) != 0) == (scap && wseam.size() > scap) && !(status & 6);
+      if (scap >= wseam.size()) sok = sok && (scap == 0 || gs == wseam);
+      else for (auto g : gs) sok = sok && std::binary_search(wseam.begin(), wseam.end(), g);
+      for (uint64_t i = scap; i < scap + 8; i++) sok = sok && sh[i] == ~0ull;
+      if (!sok) { printf("it %d: SEAMS mismatch n=%llu chunks=%llu reach=%u got=%llu want=%zu status=%u\n", it, (ull)n, (ull)n_chunks, A.reach, snh, wseam.size(), status); fails++; break; }
+      // place (needs the full sorted scan list): find_place_kernel passes the low byte through
+      std::vector<uint64_t> per(n_rec, 0), chunk_out{0};
+      for (auto w : want) { uint64_t r = std::upper_bound(raw_off.begin(), raw_off.end(), w >> 8) - raw_off.begin() - 1; per[r]++; }
+      for (uint64_t k = 0; k < n_chunks; k++) chunk_out.push_back(chunk_out.back() + per[slot[k]]);
+      const uint64_t total = chunk_out.back();
+      std::vector<ull> out(total + 8, ~0ull);
+      status = 0;
+      launch((uint32_t)std::max<uint64_t>(1, (total + FIND_NT - 1) / FIND_NT), [&] { find_place_kernel(want.data(), want.size(), raw_off.data(), cuts.data(), slot.data(), n_chunks, chunk_out.data(), out.data(), total, &status); });
+      bool pok = status == 0 && total == win.size() && total == wc;
+      for (uint64_t i = 0; pok && i < total; i++) pok = out[i] == win[i];
+      for (uint64_t i = total; i < total + 8; i++) pok = pok && out[i] == ~0ull;
+      if (!pok) { printf("it %d: PLACE mismatch total=%llu want=%zu status=%u\n", it, (ull)total, win.size(), status); fails++; break; }
+    }
+    ran++;
+    printf("it %d ok: n=%llu rec=%llu chunks=%llu reach=%u scan=%zu seam=%zu\n", it, (ull)n, (ull)n_rec, (ull)n_chunks, A.reach, want.size(), wseam.size());
+  }
+  printf("%d cases ran\n", ran);
+  printf(fails ? "FAILED\n" : "ALL OK\n");
+  return fails;
+}
