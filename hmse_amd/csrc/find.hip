@@ -10,9 +10,11 @@
 //                           Survivors are verified byte by byte against the patterns in LDS, clipped to their record (raw_off);
 //                           the hits of a tile are emitted after the strip with ONE reservation per workgroup;
 //   (2) find_seams_kernel — the strip of max(m) - 1 candidate starts in front of every chunk boundary, read through the chunk map;
-//   (3) find_place_kernel — the sorted in-record hits laid out at every chunk that maps to their record (POINTERs included).
+//   (3) place_kernel<8>   — the sorted in-record hits laid out at every chunk that maps to their record (chunkmap.h).
+// Every call starts with tables_validate_kernel (chunkmap.h): the kernels behind it leave when it set status bit 1.
 // No kernel holds an atomic or a cross-lane operation inside a loop that lanes leave at different times (tools/isa_audit.py).
 #include "common.h"
+#include "chunkmap.h"
 
 constexpr int FIND_NT = 256;                          // threads per workgroup
 constexpr int FIND_STRIP = 128;                       // S: bytes per lane
@@ -25,66 +27,14 @@ constexpr uint32_t FIND_PAT_BYTES = HMSE_FIND_MAX_PATTERNS * HMSE_FIND_MAX_LEN;
 // The patterns' bounds, read on the host during the call and handed to the kernels by value.
 struct FindPats { uint32_t n, max_len; uint32_t off[HMSE_FIND_MAX_PATTERNS + 1]; };
 
-__device__ __forceinline__ uint32_t find_fold_byte(uint32_t b) { return (b - 'A') < 26u ? (b | 0x20u) : b; }
-// A..Z -> a..z in the four bytes of a dword, every other value (>= 0x80 included) as it is
-__device__ __forceinline__ uint32_t find_fold_dword(uint32_t w) {
-  const uint32_t t = w & 0x7F7F7F7Fu;
-  const uint32_t ge = t + 0x3F3F3F3Fu;                // bit 7 of a byte: its low seven bits >= 'A'
-  const uint32_t gt = t + 0x25252525u;                // ...                               >  'Z'
-  return w | (((ge & ~gt & ~w) & 0x80808080u) >> 2);
-}
-
-// largest r in [0, n_rec) with raw_off[r] <= pos (0 if there is none)
-__device__ __forceinline__ uint64_t find_record_of(const uint64_t* __restrict__ raw_off, uint64_t n_rec, uint64_t pos) {
-  uint64_t a = 0, b = n_rec;
-  while (b - a > 1) {
-    const uint64_t mid = a + ((b - a) >> 1);
-    if (raw_off[mid] <= pos) a = mid; else b = mid;
-  }
-  return a;
-}
-
-// bits b of a 32-position word starting at `start` with lo <= start + b < hi
-__device__ __forceinline__ uint32_t find_range_mask(uint64_t start, uint64_t lo, uint64_t hi) {
-  uint32_t m = 0xFFFFFFFFu;
-  if (start + 32 > hi) m = start >= hi ? 0u : (0xFFFFFFFFu >> (32u - (uint32_t)(hi - start)));
-  if (start < lo) m = (lo - start >= 32) ? 0u : (m & (0xFFFFFFFFu << (uint32_t)(lo - start)));
-  return m;
-}
-
 template <bool IC>
 __device__ __forceinline__ bool find_match(const uint8_t* __restrict__ p, const uint8_t* sp, uint32_t m) {
   for (uint32_t i = 0; i < m; i++) {
     uint32_t b = p[i];
-    if (IC) b = find_fold_byte(b);
+    if (IC) b = fold_byte(b);
     if (b != sp[i]) return false;
   }
   return true;
-}
-
-// ---- tables -------------------------------------------------------------------------------------------------------------------
-// status bit 1: raw_off or cuts (or chunk_out) descending, records beyond raw_bytes, slot[k] >= n_rec, a chunk whose length is not
-// its record's.  Every later kernel of the call leaves when it finds the bit: nothing is then read through these tables.
-__global__ __launch_bounds__(FIND_NT) void find_validate_kernel(const uint64_t* __restrict__ raw_off, uint64_t n_rec, uint64_t raw_bytes,
-                                                                const uint64_t* __restrict__ cuts, const uint64_t* __restrict__ slot,
-                                                                uint64_t n_chunks, const uint64_t* __restrict__ chunk_out, uint32_t* status) {
-  const uint64_t n = n_rec > n_chunks ? n_rec : n_chunks;
-  const uint64_t stride = (uint64_t)gridDim.x * FIND_NT;
-  bool bad = false;
-  for (uint64_t i = (uint64_t)blockIdx.x * FIND_NT + threadIdx.x; i < n; i += stride) {
-    if (i < n_rec) {
-      bad |= raw_off[i] > raw_off[i + 1];
-      if (i == 0) bad |= raw_off[n_rec] > raw_bytes;
-    }
-    if (i < n_chunks) {
-      bad |= cuts[i] > cuts[i + 1];
-      const uint64_t s = slot[i];
-      if (s >= n_rec) bad = true;
-      else bad |= raw_off[s + 1] - raw_off[s] != cuts[i + 1] - cuts[i];
-      if (chunk_out) bad |= chunk_out[i] > chunk_out[i + 1] || (i == 0 && chunk_out[0] != 0);
-    }
-  }
-  if (bad) atomicOr(status, 2u);
 }
 
 // ---- scan ---------------------------------------------------------------------------------------------------------------------
@@ -101,7 +51,7 @@ __global__ __launch_bounds__(FIND_NT) __attribute__((amdgpu_waves_per_eu(4))) vo
   __shared__ uint32_t s_red[FIND_NT / 64 + 1];
   __shared__ unsigned long long s_base;
 
-  if (*status & 2u) return;                           // inconsistent tables (find_validate_kernel)
+  if (*status & 2u) return;                           // inconsistent tables (tables_validate_kernel)
   const uint32_t t = threadIdx.x;
   const uint32_t n_pat = P.n;
   const uint32_t o0 = P.off[0];       // (the bounds are read from the kernel arguments where they are used: scalar loads)
@@ -109,7 +59,7 @@ __global__ __launch_bounds__(FIND_NT) __attribute__((amdgpu_waves_per_eu(4))) vo
     const uint32_t total = P.off[n_pat] - o0;
     for (uint32_t i = t; i < total; i += FIND_NT) {
       const uint32_t b = pat[o0 + i];
-      s_pat[i] = (uint8_t)(IC ? find_fold_byte(b) : b);
+      s_pat[i] = (uint8_t)(IC ? fold_byte(b) : b);
     }
     if (!FEW)
       for (int i = 0; i < 8; i++) s_bm[t + i * FIND_NT] = 0;
@@ -172,7 +122,7 @@ __global__ __launch_bounds__(FIND_NT) __attribute__((amdgpu_waves_per_eu(4))) vo
     if (FEW) {
       if (IC) {
 #pragma unroll
-        for (int d = 0; d <= FIND_STRIP / 4; d++) w[d] = find_fold_dword(w[d]);
+        for (int d = 0; d <= FIND_STRIP / 4; d++) w[d] = fold_dword(w[d]);
       }
 #pragma unroll
       for (int g = 0; g < FIND_WORDS; g++) {
@@ -214,7 +164,7 @@ __global__ __launch_bounds__(FIND_NT) __attribute__((amdgpu_waves_per_eu(4))) vo
       }
     }
 #pragma unroll
-    for (int g = 0; g < FIND_WORDS; g++) cand[g] &= find_range_mask(gs0 + 32 * g, lo, hi);
+    for (int g = 0; g < FIND_WORDS; g++) cand[g] &= range_mask(gs0 + 32 * g, lo, hi);
 
     // ---- verify: hb = positions where at least one pattern matches inside its record, nh = (position, pattern) pairs ----
     uint32_t hb[FIND_WORDS];
@@ -223,7 +173,7 @@ __global__ __launch_bounds__(FIND_NT) __attribute__((amdgpu_waves_per_eu(4))) vo
     for (int g = 0; g < FIND_WORDS; g++) hb[g] = 0;
     uint64_t rec0 = 0;
     if (cand[0] | cand[1] | cand[2] | cand[3]) {
-      rec0 = find_record_of(raw_off, n_rec, gs0 > lo ? gs0 : lo);
+      rec0 = last_le(raw_off, 0, n_rec, gs0 > lo ? gs0 : lo);
       uint64_t r = rec0;
       auto verify_word = [&](uint32_t c, uint32_t& h, uint64_t start) {
         while (c) {
@@ -302,7 +252,7 @@ __global__ __launch_bounds__(FIND_NT) void find_seams_kernel(const uint8_t* __re
   const uint32_t n_pat = P.n, o0 = P.off[0];
   for (uint32_t i = t; i < P.off[n_pat] - o0; i += FIND_NT) {
     const uint32_t b = pat[o0 + i];
-    s_pat[i] = (uint8_t)(IC ? find_fold_byte(b) : b);
+    s_pat[i] = (uint8_t)(IC ? fold_byte(b) : b);
   }
   __syncthreads();
   const uint32_t span = P.max_len - 1;
@@ -317,7 +267,7 @@ __global__ __launch_bounds__(FIND_NT) void find_seams_kernel(const uint8_t* __re
       if (d <= c1 - c0) {
         o = c1 - d;
         uint32_t b0 = raw[raw_off[slot[c]] + (o - c0)];
-        if (IC) b0 = find_fold_byte(b0);
+        if (IC) b0 = fold_byte(b0);
         for (uint32_t j = 0; j < n_pat; j++) {
           const uint32_t po = P.off[j] - o0, m = P.off[j + 1] - P.off[j];
           if (m > d && o + m <= n && s_pat[po] == b0) {
@@ -327,7 +277,7 @@ __global__ __launch_bounds__(FIND_NT) void find_seams_kernel(const uint8_t* __re
               const uint64_t q = o + i;
               while (q >= cuts[k + 1]) k++;           // q < N = cuts[n_chunks]: k stays below n_chunks
               uint32_t b = raw[raw_off[slot[k]] + (q - cuts[k])];
-              if (IC) b = find_fold_byte(b);
+              if (IC) b = fold_byte(b);
               ok = b == s_pat[po + i];
             }
             if (ok) hm |= 1u << j;
@@ -357,40 +307,6 @@ __global__ __launch_bounds__(FIND_NT) void find_seams_kernel(const uint8_t* __re
   }
 }
 
-// ---- place --------------------------------------------------------------------------------------------------------------------
-// One thread per output element e: its chunk k (chunk_out[k] <= e < chunk_out[k + 1]), the i-th hit of record slot[k] in the sorted list.
-__global__ __launch_bounds__(FIND_NT) void find_place_kernel(const unsigned long long* __restrict__ hits, uint64_t n_hits,
-                                                             const uint64_t* __restrict__ raw_off, const uint64_t* __restrict__ cuts,
-                                                             const uint64_t* __restrict__ slot, uint64_t n_chunks,
-                                                             const uint64_t* __restrict__ chunk_out, unsigned long long* __restrict__ out,
-                                                             uint64_t out_cap, uint32_t* status) {
-  if (*status & 2u) return;
-  const uint64_t e = (uint64_t)blockIdx.x * FIND_NT + threadIdx.x;
-  const uint64_t total = chunk_out[n_chunks];
-  if (e == 0 && total > out_cap) atomicOr(status, 1u);
-  if (e >= total || e >= out_cap) return;
-  uint64_t a = 0, b = n_chunks;                       // largest k with chunk_out[k] <= e
-  while (b - a > 1) {
-    const uint64_t mid = a + ((b - a) >> 1);
-    if (chunk_out[mid] <= e) a = mid; else b = mid;
-  }
-  const uint64_t k = a, s = slot[k], r0 = raw_off[s], r1 = raw_off[s + 1];
-  uint64_t x = 0, y = n_hits;                         // first hit at or behind r0
-  while (x < y) {
-    const uint64_t mid = x + ((y - x) >> 1);
-    if ((hits[mid] >> 8) < r0) x = mid + 1; else y = mid;
-  }
-  const uint64_t idx = x + (e - chunk_out[k]);
-  bool bad = idx >= n_hits;
-  if (!bad) {
-    const unsigned long long h = hits[idx];
-    const uint64_t pos = h >> 8;
-    bad = pos < r0 || pos >= r1;
-    if (!bad) out[e] = ((cuts[k] + (pos - r0)) << 8) | (h & 0xFFu);
-  }
-  if (bad) atomicOr(status, 2u);                      // chunk_out is not the count of the record's hits
-}
-
 // ---- entry points -------------------------------------------------------------------------------------------------------------
 static int find_patterns(const uint32_t* pat_off, uint32_t n_pat, uint32_t flags, FindPats* P) {
   if (!pat_off || n_pat == 0 || n_pat > HMSE_FIND_MAX_PATTERNS || (flags & ~HMSE_FIND_IGNORE_CASE)) return HMSE_EINVAL;
@@ -406,20 +322,10 @@ static int find_patterns(const uint32_t* pat_off, uint32_t n_pat, uint32_t flags
   return HMSE_OK;
 }
 
-static uint64_t find_blocks(uint64_t threads) {
-  const uint64_t b = (threads + FIND_NT - 1) / FIND_NT;
-  return b < 1 ? 1 : b;
-}
-
+// the tables and nothing else, at this family's geometry
 static int find_validate(const uint64_t* raw_off, uint64_t n_rec, uint64_t raw_bytes, const uint64_t* cuts, const uint64_t* slot,
                          uint64_t n_chunks, const uint64_t* chunk_out, uint32_t* status, hipStream_t stream) {
-  const uint64_t n = n_rec > n_chunks ? n_rec : n_chunks;
-  if (n == 0) return HMSE_OK;
-  uint64_t nb = find_blocks(n);
-  if (nb > FIND_MAX_BLOCKS) nb = FIND_MAX_BLOCKS;
-  find_validate_kernel<<<dim3((uint32_t)nb), dim3(FIND_NT), 0, stream>>>(raw_off, n_rec, raw_bytes, cuts, slot, n_chunks, chunk_out, status);
-  HMSE_LAUNCH_CHECK();
-  return HMSE_OK;
+  return tables_validate<FIND_NT>(raw_off, n_rec, raw_bytes, cuts, slot, n_chunks, chunk_out, status, FIND_MAX_BLOCKS, stream);
 }
 
 extern "C" int hmse_find_scan(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* raw_off, uint64_t n_rec, const uint32_t* mult,
@@ -486,21 +392,5 @@ extern "C" int hmse_find_seams(const uint8_t* raw, uint64_t raw_bytes, const uin
 extern "C" int hmse_find_place(const uint64_t* hits, uint64_t n_hits, const uint64_t* raw_off, uint64_t n_rec, const uint64_t* cuts,
                                const uint64_t* slot, uint64_t n_chunks, const uint64_t* chunk_out, uint64_t* out, uint64_t out_cap,
                                uint32_t* status, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!status || (n_hits && !hits) || (out_cap && !out)) return HMSE_EINVAL;
-  if (n_chunks && (!cuts || !slot || !raw_off || !chunk_out)) return HMSE_EINVAL;
-  (void)hipGetLastError();
-  HMSE_FILL(status, 0, 4, stream);
-  if (n_chunks == 0) return HMSE_OK;
-  // raw_bytes is not an argument here: the records' end bounds nothing that is read (the hits carry the positions)
-  int rc = find_validate(raw_off, n_rec, ~0ull, cuts, slot, n_chunks, chunk_out, status, stream);
-  if (rc != HMSE_OK) return rc;
-  const uint64_t nb = find_blocks(out_cap);
-  if (nb > 0x7FFFFFFFull) return HMSE_EINVAL;
-  PROF_BEGIN(HMSE_STAGE_FIND_PLACE, stream);
-  find_place_kernel<<<dim3((uint32_t)nb), dim3(FIND_NT), 0, stream>>>((const unsigned long long*)hits, n_hits, raw_off, cuts, slot, n_chunks,
-                                                                      chunk_out, (unsigned long long*)out, out_cap, status);
-  PROF_END(HMSE_STAGE_FIND_PLACE, stream);
-  HMSE_LAUNCH_CHECK();
-  return HMSE_OK;
+  return place<8, FIND_NT>(find_validate, hits, n_hits, raw_off, n_rec, cuts, slot, n_chunks, chunk_out, out, out_cap, status, stream_);
 }

@@ -10,10 +10,11 @@
 //                              the lane walks again and stores;
 //   (2) findset_seams_kernel — one thread per (chunk, distance from its end): the window gathered through the chunk map, the same filter
 //                              (read from memory) and directory, only the patterns longer than the distance verified; count, reserve, store;
-//   (3) findset_place_kernel — find_place_kernel's job for the wider hit word.
+//   (3) place_kernel<HMSE_FINDSET_ID_BITS> — the in-record hits laid out at every chunk of their record (chunkmap.h).
 // Every call starts with findset_validate_kernel over the tables AND the set: the kernels behind it leave when it set status bit 1.
 // No kernel holds a cross-lane operation or a barrier inside a loop that lanes leave at different times (tools/isa_audit.py).
 #include "common.h"
+#include "chunkmap.h"
 
 constexpr int FSET_NT = 512;                          // threads per workgroup: two fit on a CU beside their LDS bitmaps, 4 waves per SIMD
 constexpr int FSET_STRIP = 128;                       // S: bytes per lane
@@ -30,48 +31,21 @@ struct FsetDev {
   uint64_t pat_bytes; uint32_t n, n_ids, bits, max_len, folded;
 };
 
-__device__ __forceinline__ uint32_t fset_fold_byte(uint32_t b) { return (b - 'A') < 26u ? (b | 0x20u) : b; }
-// A..Z -> a..z in the four bytes of a dword, every other value (>= 0x80 included) as it is
-__device__ __forceinline__ uint32_t fset_fold_dword(uint32_t w) {
-  const uint32_t t = w & 0x7F7F7F7Fu;
-  const uint32_t ge = t + 0x3F3F3F3Fu;                // bit 7 of a byte: its low seven bits >= 'A'
-  const uint32_t gt = t + 0x25252525u;                // ...                               >  'Z'
-  return w | (((ge & ~gt & ~w) & 0x80808080u) >> 2);
-}
 __device__ __forceinline__ uint32_t fset_hash(uint32_t key) { return key * HMSE_FINDSET_HASH; }
-
-// largest r in [0, n_rec) with raw_off[r] <= pos (0 if there is none)
-__device__ __forceinline__ uint64_t fset_record_of(const uint64_t* __restrict__ raw_off, uint64_t n_rec, uint64_t pos) {
-  uint64_t a = 0, b = n_rec;
-  while (b - a > 1) {
-    const uint64_t mid = a + ((b - a) >> 1);
-    if (raw_off[mid] <= pos) a = mid; else b = mid;
-  }
-  return a;
-}
-
-// bits b of a 32-position word starting at `start` with lo <= start + b < hi
-__device__ __forceinline__ uint32_t fset_range_mask(uint64_t start, uint64_t lo, uint64_t hi) {
-  uint32_t m = 0xFFFFFFFFu;
-  if (start + 32 > hi) m = start >= hi ? 0u : (0xFFFFFFFFu >> (32u - (uint32_t)(hi - start)));
-  if (start < lo) m = (lo - start >= 32) ? 0u : (m & (0xFFFFFFFFu << (uint32_t)(lo - start)));
-  return m;
-}
 
 template <bool IC>
 __device__ __forceinline__ bool fset_match(const uint8_t* __restrict__ p, const uint8_t* __restrict__ sp, uint32_t m) {
   for (uint32_t i = 0; i < m; i++) {
     uint32_t b = p[i];
-    if (IC) b = fset_fold_byte(b);
+    if (IC) b = fold_byte(b);
     if (b != sp[i]) return false;
   }
   return true;
 }
 
 // ---- tables and set -----------------------------------------------------------------------------------------------------------
-// status bit 1: the tables of find_validate_kernel (raw_off / cuts / chunk_out descending, records beyond raw_bytes, slot[k] >= n_rec, a
-// chunk whose length is not its record's), a corpus of 2^40 bytes or more, and the set: a directory that descends or does not cover
-// [0, n), an id >= n_ids, a byte range that descends, leaves upat or is not 4..max_len long, a key that is not the first four bytes of
+// status bit 1: tables that break a rule of chunkmap.h (tables_bad_at), a corpus of 2^40 bytes or more (a hit word holds 40 bits of
+// position), and the set: a directory that descends or does not cover [0, n), an id >= n_ids, a byte range that descends, leaves upat or is not 4..max_len long, a key that is not the first four bytes of
 // its pattern (folded ones if the set is), an entry outside its directory cell or without its bit in the bitmap.
 __global__ __launch_bounds__(FSET_NT) void findset_validate_kernel(const uint64_t* __restrict__ raw_off, uint64_t n_rec, uint64_t raw_bytes,
                                                                    const uint64_t* __restrict__ cuts, const uint64_t* __restrict__ slot,
@@ -81,18 +55,8 @@ __global__ __launch_bounds__(FSET_NT) void findset_validate_kernel(const uint64_
   const uint64_t cells = F.n ? (1ull << F.bits) : 0;
   bool bad = false;
   for (uint64_t i = (uint64_t)blockIdx.x * FSET_NT + threadIdx.x; i < n; i += stride) {
-    if (i < n_rec) {
-      bad |= raw_off[i] > raw_off[i + 1];
-      if (i == 0) bad |= raw_off[n_rec] > raw_bytes;
-    }
-    if (i < n_chunks) {
-      bad |= cuts[i] > cuts[i + 1];
-      if (i == 0) bad |= (cuts[n_chunks] >> FSET_POS_BITS) != 0;
-      const uint64_t s = slot[i];
-      if (s >= n_rec) bad = true;
-      else bad |= raw_off[s + 1] - raw_off[s] != cuts[i + 1] - cuts[i];
-      if (chunk_out) bad |= chunk_out[i] > chunk_out[i + 1] || (i == 0 && chunk_out[0] != 0);
-    }
+    bad |= tables_bad_at(i, raw_off, n_rec, raw_bytes, cuts, slot, n_chunks, chunk_out);
+    if (i == 0 && n_chunks) bad |= (cuts[n_chunks] >> FSET_POS_BITS) != 0;
     if (i < cells) {
       bad |= F.dir[i] > F.dir[i + 1];
       if (i == 0) bad |= F.dir[0] != 0 || F.dir[cells] != F.n;
@@ -102,7 +66,7 @@ __global__ __launch_bounds__(FSET_NT) void findset_validate_kernel(const uint64_
       bad |= F.uid[i] >= F.n_ids;
       if (e < a || e - a < HMSE_FINDSET_MIN_LEN || e - a > F.max_len || e > F.pat_bytes) bad = true;
       else bad |= load_u32_unaligned(F.upat + a) != key;
-      if (F.folded) bad |= fset_fold_dword(key) != key;
+      if (F.folded) bad |= fold_dword(key) != key;
       const uint32_t h = fset_hash(key), cell = h >> (32u - F.bits), bit = h >> FSET_BM_SHIFT;
       bad |= F.dir[cell] > i || F.dir[cell + 1] <= i;
       bad |= ((F.bitmap[bit >> 5] >> (bit & 31u)) & 1u) == 0;
@@ -118,7 +82,7 @@ template <bool IC, bool EMIT>
 __device__ __forceinline__ uint32_t fset_walk(const uint8_t* __restrict__ raw, uint64_t p, uint64_t end, uint32_t weight, const FsetDev& F,
                                               unsigned long long* __restrict__ hits, uint64_t hits_cap, uint64_t& wr, unsigned long long* counts) {
   uint32_t key = load_u32_unaligned(raw + p);
-  if (IC) key = fset_fold_dword(key);
+  if (IC) key = fold_dword(key);
   const uint32_t cell = fset_hash(key) >> (32u - F.bits);
   uint32_t i = F.dir[cell], i1 = F.dir[cell + 1];
   if (i1 > F.n) i1 = F.n;
@@ -182,7 +146,7 @@ __global__ __launch_bounds__(FSET_NT) void findset_scan_kernel(const uint8_t* __
     w[FSET_STRIP / 4] = ld4(gs0 + FSET_STRIP);
     if (IC) {
 #pragma unroll
-      for (int d = 0; d <= FSET_STRIP / 4; d++) w[d] = fset_fold_dword(w[d]);
+      for (int d = 0; d <= FSET_STRIP / 4; d++) w[d] = fold_dword(w[d]);
     }
 
     // ---- filter: cand = positions whose window's hash has its bit in the bitmap ----
@@ -197,7 +161,7 @@ __global__ __launch_bounds__(FSET_NT) void findset_scan_kernel(const uint8_t* __
         const uint32_t bit = fset_hash(win) >> FSET_BM_SHIFT;
         cm |= ((s_bm[bit >> 5] >> (bit & 31u)) & 1u) << k;
       }
-      cand[g] = cm & fset_range_mask(gs0 + 32 * g, lo, hi);
+      cand[g] = cm & range_mask(gs0 + 32 * g, lo, hi);
     }
 
     // ---- count: hb = positions where at least one pattern matches inside its record, nh = (position, pattern) pairs ----
@@ -207,7 +171,7 @@ __global__ __launch_bounds__(FSET_NT) void findset_scan_kernel(const uint8_t* __
     for (int g = 0; g < FSET_WORDS; g++) hb[g] = 0;
     uint64_t rec0 = 0;
     if (cand[0] | cand[1] | cand[2] | cand[3]) {
-      rec0 = fset_record_of(raw_off, n_rec, gs0 > lo ? gs0 : lo);
+      rec0 = last_le(raw_off, 0, n_rec, gs0 > lo ? gs0 : lo);
       uint64_t r = rec0, none = 0;
       auto count_word = [&](uint32_t c, uint32_t& h, uint64_t start) {
         while (c) {
@@ -260,13 +224,6 @@ __global__ __launch_bounds__(FSET_NT) void findset_scan_kernel(const uint8_t* __
 // ---- seams --------------------------------------------------------------------------------------------------------------------
 // One thread and trip per (chunk c, distance d = 1 .. max_len - 1 of the start from the chunk's end).  The start o = cuts[c + 1] - d lies in c;
 // a pattern of m bytes is a seam hit there iff m > d (it crosses cuts[c + 1]), o + m <= N and the bytes agree, read through the chunk map.
-// corpus byte q, with k a chunk at or in front of q's (k moves forward to q's chunk; q < N = cuts[n_chunks] keeps it below n_chunks)
-__device__ __forceinline__ uint32_t fset_corpus_byte(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ raw_off,
-                                                     const uint64_t* __restrict__ cuts, const uint64_t* __restrict__ slot, uint64_t q, uint64_t& k) {
-  while (q >= cuts[k + 1]) k++;
-  return raw[raw_off[slot[k]] + (q - cuts[k])];
-}
-
 template <bool IC, bool EMIT>
 __device__ __forceinline__ uint32_t fset_seam_walk(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ raw_off, const uint64_t* __restrict__ cuts,
                                                    const uint64_t* __restrict__ slot, uint64_t c, uint64_t d, uint64_t o, uint64_t n, uint32_t key,
@@ -283,8 +240,8 @@ __device__ __forceinline__ uint32_t fset_seam_walk(const uint8_t* __restrict__ r
     uint64_t k = c;
     bool ok = true;
     for (uint32_t j = 4; j < m && ok; j++) {
-      uint32_t b = fset_corpus_byte(raw, raw_off, cuts, slot, o + j, k);
-      if (IC) b = fset_fold_byte(b);
+      uint32_t b = corpus_byte(raw, raw_off, cuts, slot, o + j, k);
+      if (IC) b = fold_byte(b);
       ok = b == F.upat[a + j];
     }
     if (!ok) continue;
@@ -321,8 +278,8 @@ __global__ __launch_bounds__(FSET_NT) void findset_seams_kernel(const uint8_t* _
       if (d <= c1 - c0 && c1 - d + 4 <= n) {          // the start lies in chunk c and the key inside the corpus
         o = c1 - d;
         uint64_t k = c;
-        for (uint32_t j = 0; j < 4; j++) key |= fset_corpus_byte(raw, raw_off, cuts, slot, o + j, k) << (8 * j);
-        if (IC) key = fset_fold_dword(key);
+        for (uint32_t j = 0; j < 4; j++) key |= corpus_byte(raw, raw_off, cuts, slot, o + j, k) << (8 * j);
+        if (IC) key = fold_dword(key);
         const uint32_t bit = fset_hash(key) >> FSET_BM_SHIFT;
         if ((F.bitmap[bit >> 5] >> (bit & 31u)) & 1u)
           nh = fset_seam_walk<IC, false>(raw, raw_off, cuts, slot, c, d, o, n, key, F, nullptr, 0, none, nullptr);
@@ -342,40 +299,6 @@ __global__ __launch_bounds__(FSET_NT) void findset_seams_kernel(const uint8_t* _
       if (nh) fset_seam_walk<IC, true>(raw, raw_off, cuts, slot, c, d, o, n, key, F, hits, hits_cap, wr, counts);
     }
   }
-}
-
-// ---- place --------------------------------------------------------------------------------------------------------------------
-// One thread per output element e: its chunk k (chunk_out[k] <= e < chunk_out[k + 1]), the i-th hit of record slot[k] in the sorted list.
-__global__ __launch_bounds__(FSET_NT) void findset_place_kernel(const unsigned long long* __restrict__ hits, uint64_t n_hits,
-                                                                const uint64_t* __restrict__ raw_off, const uint64_t* __restrict__ cuts,
-                                                                const uint64_t* __restrict__ slot, uint64_t n_chunks,
-                                                                const uint64_t* __restrict__ chunk_out, unsigned long long* __restrict__ out,
-                                                                uint64_t out_cap, uint32_t* status) {
-  if (*status & 2u) return;
-  const uint64_t e = (uint64_t)blockIdx.x * FSET_NT + threadIdx.x;
-  const uint64_t total = chunk_out[n_chunks];
-  if (e == 0 && total > out_cap) atomicOr(status, 1u);
-  if (e >= total || e >= out_cap) return;
-  uint64_t a = 0, b = n_chunks;                       // largest k with chunk_out[k] <= e
-  while (b - a > 1) {
-    const uint64_t mid = a + ((b - a) >> 1);
-    if (chunk_out[mid] <= e) a = mid; else b = mid;
-  }
-  const uint64_t k = a, s = slot[k], r0 = raw_off[s], r1 = raw_off[s + 1];
-  uint64_t x = 0, y = n_hits;                         // first hit at or behind r0
-  while (x < y) {
-    const uint64_t mid = x + ((y - x) >> 1);
-    if ((hits[mid] >> HMSE_FINDSET_ID_BITS) < r0) x = mid + 1; else y = mid;
-  }
-  const uint64_t idx = x + (e - chunk_out[k]);
-  bool bad = idx >= n_hits;
-  if (!bad) {
-    const unsigned long long h = hits[idx];
-    const uint64_t pos = h >> HMSE_FINDSET_ID_BITS;
-    bad = pos < r0 || pos >= r1;
-    if (!bad) out[e] = ((cuts[k] + (pos - r0)) << HMSE_FINDSET_ID_BITS) | (h & ((1ull << HMSE_FINDSET_ID_BITS) - 1));
-  }
-  if (bad) atomicOr(status, 2u);                      // chunk_out is not the count of the record's hits
 }
 
 // ---- entry points -------------------------------------------------------------------------------------------------------------
@@ -409,6 +332,12 @@ static int fset_validate(const uint64_t* raw_off, uint64_t n_rec, uint64_t raw_b
   findset_validate_kernel<<<dim3((uint32_t)nb), dim3(FSET_NT), 0, stream>>>(raw_off, n_rec, raw_bytes, cuts, slot, n_chunks, chunk_out, F, n, status);
   HMSE_LAUNCH_CHECK();
   return HMSE_OK;
+}
+
+// no set: the tables alone, and the corpus below 2^40 bytes (hmse_findset_place)
+static int fset_validate_tables(const uint64_t* raw_off, uint64_t n_rec, uint64_t raw_bytes, const uint64_t* cuts, const uint64_t* slot,
+                                uint64_t n_chunks, const uint64_t* chunk_out, uint32_t* status, hipStream_t stream) {
+  return fset_validate(raw_off, n_rec, raw_bytes, cuts, slot, n_chunks, chunk_out, FsetDev{}, status, stream);
 }
 
 extern "C" int hmse_findset_scan(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* raw_off, uint64_t n_rec, const uint32_t* mult,
@@ -473,21 +402,5 @@ extern "C" int hmse_findset_seams(const uint8_t* raw, uint64_t raw_bytes, const 
 extern "C" int hmse_findset_place(const uint64_t* hits, uint64_t n_hits, const uint64_t* raw_off, uint64_t n_rec, const uint64_t* cuts,
                                   const uint64_t* slot, uint64_t n_chunks, const uint64_t* chunk_out, uint64_t* out, uint64_t out_cap,
                                   uint32_t* status, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!status || (n_hits && !hits) || (out_cap && !out)) return HMSE_EINVAL;
-  if (n_chunks && (!cuts || !slot || !raw_off || !chunk_out)) return HMSE_EINVAL;
-  (void)hipGetLastError();
-  HMSE_FILL(status, 0, 4, stream);
-  if (n_chunks == 0) return HMSE_OK;
-  FsetDev F = {};                                     // no set here; raw_bytes is not an argument (the hits carry the positions)
-  int rc = fset_validate(raw_off, n_rec, ~0ull, cuts, slot, n_chunks, chunk_out, F, status, stream);
-  if (rc != HMSE_OK) return rc;
-  const uint64_t nb = out_cap ? (out_cap + FSET_NT - 1) / FSET_NT : 1;
-  if (nb > 0x7FFFFFFFull) return HMSE_EINVAL;
-  PROF_BEGIN(HMSE_STAGE_FIND_PLACE, stream);
-  findset_place_kernel<<<dim3((uint32_t)nb), dim3(FSET_NT), 0, stream>>>((const unsigned long long*)hits, n_hits, raw_off, cuts, slot, n_chunks,
-                                                                         chunk_out, (unsigned long long*)out, out_cap, status);
-  PROF_END(HMSE_STAGE_FIND_PLACE, stream);
-  HMSE_LAUNCH_CHECK();
-  return HMSE_OK;
+  return place<HMSE_FINDSET_ID_BITS, FSET_NT>(fset_validate_tables, hits, n_hits, raw_off, n_rec, cuts, slot, n_chunks, chunk_out, out, out_cap, status, stream_);
 }

@@ -16,45 +16,11 @@
 //       for the rest.  lines_ranges_kernel proves every range and the prefix sum first: a refused call writes nothing.
 // No kernel holds an atomic or a cross-lane operation inside a loop that lanes leave at different times (tools/isa_audit.py).
 #include "common.h"
+#include "chunkmap.h"
 
 constexpr int LINES_NT = 256;                // four wavefronts = four hits (or ranges) per workgroup
 constexpr uint32_t LINES_TRIP = 64;          // bytes one trip looks at: one per lane
 constexpr uint32_t LINES_MAX_BLOCKS = 2048;  // of the two checking kernels; the rest by the grid stride
-
-// ---- tables -------------------------------------------------------------------------------------------------------------------
-// find_validate_kernel's rules (status bit 1): raw_off or cuts descending, records beyond raw_bytes, slot[k] >= n_rec, a chunk whose
-// length is not its record's — and cuts[0] != 0, as that kernel asks of chunk_out[0]: here the positions come from the caller, and one
-// below cuts[0] would lie in no chunk.  Every later kernel of the call reads nothing through the tables when it finds the bit.
-__global__ __launch_bounds__(LINES_NT) void lines_validate_kernel(const uint64_t* __restrict__ raw_off, uint64_t n_rec, uint64_t raw_bytes,
-                                                                  const uint64_t* __restrict__ cuts, const uint64_t* __restrict__ slot,
-                                                                  uint64_t n_chunks, uint32_t* status) {
-  const uint64_t n = n_rec > n_chunks ? n_rec : n_chunks;
-  const uint64_t stride = (uint64_t)gridDim.x * LINES_NT;
-  bool bad = false;
-  for (uint64_t i = (uint64_t)blockIdx.x * LINES_NT + threadIdx.x; i < n; i += stride) {
-    if (i < n_rec) {
-      bad |= raw_off[i] > raw_off[i + 1];
-      if (i == 0) bad |= raw_off[n_rec] > raw_bytes;
-    }
-    if (i < n_chunks) {
-      bad |= cuts[i] > cuts[i + 1] || (i == 0 && cuts[0] != 0);
-      const uint64_t s = slot[i];
-      if (s >= n_rec) bad = true;
-      else bad |= raw_off[s + 1] - raw_off[s] != cuts[i + 1] - cuts[i];
-    }
-  }
-  if (bad) atomicOr(status, 2u);
-}
-
-// largest c in [0, n_chunks) with cuts[c] <= p, for p < cuts[n_chunks]: the chunk that holds p (empty chunks hold nothing)
-__device__ __forceinline__ uint64_t lines_chunk_of(const uint64_t* __restrict__ cuts, uint64_t n_chunks, uint64_t p) {
-  uint64_t a = 0, b = n_chunks;
-  while (b - a > 1) {
-    const uint64_t mid = a + ((b - a) >> 1);
-    if (cuts[mid] <= p) a = mid; else b = mid;
-  }
-  return a;
-}
 
 // ---- extent -------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(LINES_NT) void lines_extent_kernel(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ raw_off,
@@ -65,7 +31,7 @@ __global__ __launch_bounds__(LINES_NT) void lines_extent_kernel(const uint8_t* _
   const uint64_t i = (uint64_t)blockIdx.x * (LINES_NT / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (i >= n) return;
   const uint32_t lane = lane_id();
-  const bool tables = ((uint32_t)__builtin_amdgcn_readfirstlane((int)*status) & 2u) == 0;       // lines_validate_kernel ran before this one
+  const bool tables = ((uint32_t)__builtin_amdgcn_readfirstlane((int)*status) & 2u) == 0;       // tables_validate_kernel ran before this one
   const uint64_t N = tables && n_chunks ? cuts[n_chunks] : 0;
   const uint64_t o = pos[i];
   if (!tables || o >= N) {
@@ -77,7 +43,7 @@ __global__ __launch_bounds__(LINES_NT) void lines_extent_kernel(const uint8_t* _
   }
   const uint64_t R = reach;
   const uint64_t lo = o > R ? o - R : 0, hi = R < N - o ? o + R : N;      // what may be looked at: [lo, o) and [o, hi)
-  const uint64_t c_o = lines_chunk_of(cuts, n_chunks, o);
+  const uint64_t c_o = last_le(cuts, 0, n_chunks, o);
   uint32_t fl = 0;
 
   // ---- backward: the (before + 1)-th delimiter met below o.  More than `reach` cannot be met: the count is clipped, not the answer ----
@@ -166,12 +132,12 @@ __global__ __launch_bounds__(LINES_NT) void lines_gather_kernel(const uint8_t* _
                                                                 const uint64_t* __restrict__ out_off, uint64_t n, uint8_t* __restrict__ out,
                                                                 const uint32_t* status) {
   const uint64_t i = (uint64_t)blockIdx.x * (LINES_NT / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (i >= n || __builtin_amdgcn_readfirstlane((int)*status)) return;      // a refused call writes nothing (lines_validate_kernel, lines_ranges_kernel)
+  if (i >= n || __builtin_amdgcn_readfirstlane((int)*status)) return;      // a refused call writes nothing (tables_validate_kernel, lines_ranges_kernel)
   const uint32_t lane = lane_id();
   const uint64_t s = start[i], e = end[i];
   if (s >= e) return;
   uint8_t* dst = out + out_off[i];
-  uint64_t c = lines_chunk_of(cuts, n_chunks, s), p = s;
+  uint64_t c = last_le(cuts, 0, n_chunks, s), p = s;
   while (p < e) {
     const uint64_t c0 = cuts[c], c1 = cuts[c + 1];
     if (p == c1) { c++; continue; }                    // p < e <= N: a chunk follows
@@ -193,15 +159,12 @@ __global__ __launch_bounds__(LINES_NT) void lines_gather_kernel(const uint8_t* _
 }
 
 // ---- entry points -------------------------------------------------------------------------------------------------------------
+// The table rules of chunkmap.h (status bit 1) and cuts[0] != 0: here the positions come from the caller, and one below cuts[0] would lie
+// in no chunk.  It is the rule chunk_out[0] != 0, so cuts goes in as the chunk_out as well.  Every later kernel of the call reads
+// nothing through the tables when it finds the bit.
 static int lines_validate(const uint64_t* raw_off, uint64_t n_rec, uint64_t raw_bytes, const uint64_t* cuts, const uint64_t* slot,
                           uint64_t n_chunks, uint32_t* status, hipStream_t stream) {
-  const uint64_t n = n_rec > n_chunks ? n_rec : n_chunks;
-  if (n == 0) return HMSE_OK;
-  uint64_t nb = (n + LINES_NT - 1) / LINES_NT;
-  if (nb > LINES_MAX_BLOCKS) nb = LINES_MAX_BLOCKS;
-  lines_validate_kernel<<<dim3((uint32_t)nb), dim3(LINES_NT), 0, stream>>>(raw_off, n_rec, raw_bytes, cuts, slot, n_chunks, status);
-  HMSE_LAUNCH_CHECK();
-  return HMSE_OK;
+  return tables_validate<LINES_NT>(raw_off, n_rec, raw_bytes, cuts, slot, n_chunks, /*chunk_out=*/cuts, status, LINES_MAX_BLOCKS, stream);
 }
 
 static bool lines_tables_null(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* raw_off, uint64_t n_rec, const uint64_t* cuts,

@@ -2,7 +2,8 @@
 // automaton on the host; hmse_amd/find.py StoreFinder.find_regex; include/hmse.h hmse_regex_*).
 //
 // Replaces the detour read_store -> host -> re.finditer, which decodes and scans every duplicate chunk once per occurrence.  As for
-// the literal search (find.hip) a record is looked at once and hmse_find_place lays its hits out at every chunk that maps to it:
+// the literal search (find.hip) a record is looked at once and hmse_find_place (place_kernel<8>, chunkmap.h) lays its hits out at every
+// chunk that maps to it:
 //   (1) regex_scan_kernel  — per workgroup the transition table (up to 32 KiB) and the class map go to LDS once; per tile of RX_TILE
 //                            bytes (+ 255 of overhang) every raw byte is read from HBM once, in 16-byte pieces, translated to its
 //                            byte class on the way into LDS, and the first-step filter (does this byte leave the start state alive?)
@@ -14,6 +15,7 @@
 //   (2) regex_seams_kernel — the last reach - 1 starts of every chunk, walked through the chunk map.
 // No kernel holds an atomic, a barrier or a cross-lane operation inside a loop that lanes leave at different times (tools/isa_audit.py).
 #include "common.h"
+#include "chunkmap.h"
 
 constexpr int RX_NT = 256;                            // threads per workgroup
 constexpr int RX_STRIP = 32;                          // S: bytes per lane and tile (two 16-byte pieces)
@@ -25,15 +27,6 @@ constexpr uint32_t RX_MAX_BLOCKS = 512;               // 256 CUs x 2 workgroups 
 
 // The automaton's header, handed to the kernels by value.
 struct RxDev { const uint16_t* table; const uint8_t* classmap; uint32_t n_states, n_classes, reach; };
-
-// largest r in [a, b) with raw_off[r] <= pos (a if there is none)
-__device__ __forceinline__ uint64_t rx_record_of(const uint64_t* __restrict__ raw_off, uint64_t a, uint64_t b, uint64_t pos) {
-  while (b - a > 1) {
-    const uint64_t mid = a + ((b - a) >> 1);
-    if (raw_off[mid] <= pos) a = mid; else b = mid;
-  }
-  return a;
-}
 
 // the sum of v over the workgroup, in every thread (s_sum: RX_NT entries)
 __device__ __forceinline__ unsigned long long rx_block_sum(unsigned long long v, unsigned long long* s_sum) {
@@ -53,8 +46,8 @@ __device__ __forceinline__ unsigned long long rx_block_sum(unsigned long long v,
 }
 
 // ---- tables and automaton -----------------------------------------------------------------------------------------------------
-// status bit 1: inconsistent tables, by find_validate_kernel's rules (raw_off or cuts descending, records beyond raw_bytes, slot[k] >=
-// n_rec, a chunk whose length is not its record's).  status bit 2: a bad automaton — a table entry whose low 15 bits are >= n_states,
+// status bit 1: tables that break a rule of chunkmap.h (tables_bad_at).  status bit 2: a bad automaton — a table entry whose low 15 bits
+// are >= n_states,
 // a non-zero dead row, a classmap value >= n_classes.  Every later kernel of the call leaves when it finds either bit.
 __global__ __launch_bounds__(RX_NT) void regex_validate_kernel(const uint64_t* __restrict__ raw_off, uint64_t n_rec, uint64_t raw_bytes,
                                                                const uint64_t* __restrict__ cuts, const uint64_t* __restrict__ slot,
@@ -63,16 +56,7 @@ __global__ __launch_bounds__(RX_NT) void regex_validate_kernel(const uint64_t* _
   const uint64_t n_tab = (uint64_t)X.n_states * X.n_classes;
   bool bad = false, bad_rx = false;
   for (uint64_t i = (uint64_t)blockIdx.x * RX_NT + threadIdx.x; i < n; i += stride) {
-    if (i < n_rec) {
-      bad |= raw_off[i] > raw_off[i + 1];
-      if (i == 0) bad |= raw_off[n_rec] > raw_bytes;
-    }
-    if (i < n_chunks) {
-      bad |= cuts[i] > cuts[i + 1];
-      const uint64_t s = slot[i];
-      if (s >= n_rec) bad = true;
-      else bad |= raw_off[s + 1] - raw_off[s] != cuts[i + 1] - cuts[i];
-    }
+    bad |= tables_bad_at(i, raw_off, n_rec, raw_bytes, cuts, slot, n_chunks, nullptr);
     if (i < n_tab) {
       const uint32_t e = X.table[i];
       bad_rx |= (e & 0x7FFFu) >= X.n_states || (i < X.n_classes && e != 0);
@@ -113,7 +97,7 @@ __global__ __launch_bounds__(RX_NT) void regex_scan_kernel(const uint8_t* __rest
     const uint64_t g0 = tile * (uint64_t)RX_TILE;
     if (t < 2) {
       const uint64_t last = g0 + RX_TILE - 1 < hi ? g0 + RX_TILE - 1 : hi;
-      s_rec[t] = rx_record_of(raw_off, 0, n_rec, t == 0 ? (g0 > lo ? g0 : lo) : last);
+      s_rec[t] = last_le(raw_off, 0, n_rec, t == 0 ? (g0 > lo ? g0 : lo) : last);
     }
     // ---- stage and filter: piece q of the tile = 16 bytes from HBM -> 16 classes in LDS, bit i of surv = byte i may start a match ----
     uint32_t surv = 0;                                // bits 0..15: piece t, bits 16..31: piece t + RX_NT
@@ -163,7 +147,7 @@ __global__ __launch_bounds__(RX_NT) void regex_scan_kernel(const uint8_t* __rest
       if (k < n_work) {
         const uint32_t off = s_work[k];
         const uint64_t p = g0 + off;
-        const uint64_t r = rx_record_of(raw_off, r_first, r_last + 1, p);
+        const uint64_t r = last_le(raw_off, r_first, r_last + 1, p);
         if (raw_off[r + 1] - p >= reach) {            // a scan start: the walk stays inside record r (and inside the staged bytes)
           uint32_t s = 1, best = 0;
           for (uint32_t step = 0; step < reach; step++) {

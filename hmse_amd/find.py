@@ -14,7 +14,8 @@ Definitions (tests/find_ref.py restates them in plain Python):
     bytes.lower() on both sides;
   * result: counts int64[P], and in CSR form ptr int64[P + 1], offsets int64[ptr[P]] — ascending per pattern, no offset twice.
 Sorting, prefix sums and searchsorted go through torch (plumbing, as SimilarityIndex.locate does); the byte work runs in the HIP kernels
-of hmse_amd/csrc/find.hip.  There is no CPU path.
+of hmse_amd/csrc/find.hip.  There is no CPU path.  Patterns, a PatternSet and a Regex go through ONE count / locate flow
+(StoreFinder._count, _locate over a _Query); find, find_set and find_regex add only what is theirs.
 
 A whole dictionary (up to 2^20 distinct patterns) is compiled once into a PatternSet and answered by StoreFinder.count_set / find_set with
 ONE scan and ONE seam pass (hmse_amd/csrc/findset.hip; include/hmse.h hmse_findset_*): the same definitions, the same Found.  count and
@@ -35,6 +36,7 @@ automaton, multi-byte line delimiters, routing find / find_set through the DFA.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from dataclasses import dataclass
 
 import numpy as np
@@ -70,6 +72,11 @@ class Lines:
     hits: torch.Tensor           # int64 [L]  occurrences of the pattern that fell into this extent
     counts: torch.Tensor         # int64 [P]  extents per pattern (with before = after = 0 and no cut: matching lines, grep -c)
 
+
+# Something that can be searched for — a group of at most 32 patterns, a PatternSet's long entries, one Regex: its scan and seams calls
+# (hits_cap -> (hits, n_hits, counts)), its place call and the width of the low field of its hit word.  StoreFinder._count and _locate
+# are the one flow over it; the ops functions are looked up when a call is made.
+_Query = namedtuple("_Query", "scan seams place low_bits")
 
 HMSE_LINES_START_CUT, HMSE_LINES_END_CUT, HMSE_LINES_MAX_REACH = ops.LINES_START_CUT, ops.LINES_END_CUT, ops.LINES_MAX_REACH
 
@@ -214,55 +221,97 @@ class StoreFinder:
         pat = torch.from_numpy(flat.copy()).to(self.dev) if n else None
         return pat, [off[g: min(g + GROUP, n) + 1] for g in range(0, n, GROUP)], n
 
-    def _count_group(self, pat, off, ignore_case):
-        """-> (occurrences int64[p], in-record hits of the scan, seam hits): two count-only launches."""
-        _, n_scan, c_scan = ops.find_scan(self.raw, self.raw_off, self.mult, pat, off, ignore_case, hits_cap=0)
-        _, n_seam, c_seam = ops.find_seams(self.raw, self.raw_off, self.cuts, self.slot, pat, off, ignore_case, hits_cap=0)
+    # ------------------------------------------------------------------ the one query flow
+    def _q_group(self, pat, off, ignore_case) -> _Query:
+        return _Query(lambda cap: ops.find_scan(self.raw, self.raw_off, self.mult, pat, off, ignore_case, hits_cap=cap),
+                      lambda cap: ops.find_seams(self.raw, self.raw_off, self.cuts, self.slot, pat, off, ignore_case, hits_cap=cap),
+                      lambda *a: ops.find_place(*a), 8)
+
+    def _q_set(self, ps: PatternSet) -> _Query:
+        return _Query(lambda cap: ops.findset_scan(self.raw, self.raw_off, self.mult, ps.set, hits_cap=cap),
+                      lambda cap: ops.findset_seams(self.raw, self.raw_off, self.cuts, self.slot, ps.set, hits_cap=cap),
+                      lambda *a: ops.findset_place(*a), ops.FINDSET_ID_BITS)
+
+    def _q_regex(self, r: Regex) -> _Query:
+        return _Query(lambda cap: ops.regex_scan(self.raw, self.raw_off, self.mult, r.rx, hits_cap=cap),
+                      lambda cap: ops.regex_seams(self.raw, self.raw_off, self.cuts, self.slot, r.rx, hits_cap=cap),
+                      lambda *a: ops.find_place(*a), 8)                          # (a regex hit word is find's: the length - 1 in the low byte)
+
+    def _count(self, q: _Query):
+        """-> (occurrences int64[counters of q], in-record hits of the scan, seam hits): two count-only launches."""
+        _, n_scan, c_scan = q.scan(0)
+        _, n_seam, c_seam = q.seams(0)
         return c_scan + c_seam, n_scan, n_seam
+
+    def _locate(self, q: _Query, n_scan: int, n_seam: int):
+        """-> the hit words of q with CORPUS offsets, in up to two pieces: the in-record hits laid out at every chunk of their record
+        (ascending), the seam hits (any order)."""
+        found = []
+        if n_scan:
+            hits, _, c_scan = q.scan(n_scan)
+            hits = torch.sort(hits)[0]                                           # by position in raw, then the low field
+            rec_lo = torch.searchsorted(hits, self.raw_off << q.low_bits)        # first hit of every record
+            per_chunk = (rec_lo[1:] - rec_lo[:-1])[self.slot]
+            chunk_out = torch.zeros(self.slot.numel() + 1, dtype=torch.int64, device=self.dev)
+            torch.cumsum(per_chunk, 0, out=chunk_out[1:])
+            found.append(q.place(hits, self.raw_off, self.cuts, self.slot, chunk_out, int(c_scan.sum())))
+        if n_seam:
+            found.append(q.seams(n_seam)[0])
+        return found
+
+    def _empty(self, n: int, cls=Found):
+        z = lambda k: torch.zeros(k, dtype=torch.int64, device=self.dev)
+        return cls(z(n + 1), z(0), z(n)) if cls is Found else cls(z(n + 1), z(0), z(n), z(0))
+
+    def _ptr(self, counts: torch.Tensor) -> torch.Tensor:
+        ptr = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=self.dev)
+        torch.cumsum(counts, 0, out=ptr[1:])
+        return ptr
+
+    @staticmethod
+    def _total_within(counts: torch.Tensor, max_hits: int, largest_only: bool = False) -> int:
+        """-> the sum of counts; ValueError naming the counts (or the ten largest) if it exceeds max_hits."""
+        total = int(counts.sum())
+        if total > int(max_hits):
+            if not largest_only:
+                raise ValueError(f"find: {total} occurrences exceed max_hits = {max_hits}; counts per pattern: {counts.tolist()}")
+            top = torch.topk(counts, min(10, counts.numel()))
+            worst = ", ".join(f"pattern {int(j)}: {int(c)}" for c, j in zip(top.values.tolist(), top.indices.tolist()))
+            raise ValueError(f"find: {total} occurrences exceed max_hits = {max_hits}; the largest counts: {worst}")
+        return total
+
+    @staticmethod
+    def _all_located(located: int, counted: int) -> None:
+        if located != counted:
+            raise ops.HmseError(-1, f"find: {located} occurrences located, {counted} counted")
 
     def count(self, patterns, ignore_case: bool = False) -> torch.Tensor:
         """Occurrences per pattern, int64[P] on the device: two count-only launches per 32 patterns, nothing is materialised."""
         pat, groups, n = self._groups(patterns)
         if n == 0 or self.n_records == 0:
             return torch.zeros(n, dtype=torch.int64, device=self.dev)
-        return torch.cat([self._count_group(pat, off, ignore_case)[0] for off in groups])
+        return torch.cat([self._count(self._q_group(pat, off, ignore_case))[0] for off in groups])
 
     def find(self, patterns, ignore_case: bool = False, max_hits: int = 1 << 24) -> Found:
         """Every occurrence of every pattern.  Counts first: ValueError naming the counts if their sum exceeds max_hits."""
         pat, groups, n = self._groups(patterns)
-        dev = self.dev
         if n == 0 or self.n_records == 0:
-            z = torch.zeros(n, dtype=torch.int64, device=dev)
-            return Found(torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int64, device=dev), z)
-        counted = [self._count_group(pat, off, ignore_case) for off in groups]
+            return self._empty(n)
+        qs = [self._q_group(pat, off, ignore_case) for off in groups]
+        counted = [self._count(q) for q in qs]
         counts = torch.cat([c[0] for c in counted])
-        total = int(counts.sum())
-        if total > int(max_hits):
-            raise ValueError(f"find: {total} occurrences exceed max_hits = {max_hits}; counts per pattern: {counts.tolist()}")
+        total = self._total_within(counts, max_hits)
         parts = []
-        for off, (c, n_scan, n_seam) in zip(groups, counted):
-            found = []
-            if n_scan:
-                hits, _, c_scan = ops.find_scan(self.raw, self.raw_off, self.mult, pat, off, ignore_case, hits_cap=n_scan)
-                hits = torch.sort(hits)[0]                                   # by position in raw, then pattern
-                rec_lo = torch.searchsorted(hits, self.raw_off << 8)         # first hit of every record
-                per_chunk = (rec_lo[1:] - rec_lo[:-1])[self.slot]
-                chunk_out = torch.zeros(self.slot.numel() + 1, dtype=torch.int64, device=dev)
-                torch.cumsum(per_chunk, 0, out=chunk_out[1:])
-                found.append(ops.find_place(hits, self.raw_off, self.cuts, self.slot, chunk_out, int(c_scan.sum())))
-            if n_seam:
-                found.append(ops.find_seams(self.raw, self.raw_off, self.cuts, self.slot, pat, off, ignore_case, hits_cap=n_seam)[0])
+        for q, (c, n_scan, n_seam) in zip(qs, counted):
+            found = self._locate(q, n_scan, n_seam)
             if found:
                 h = torch.cat(found)
                 key = torch.sort(((h & 0xFF) << 56) | (h >> 8))[0]          # by (pattern, offset): offsets stay below 2^56
                 parts.append(key & ((1 << 56) - 1))
-        offsets = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int64, device=dev)
-        ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(counts, 0, out=ptr[1:])
-        if offsets.numel() != total:
-            raise ops.HmseError(-1, f"find: {offsets.numel()} occurrences located, {total} counted")
+        offsets = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int64, device=self.dev)
+        ptr = self._ptr(counts)
+        self._all_located(offsets.numel(), total)
         return Found(ptr, offsets, counts)
-
 
     # ------------------------------------------------------------------ from a hit to its line
     def lines(self, found, delim: bytes = b"\n", before: int = 0, after: int = 0, reach: int = 1 << 16) -> Lines:
@@ -353,18 +402,20 @@ class StoreFinder:
         return pset
 
     def _count_unique(self, ps: PatternSet):
-        """-> (occurrences int64[n_unique], in-record hits of the set's scan, its seam hits, [(group, in-record, seam) of the short ones])."""
+        """-> (occurrences int64[n_unique], in-record hits of the set's scan, its seam hits, [(unique ids, query, in-record hits, seam
+        hits) of every group of short patterns])."""
         counts = torch.zeros(ps.n_unique, dtype=torch.int64, device=self.dev)
         n_scan = n_seam = 0
         if ps.n_entries:
-            _, n_scan, c_scan = ops.findset_scan(self.raw, self.raw_off, self.mult, ps.set, hits_cap=0)
-            _, n_seam, c_seam = ops.findset_seams(self.raw, self.raw_off, self.cuts, self.slot, ps.set, hits_cap=0)
-            counts += c_scan + c_seam
+            c, n_scan, n_seam = self._count(self._q_set(ps))
+            counts += c
         short = []
         for g, off in ps.short_groups():
-            c, a, b = self._count_group(ps.short_pat, off, ps.ignore_case)
-            counts[ps.short_ids_d[g: g + len(off) - 1]] = c
-            short.append((g, off, a, b))
+            q = self._q_group(ps.short_pat, off, ps.ignore_case)
+            c, a, b = self._count(q)
+            ids = ps.short_ids_d[g: g + len(off) - 1]
+            counts[ids] = c
+            short.append((ids, q, a, b))
         return counts, n_scan, n_seam, short
 
     def count_set(self, pset: PatternSet) -> torch.Tensor:
@@ -381,54 +432,21 @@ class StoreFinder:
         ps = self._set_of(pset)
         dev, n = self.dev, ps.n_patterns
         if n == 0 or self.n_records == 0:
-            z = torch.zeros(n, dtype=torch.int64, device=dev)
-            return Found(torch.zeros(n + 1, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int64, device=dev), z)
+            return self._empty(n)
         cu, n_scan, n_seam, short = self._count_unique(ps)
         counts = cu[ps.index_d]
-        total = int(counts.sum())
-        if total > int(max_hits):
-            top = torch.topk(counts, min(10, n))
-            worst = ", ".join(f"pattern {int(j)}: {int(c)}" for c, j in zip(top.values.tolist(), top.indices.tolist()))
-            raise ValueError(f"find: {total} occurrences exceed max_hits = {max_hits}; the largest counts: {worst}")
+        total = self._total_within(counts, max_hits, largest_only=True)
         B, ID = ops.FINDSET_ID_BITS, (1 << ops.FINDSET_ID_BITS) - 1
-        keys = []                                                               # unique pattern << 40 | corpus offset
-        if n_scan:
-            hits, _, c_scan = ops.findset_scan(self.raw, self.raw_off, self.mult, ps.set, hits_cap=n_scan)
-            hits = torch.sort(hits)[0]                                           # by position in raw, then id (positions stay below 2^39)
-            rec_lo = torch.searchsorted(hits, self.raw_off << B)                 # first hit of every record
-            per_chunk = (rec_lo[1:] - rec_lo[:-1])[self.slot]
-            chunk_out = torch.zeros(self.slot.numel() + 1, dtype=torch.int64, device=dev)
-            torch.cumsum(per_chunk, 0, out=chunk_out[1:])
-            h = ops.findset_place(hits, self.raw_off, self.cuts, self.slot, chunk_out, int(c_scan.sum()))
-            keys.append(((h & ID) << 40) | (h >> B))
-        if n_seam:
-            h = ops.findset_seams(self.raw, self.raw_off, self.cuts, self.slot, ps.set, hits_cap=n_seam)[0]
-            keys.append(((h & ID) << 40) | (h >> B))
-        for g, off, a, b in short:                                               # the 1..3-byte patterns: the grouped kernels
-            ids = ps.short_ids_d[g: g + len(off) - 1]
-            if a:
-                hits, _, c_scan = ops.find_scan(self.raw, self.raw_off, self.mult, ps.short_pat, off, ps.ignore_case, hits_cap=a)
-                hits = torch.sort(hits)[0]
-                rec_lo = torch.searchsorted(hits, self.raw_off << 8)
-                per_chunk = (rec_lo[1:] - rec_lo[:-1])[self.slot]
-                chunk_out = torch.zeros(self.slot.numel() + 1, dtype=torch.int64, device=dev)
-                torch.cumsum(per_chunk, 0, out=chunk_out[1:])
-                h = ops.find_place(hits, self.raw_off, self.cuts, self.slot, chunk_out, int(c_scan.sum()))
-                keys.append((ids[h & 0xFF] << 40) | (h >> 8))
-            if b:
-                h = ops.find_seams(self.raw, self.raw_off, self.cuts, self.slot, ps.short_pat, off, ps.ignore_case, hits_cap=b)[0]
-                keys.append((ids[h & 0xFF] << 40) | (h >> 8))
+        # unique pattern << 40 | corpus offset (positions stay below 2^40); the 1..3-byte patterns come from the grouped kernels
+        keys = [((h & ID) << 40) | (h >> B) for h in self._locate(self._q_set(ps), n_scan, n_seam)]
+        for ids, q, a, b in short:
+            keys += [(ids[h & 0xFF] << 40) | (h >> 8) for h in self._locate(q, a, b)]
         found = torch.sort(torch.cat(keys))[0] & ((1 << 40) - 1) if keys else torch.zeros(0, dtype=torch.int64, device=dev)
-        if found.numel() != int(cu.sum()):
-            raise ops.HmseError(-1, f"find: {found.numel()} occurrences located, {int(cu.sum())} counted")
+        self._all_located(found.numel(), int(cu.sum()))
         # expand the unique patterns' lists back to the caller's patterns
-        ptr_u = torch.zeros(ps.n_unique + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(cu, 0, out=ptr_u[1:])
-        ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(counts, 0, out=ptr[1:])
+        ptr_u, ptr = self._ptr(cu), self._ptr(counts)
         src = torch.repeat_interleave(ptr_u[:-1][ps.index_d] - ptr[:-1], counts) + torch.arange(total, dtype=torch.int64, device=dev)
         return Found(ptr, found[src], counts)
-
 
     # ------------------------------------------------------------------ regular expressions
     def _regexes(self, rx):
@@ -440,53 +458,32 @@ class StoreFinder:
                 raise ValueError(f"find: the Regex lives on {r.dev}, the finder on {self.dev}")
         return rxs
 
-    def _count_regex(self, r: Regex):
-        """-> (occurrences int64[1], scan hits, seam hits): two count-only launches."""
-        _, n_scan, c_scan = ops.regex_scan(self.raw, self.raw_off, self.mult, r.rx, hits_cap=0)
-        _, n_seam, c_seam = ops.regex_seams(self.raw, self.raw_off, self.cuts, self.slot, r.rx, hits_cap=0)
-        return c_scan + c_seam, n_scan, n_seam
-
     def count_regex(self, rx) -> torch.Tensor:
         """Occurrences per regex, int64[P] on the device (`rx`: a Regex, or a list of them, answered one after the other): two
         count-only launches per regex, nothing is materialised."""
         rxs = self._regexes(rx)
         if not rxs or self.n_records == 0:
             return torch.zeros(len(rxs), dtype=torch.int64, device=self.dev)
-        return torch.cat([self._count_regex(r)[0] for r in rxs])
+        return torch.cat([self._count(self._q_regex(r))[0] for r in rxs])
 
     def find_regex(self, rx, max_hits: int = 1 << 24) -> RegexFound:
         """Every occurrence of every regex, with its length.  Counts first: ValueError naming the counts if their sum exceeds max_hits."""
-        rxs = self._regexes(rx)
-        n, dev = len(rxs), self.dev
-        z = lambda k: torch.zeros(k, dtype=torch.int64, device=dev)
+        qs = [self._q_regex(r) for r in self._regexes(rx)]
+        n = len(qs)
         if n == 0 or self.n_records == 0:
-            return RegexFound(z(n + 1), z(0), z(n), z(0))
-        counted = [self._count_regex(r) for r in rxs]
+            return self._empty(n, RegexFound)
+        counted = [self._count(q) for q in qs]
         counts = torch.cat([c[0] for c in counted])
-        total = int(counts.sum())
-        if total > int(max_hits):
-            raise ValueError(f"find: {total} occurrences exceed max_hits = {max_hits}; counts per pattern: {counts.tolist()}")
+        total = self._total_within(counts, max_hits)
         parts = []
-        for r, (c, n_scan, n_seam) in zip(rxs, counted):
-            found = []
-            if n_scan:
-                hits, _, c_scan = ops.regex_scan(self.raw, self.raw_off, self.mult, r.rx, hits_cap=n_scan)
-                hits = torch.sort(hits)[0]                                   # by position in raw
-                rec_lo = torch.searchsorted(hits, self.raw_off << 8)         # first hit of every record
-                per_chunk = (rec_lo[1:] - rec_lo[:-1])[self.slot]
-                chunk_out = torch.zeros(self.slot.numel() + 1, dtype=torch.int64, device=dev)
-                torch.cumsum(per_chunk, 0, out=chunk_out[1:])
-                found.append(ops.find_place(hits, self.raw_off, self.cuts, self.slot, chunk_out, int(c_scan.sum())))
-            if n_seam:
-                found.append(ops.regex_seams(self.raw, self.raw_off, self.cuts, self.slot, r.rx, hits_cap=n_seam)[0])
+        for q, (c, n_scan, n_seam) in zip(qs, counted):
+            found = self._locate(q, n_scan, n_seam)
             if found:
                 parts.append(torch.sort(torch.cat(found))[0])                # by corpus offset: one length per start
-        h = torch.cat(parts) if parts else z(0)
-        ptr = z(n + 1)
-        torch.cumsum(counts, 0, out=ptr[1:])
-        if h.numel() != total:
-            raise ops.HmseError(-1, f"find: {h.numel()} occurrences located, {total} counted")
-        return RegexFound(ptr, h >> 8, counts, (h & 0xFF) + 1)
+        h = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int64, device=self.dev)
+        ptr = self._ptr(counts)
+        self._all_located(h.numel(), total)
+        return RegexFound(ptr, h >> 8, counts, (h & 0xFF) + 1)                   # the length split: length - 1 is the low byte
 
     def grep_regex(self, rx, delim: bytes = b"\n", before: int = 0, after: int = 0, reach: int = 1 << 16, max_hits: int = 1 << 24) -> Lines:
         """lines(find_regex(rx, max_hits), delim, before, after, reach): per regex the lines that hold a match's start."""

@@ -738,20 +738,27 @@ def _find_bounds(pat: torch.Tensor, pat_off):
     return (C.c_uint32 * len(off))(*off), len(off) - 1
 
 
-def _find_hits(call, where: str, n_pat: int, hits_cap: int | None, dev):
-    """The calling convention hmse_find_scan and hmse_find_seams share: `call(hits, cap, meta, counts)` enqueues one; meta = [n_hits,
-    status].  hits_cap 0: count only; None: sized by a count-only call.  A list that ran out (status bit 0) is filled by ONE more call
-    with hits_cap = n_hits (as l2_cdc repeats with the larger candidate list).  -> (hits int64[n_hits], n_hits, counts int64[n_pat])."""
+_BAD_TABLES = ((2, "inconsistent tables"),)
+_BAD_TABLES_OR_AUTOMATON = _BAD_TABLES + ((4, "bad automaton"),)
+
+
+def _hit_list(call, where: str, n_counts: int, hits_cap: int | None, dev, refuse=_BAD_TABLES):
+    """The calling convention the scan and seams entry points of hmse_find_*, hmse_findset_* and hmse_regex_* share: `call(hits, cap,
+    meta, counts)` enqueues one; meta = [n_hits, status]; `counts` has n_counts entries.  `refuse`: (status bit, message) pairs, the
+    first one set raises.  hits_cap 0: count only; None: sized by a count-only call.  A list that ran out (status bit 0) is filled by
+    ONE more call with hits_cap = n_hits (as l2_cdc repeats with the larger candidate list).
+    -> (hits int64[n_hits], n_hits, counts int64[n_counts])."""
     cap = hits_cap
     for _ in range(3):
         hits = _buf(max(int(cap or 0), 1), torch.int64, dev)
         meta = _buf(2, torch.int64, dev, fill=0)      # [n_hits, status]
-        counts = _buf(n_pat, torch.int64, dev, fill=0)
+        counts = _buf(n_counts, torch.int64, dev, fill=0)
         _check(call(hits, int(cap or 0), meta, counts), where)
         n_hits, status = (int(v) for v in meta.tolist())
         status &= 0xFFFFFFFF
-        if status & 2:
-            raise HmseError(-1, f"{where}: inconsistent tables (device status {status:#x})")
+        for bit, what in refuse:
+            if status & bit:
+                raise HmseError(-1, f"{where}: {what} (device status {status:#x})")
         if cap is None or (status & 1):
             if cap is not None and cap >= n_hits:
                 break
@@ -763,17 +770,33 @@ def _find_hits(call, where: str, n_pat: int, hits_cap: int | None, dev):
     raise HmseError(-2, f"{where}: the hit list ran out twice ({n_hits} hits, {cap} entries)")
 
 
+def _records_args(where: str, raw, raw_off, mult, more=()) -> int:
+    """The "records" arguments of a scan: raw, raw_off and the optional mult.  -> n_rec."""
+    for t, nm in ((raw, "raw"), (raw_off, "raw_off")) + more + (((mult, "mult"),) if mult is not None else ()):
+        _require_gpu(t, nm)
+    n_rec = raw_off.numel() - 1
+    if n_rec < 0 or (mult is not None and mult.numel() != n_rec):
+        raise HmseError(-1, f"{where}: raw_off / mult do not match")
+    return n_rec
+
+
+def _chunk_map_args(where: str, raw, raw_off, cuts, slot, more=()) -> int:
+    """The "chunk map" arguments: raw, raw_off, cuts and slot (and what else the call takes on the device).  -> n_chunks."""
+    for t, nm in ((raw, "raw"), (raw_off, "raw_off"), (cuts, "cuts"), (slot, "slot")) + more:
+        _require_gpu(t, nm)
+    n_chunks = slot.numel()
+    if cuts.numel() != n_chunks + 1 or raw_off.numel() < 1:
+        raise HmseError(-1, f"{where}: cuts / slot / raw_off do not match")
+    return n_chunks
+
+
 def find_scan(raw: torch.Tensor, raw_off: torch.Tensor, mult: torch.Tensor | None, pat: torch.Tensor, pat_off, ignore_case: bool = False,
               hits_cap: int | None = None, raw_bytes: int | None = None):
     """hmse_find_scan: every match of the patterns (`pat` uint8 on the device, `pat_off` host bounds) lying wholly inside one record
     [raw_off[r], raw_off[r + 1]) of `raw`.  -> (hits int64[n] = position in raw << 8 | pattern, any order; n_hits; counts int64[P] =
     per pattern the sum of mult[record] (int32, None: 1 each)).  hits_cap 0: count only (hits empty).  Replaces the read_store +
     host bytes.find loop."""
-    for t, nm in ((raw, "raw"), (raw_off, "raw_off"), (pat, "pat")) + (((mult, "mult"),) if mult is not None else ()):
-        _require_gpu(t, nm)
-    n_rec = raw_off.numel() - 1
-    if n_rec < 0 or (mult is not None and mult.numel() != n_rec):
-        raise HmseError(-1, "find_scan: raw_off / mult do not match")
+    n_rec = _records_args("find_scan", raw, raw_off, mult, ((pat, "pat"),))
     bounds, n_pat = _find_bounds(pat, pat_off)
     nb = raw.numel() if raw_bytes is None else int(raw_bytes)
     flags = FIND_IGNORE_CASE if ignore_case else 0
@@ -781,18 +804,14 @@ def find_scan(raw: torch.Tensor, raw_off: torch.Tensor, mult: torch.Tensor | Non
     call = lambda hits, cap, meta, counts: lib.hmse_find_scan(_ptr(raw) if raw.numel() else None, nb, _ptr(raw_off), max(n_rec, 0), _ptr(mult),
                                                               _ptr(pat), bounds, n_pat, flags, _ptr(hits) if cap else None, cap,
                                                               meta.data_ptr(), _ptr(counts), meta.data_ptr() + 8, _stream())
-    return _find_hits(call, "hmse_find_scan", n_pat, hits_cap, raw_off.device)
+    return _hit_list(call, "hmse_find_scan", n_pat, hits_cap, raw_off.device)
 
 
 def find_seams(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, pat: torch.Tensor, pat_off,
                ignore_case: bool = False, hits_cap: int | None = None):
     """hmse_find_seams: the occurrences that start in a chunk and end behind it, read through the chunk map (`cuts` int64[n + 1],
     `slot` int64[n]: the record of every chunk).  -> (hits int64[n] = corpus offset << 8 | pattern, any order; n_hits; counts)."""
-    for t, nm in ((raw, "raw"), (raw_off, "raw_off"), (cuts, "cuts"), (slot, "slot"), (pat, "pat")):
-        _require_gpu(t, nm)
-    n_chunks = slot.numel()
-    if cuts.numel() != n_chunks + 1 or raw_off.numel() < 1:
-        raise HmseError(-1, "find_seams: cuts / slot / raw_off do not match")
+    n_chunks = _chunk_map_args("find_seams", raw, raw_off, cuts, slot, ((pat, "pat"),))
     bounds, n_pat = _find_bounds(pat, pat_off)
     flags = FIND_IGNORE_CASE if ignore_case else 0
     lib = _lib.hip_lib()
@@ -800,42 +819,44 @@ def find_seams(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slo
     call = lambda hits, cap, meta, counts: lib.hmse_find_seams(keep(raw), raw.numel(), _ptr(raw_off), raw_off.numel() - 1, _ptr(cuts), keep(slot),
                                                                n_chunks, _ptr(pat), bounds, n_pat, flags, _ptr(hits) if cap else None, cap,
                                                                meta.data_ptr(), _ptr(counts), meta.data_ptr() + 8, _stream())
-    return _find_hits(call, "hmse_find_seams", n_pat, hits_cap, cuts.device)
+    return _hit_list(call, "hmse_find_seams", n_pat, hits_cap, cuts.device)
+
+
+def _place(name: str, hits, raw_off, cuts, slot, chunk_out, n_out: int) -> torch.Tensor:
+    """hmse_find_place and hmse_findset_place: one kernel template, two widths of the hit word's low field (csrc/chunkmap.h)."""
+    for t, nm in ((hits, "hits"), (raw_off, "raw_off"), (cuts, "cuts"), (slot, "slot"), (chunk_out, "chunk_out")):
+        _require_gpu(t, nm)
+    n_chunks = slot.numel()
+    if cuts.numel() != n_chunks + 1 or chunk_out.numel() != n_chunks + 1 or raw_off.numel() < 1:
+        raise HmseError(-1, f"{name}: cuts / slot / chunk_out do not match")
+    dev = cuts.device
+    out = _buf(max(int(n_out), 1), torch.int64, dev)
+    status = _buf(1, torch.int32, dev, fill=0)
+    keep = lambda t: _ptr(t) if t.numel() else None
+    rc = getattr(_lib.hip_lib(), "hmse_" + name)(keep(hits), hits.numel(), _ptr(raw_off), raw_off.numel() - 1, _ptr(cuts), keep(slot), n_chunks,
+                                                 _ptr(chunk_out), _ptr(out) if n_out else None, int(n_out), _ptr(status), _stream())
+    _check(rc, "hmse_" + name)
+    st = int(status.item())
+    if st:
+        raise HmseError(-2 if st == 1 else -1, f"hmse_{name} device status {st:#x}"
+                        + (": inconsistent tables" if st & 2 else ": chunk_out[-1] exceeds the output"))
+    return out[:int(n_out)]
 
 
 def find_place(hits: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, chunk_out: torch.Tensor, n_out: int) -> torch.Tensor:
     """hmse_find_place: the scan's hits, SORTED ascending, laid out at every chunk that maps to their record.  `chunk_out` int64
     [n_chunks + 1]: exclusive prefix sum of the number of hits of record slot[k]; n_out = chunk_out[-1].  -> int64[n_out] =
     corpus offset << 8 | pattern, ascending."""
-    for t, nm in ((hits, "hits"), (raw_off, "raw_off"), (cuts, "cuts"), (slot, "slot"), (chunk_out, "chunk_out")):
-        _require_gpu(t, nm)
-    n_chunks = slot.numel()
-    if cuts.numel() != n_chunks + 1 or chunk_out.numel() != n_chunks + 1 or raw_off.numel() < 1:
-        raise HmseError(-1, "find_place: cuts / slot / chunk_out do not match")
-    dev = cuts.device
-    out = _buf(max(int(n_out), 1), torch.int64, dev)
-    status = _buf(1, torch.int32, dev, fill=0)
-    keep = lambda t: _ptr(t) if t.numel() else None
-    rc = _lib.hip_lib().hmse_find_place(keep(hits), hits.numel(), _ptr(raw_off), raw_off.numel() - 1, _ptr(cuts), keep(slot), n_chunks,
-                                        _ptr(chunk_out), _ptr(out) if n_out else None, int(n_out), _ptr(status), _stream())
-    _check(rc, "hmse_find_place")
-    st = int(status.item())
-    if st:
-        raise HmseError(-2 if st == 1 else -1, f"hmse_find_place device status {st:#x}"
-                        + (": inconsistent tables" if st & 2 else ": chunk_out[-1] exceeds the output"))
-    return out[:int(n_out)]
+    return _place("find_place", hits, raw_off, cuts, slot, chunk_out, n_out)
 
 
 def _lines_tables(where: str, raw, raw_off, cuts, slot, more):
-    for t, nm in ((raw, "raw"), (raw_off, "raw_off"), (cuts, "cuts"), (slot, "slot")) + more:
-        _require_gpu(t, nm)
+    _chunk_map_args(where, raw, raw_off, cuts, slot, more)
     for t, nm in ((raw_off, "raw_off"), (cuts, "cuts"), (slot, "slot")) + more:
         if t.dtype != torch.int64:
             raise HmseError(-1, f"{where}: {nm} must be torch.int64 (the bits of the u64 array)")
     if raw.dtype != torch.uint8:
         raise HmseError(-1, f"{where}: raw must be torch.uint8")
-    if cuts.numel() != slot.numel() + 1 or raw_off.numel() < 1:
-        raise HmseError(-1, f"{where}: cuts / slot / raw_off do not match")
 
 
 def lines_extent(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, pos: torch.Tensor, delim: int = 0x0A,
@@ -919,56 +940,32 @@ def findset_scan(raw: torch.Tensor, raw_off: torch.Tensor, mult: torch.Tensor | 
                  raw_bytes: int | None = None):
     """hmse_findset_scan: every match of the set's patterns lying wholly inside one record of `raw` (find_scan's contract).
     -> (hits int64[n] = position in raw << 24 | id, any order; n_hits; counts int64[n_ids] weighted by mult)."""
-    for t, nm in ((raw, "raw"), (raw_off, "raw_off")) + (((mult, "mult"),) if mult is not None else ()):
-        _require_gpu(t, nm)
-    n_rec = raw_off.numel() - 1
-    if n_rec < 0 or (mult is not None and mult.numel() != n_rec):
-        raise HmseError(-1, "findset_scan: raw_off / mult do not match")
+    n_rec = _records_args("findset_scan", raw, raw_off, mult)
     hdr, flags = _findset_args(fs)
     nb = raw.numel() if raw_bytes is None else int(raw_bytes)
     lib = _lib.hip_lib()
     call = lambda hits, cap, meta, counts: lib.hmse_findset_scan(_ptr(raw) if raw.numel() else None, nb, _ptr(raw_off), max(n_rec, 0), _ptr(mult),
                                                                  C.byref(hdr), flags, _ptr(hits) if cap else None, cap, meta.data_ptr(),
                                                                  _ptr(counts) if fs.n_ids else None, meta.data_ptr() + 8, _stream())
-    return _find_hits(call, "hmse_findset_scan", int(fs.n_ids), hits_cap, raw_off.device)
+    return _hit_list(call, "hmse_findset_scan", int(fs.n_ids), hits_cap, raw_off.device)
 
 
 def findset_seams(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, fs: FindSet, hits_cap: int | None = None):
     """hmse_findset_seams: the set's occurrences that start in a chunk and end behind it (find_seams' contract).
     -> (hits int64[n] = corpus offset << 24 | id, any order; n_hits; counts int64[n_ids])."""
-    for t, nm in ((raw, "raw"), (raw_off, "raw_off"), (cuts, "cuts"), (slot, "slot")):
-        _require_gpu(t, nm)
-    n_chunks = slot.numel()
-    if cuts.numel() != n_chunks + 1 or raw_off.numel() < 1:
-        raise HmseError(-1, "findset_seams: cuts / slot / raw_off do not match")
+    n_chunks = _chunk_map_args("findset_seams", raw, raw_off, cuts, slot)
     hdr, flags = _findset_args(fs)
     lib = _lib.hip_lib()
     keep = lambda t: _ptr(t) if t.numel() else None
     call = lambda hits, cap, meta, counts: lib.hmse_findset_seams(keep(raw), raw.numel(), _ptr(raw_off), raw_off.numel() - 1, _ptr(cuts), keep(slot),
                                                                   n_chunks, C.byref(hdr), flags, _ptr(hits) if cap else None, cap, meta.data_ptr(),
                                                                   _ptr(counts) if fs.n_ids else None, meta.data_ptr() + 8, _stream())
-    return _find_hits(call, "hmse_findset_seams", int(fs.n_ids), hits_cap, cuts.device)
+    return _hit_list(call, "hmse_findset_seams", int(fs.n_ids), hits_cap, cuts.device)
 
 
 def findset_place(hits: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, chunk_out: torch.Tensor, n_out: int) -> torch.Tensor:
     """hmse_findset_place: find_place for the hit word position << 24 | id.  -> int64[n_out] = corpus offset << 24 | id, ascending."""
-    for t, nm in ((hits, "hits"), (raw_off, "raw_off"), (cuts, "cuts"), (slot, "slot"), (chunk_out, "chunk_out")):
-        _require_gpu(t, nm)
-    n_chunks = slot.numel()
-    if cuts.numel() != n_chunks + 1 or chunk_out.numel() != n_chunks + 1 or raw_off.numel() < 1:
-        raise HmseError(-1, "findset_place: cuts / slot / chunk_out do not match")
-    dev = cuts.device
-    out = _buf(max(int(n_out), 1), torch.int64, dev)
-    status = _buf(1, torch.int32, dev, fill=0)
-    keep = lambda t: _ptr(t) if t.numel() else None
-    rc = _lib.hip_lib().hmse_findset_place(keep(hits), hits.numel(), _ptr(raw_off), raw_off.numel() - 1, _ptr(cuts), keep(slot), n_chunks,
-                                           _ptr(chunk_out), _ptr(out) if n_out else None, int(n_out), _ptr(status), _stream())
-    _check(rc, "hmse_findset_place")
-    st = int(status.item())
-    if st:
-        raise HmseError(-2 if st == 1 else -1, f"hmse_findset_place device status {st:#x}"
-                        + (": inconsistent tables" if st & 2 else ": chunk_out[-1] exceeds the output"))
-    return out[:int(n_out)]
+    return _place("findset_place", hits, raw_off, cuts, slot, chunk_out, n_out)
 
 
 REGEX_MAX_LEN, REGEX_MAX_TABLE, REGEX_ACCEPT = 256, 16384, 0x8000
@@ -996,62 +993,30 @@ def _regex_args(rx: Regex):
     return rx.header()
 
 
-def _regex_hits(call, where: str, hits_cap, dev):
-    """_find_hits for the one count and the three status bits of hmse_regex_*: a list that ran out (bit 0) is filled by ONE more call
-    with hits_cap = n_hits.  -> (hits int64[n_hits], n_hits, count int64[1])."""
-    cap = hits_cap
-    for _ in range(3):
-        hits = _buf(max(int(cap or 0), 1), torch.int64, dev)
-        meta = _buf(2, torch.int64, dev, fill=0)      # [n_hits, status]
-        count = _buf(1, torch.int64, dev, fill=0)
-        _check(call(hits, int(cap or 0), meta, count), where)
-        n_hits, status = (int(v) for v in meta.tolist())
-        status &= 0xFFFFFFFF
-        if status & 6:
-            raise HmseError(-1, f"{where}: {'inconsistent tables' if status & 2 else 'bad automaton'} (device status {status:#x})")
-        if cap is None or (status & 1):
-            if cap is not None and cap >= n_hits:
-                break
-            cap = n_hits                              # exact: the second call cannot run out
-            if cap == 0:
-                return hits[:0], 0, count
-            continue
-        return hits[:min(n_hits, int(cap))], n_hits, count
-    raise HmseError(-2, f"{where}: the hit list ran out twice ({n_hits} hits, {cap} entries)")
-
-
 def regex_scan(raw: torch.Tensor, raw_off: torch.Tensor, mult: torch.Tensor | None, rx: Regex, hits_cap: int | None = None,
                raw_bytes: int | None = None):
     """hmse_regex_scan: the occurrence of the regex at every SCAN start p of every record (raw_off[r + 1] - p >= reach).
     -> (hits int64[n] = position in raw << 8 | (length - 1), any order; n_hits; count int64[1] = the sum of mult[record] over the hits
     (int32, None: 1 each)).  hits_cap 0: count only; None: sized by a count-only call.  HmseError for inconsistent tables (device
     status bit 1) or a bad automaton (bit 2)."""
-    for t, nm in ((raw, "raw"), (raw_off, "raw_off")) + (((mult, "mult"),) if mult is not None else ()):
-        _require_gpu(t, nm)
-    n_rec = raw_off.numel() - 1
-    if n_rec < 0 or (mult is not None and mult.numel() != n_rec):
-        raise HmseError(-1, "regex_scan: raw_off / mult do not match")
+    n_rec = _records_args("regex_scan", raw, raw_off, mult)
     hdr = _regex_args(rx)
     nb = raw.numel() if raw_bytes is None else int(raw_bytes)
     lib = _lib.hip_lib()
     call = lambda hits, cap, meta, counts: lib.hmse_regex_scan(_ptr(raw) if raw.numel() else None, nb, _ptr(raw_off), max(n_rec, 0), _ptr(mult),
                                                                C.byref(hdr), _ptr(hits) if cap else None, cap, meta.data_ptr(), _ptr(counts),
                                                                meta.data_ptr() + 8, _stream())
-    return _regex_hits(call, "hmse_regex_scan", hits_cap, raw_off.device)
+    return _hit_list(call, "hmse_regex_scan", 1, hits_cap, raw_off.device, _BAD_TABLES_OR_AUTOMATON)
 
 
 def regex_seams(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, rx: Regex, hits_cap: int | None = None):
     """hmse_regex_seams: the occurrence of the regex at every SEAM start o of every chunk (cuts[k + 1] - o < reach), walked through
     the chunk map.  -> (hits int64[n] = corpus offset << 8 | (length - 1), any order; n_hits; count int64[1] = n_hits)."""
-    for t, nm in ((raw, "raw"), (raw_off, "raw_off"), (cuts, "cuts"), (slot, "slot")):
-        _require_gpu(t, nm)
-    n_chunks = slot.numel()
-    if cuts.numel() != n_chunks + 1 or raw_off.numel() < 1:
-        raise HmseError(-1, "regex_seams: cuts / slot / raw_off do not match")
+    n_chunks = _chunk_map_args("regex_seams", raw, raw_off, cuts, slot)
     hdr = _regex_args(rx)
     lib = _lib.hip_lib()
     keep = lambda t: _ptr(t) if t.numel() else None
     call = lambda hits, cap, meta, counts: lib.hmse_regex_seams(keep(raw), raw.numel(), _ptr(raw_off), raw_off.numel() - 1, _ptr(cuts), keep(slot),
                                                                 n_chunks, C.byref(hdr), _ptr(hits) if cap else None, cap, meta.data_ptr(),
                                                                 _ptr(counts), meta.data_ptr() + 8, _stream())
-    return _regex_hits(call, "hmse_regex_seams", hits_cap, cuts.device)
+    return _hit_list(call, "hmse_regex_seams", 1, hits_cap, cuts.device, _BAD_TABLES_OR_AUTOMATON)

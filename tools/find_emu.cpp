@@ -2,7 +2,8 @@
 // brute-force search: random corpora with tiny and empty chunks, deduplicated into records with junk around them in raw, 1..32 patterns of
 // 1..256 bytes, both filters, both case modes, full / short / no hit lists; then seams and place over the same chunk map.  No GPU: this
 // checks the kernels' LOGIC and their bounds (build it with a sanitizer), not their code objects.  Driven by tools/find_emu.py, which cuts
-// the kernels out of find.hip (everything in front of its entry points) into find_kernels.inc.
+// the kernels out of find.hip (everything in front of its entry points) into find_kernels.inc; the validate and place kernels come
+// from hmse_amd/csrc/chunkmap.h, included as it is.
 #include <algorithm>
 #include <barrier>
 #include <cstdint>
@@ -16,27 +17,7 @@
 #include <thread>
 #include <vector>
 #include "hmse.h"
-#define __global__
-#define __device__
-#define __host__
-#define __forceinline__ inline
-#define __shared__ static
-#define __restrict__
-#define __launch_bounds__(...)
-struct uint4 { uint32_t x, y, z, w; };
-static inline uint4 make_uint4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return uint4{a, b, c, d}; }
-struct Idx { uint32_t x; };
-static thread_local Idx threadIdx, blockIdx;
-static Idx gridDim;
-static std::barrier<>* g_bar;
-static inline void __syncthreads() { g_bar->arrive_and_wait(); }
-static inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
-static inline uint32_t atomicOr(uint32_t* p, uint32_t v) { return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST); }
-static inline uint32_t emu_alignbyte(uint32_t hi, uint32_t lo, uint32_t b) { return (uint32_t)(((((uint64_t)hi) << 32) | lo) >> (8 * (b & 3))); }
-#define __builtin_amdgcn_alignbyte emu_alignbyte
-#define __builtin_amdgcn_readfirstlane(x) (x)
-static inline uint4 load_u4_unaligned(const uint8_t* p) { uint4 v; memcpy(&v, p, 16); return v; }
-static inline uint32_t load_u32_unaligned(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
+#include "hip_on_cpu.h"
 template <int NT> static inline uint32_t block_exclusive_scan(uint32_t v, uint32_t*, uint32_t* total) {
   static uint32_t arr[NT];
   arr[threadIdx.x] = v;
@@ -47,6 +28,7 @@ template <int NT> static inline uint32_t block_exclusive_scan(uint32_t v, uint32
   *total = tot;
   return pre;
 }
+#include "chunkmap.h"
 #include "find_kernels.inc"
 
 static void launch(uint32_t grid, const std::function<void()>& f) {
@@ -141,7 +123,7 @@ int main(int argc, char** argv) {
     const uint64_t cap = R(3) == 0 ? 0 : (R(2) ? want.size() : R(want.size() + 1));
     std::vector<ull> hits(cap + 8, ~0ull), counts(np, 0);
     ull nh = 0; uint32_t status = 0;
-    launch(1, [&] { find_validate_kernel(raw_off.data(), n_rec, raw_bytes, nullptr, nullptr, 0, nullptr, &status); });
+    launch(1, [&] { tables_validate_kernel<FIND_NT>(raw_off.data(), n_rec, raw_bytes, nullptr, nullptr, 0, nullptr, &status); });
     if (status) { printf("it %d: validate status %u\n", it, status); fails++; break; }
     if (n_rec && raw_bytes) {
       const uint64_t n_tiles = (raw_bytes + FIND_TILE - 1) / FIND_TILE;
@@ -173,7 +155,7 @@ int main(int argc, char** argv) {
     if (n_chunks) {
       std::vector<ull> sh(wseam.size() + 8, ~0ull), sc(np, 0);
       ull snh = 0; status = 0;
-      launch(2, [&] { find_validate_kernel(raw_off.data(), n_rec, raw_bytes, cuts.data(), slot.data(), n_chunks, nullptr, &status); });
+      launch(2, [&] { tables_validate_kernel<FIND_NT>(raw_off.data(), n_rec, raw_bytes, cuts.data(), slot.data(), n_chunks, nullptr, &status); });
       if (status) { printf("it %d: validate(seams) status %u\n", it, status); fails++; break; }
       if (P.max_len >= 2) {
         const uint64_t nt = n_chunks * (P.max_len - 1);
@@ -197,8 +179,8 @@ int main(int argc, char** argv) {
       const uint64_t total = chunk_out.back();
       std::vector<ull> out(total + 8, ~0ull);
       status = 0;
-      launch(1, [&] { find_validate_kernel(raw_off.data(), n_rec, ~0ull, cuts.data(), slot.data(), n_chunks, chunk_out.data(), &status); });
-      launch((uint32_t)std::max<uint64_t>(1, (total + FIND_NT - 1) / FIND_NT), [&] { find_place_kernel(hs.data(), hs.size(), raw_off.data(), cuts.data(), slot.data(), n_chunks, chunk_out.data(), out.data(), total, &status); });
+      launch(1, [&] { tables_validate_kernel<FIND_NT>(raw_off.data(), n_rec, ~0ull, cuts.data(), slot.data(), n_chunks, chunk_out.data(), &status); });
+      launch((uint32_t)std::max<uint64_t>(1, (total + FIND_NT - 1) / FIND_NT), [&] { place_kernel<8, FIND_NT>(hs.data(), hs.size(), raw_off.data(), cuts.data(), slot.data(), n_chunks, chunk_out.data(), out.data(), total, &status); });
       bool pok = status == 0 && total == win.size();
       for (uint64_t i = 0; pok && i < total; i++) pok = (out[i] >> 8) == win[i].first && (out[i] & 255) == win[i].second;
       for (uint64_t i = total; i < total + 8; i++) pok = pok && out[i] == ~0ull;

@@ -3,7 +3,8 @@
 // 1..300 patterns of 4..256 bytes (nested prefixes, shared keys), both case modes, full / short / no hit lists; then seams and place over
 // the same chunk map, and a damaged set that the validate kernel must refuse.  No GPU: this checks the kernels' LOGIC and their bounds
 // (build it with a sanitizer), not their code objects.  Driven by tools/findset_emu.py, which cuts the kernels out of findset.hip
-// (everything in front of its entry points) into findset_kernels.inc.
+// (everything in front of its entry points) into findset_kernels.inc; the table rules and the place kernel come from
+// hmse_amd/csrc/chunkmap.h, included as it is.
 #include <algorithm>
 #include <barrier>
 #include <cstdint>
@@ -19,27 +20,7 @@
 #include <tuple>
 #include <vector>
 #include "hmse.h"
-#define __global__
-#define __device__
-#define __host__
-#define __forceinline__ inline
-#define __shared__ static
-#define __restrict__
-#define __launch_bounds__(...)
-struct Idx { uint32_t x; };
-static thread_local Idx threadIdx, blockIdx;
-static Idx gridDim;
-static std::barrier<>* g_bar;
-static inline void __syncthreads() { g_bar->arrive_and_wait(); }
-static inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
-static inline uint32_t atomicOr(uint32_t* p, uint32_t v) { return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST); }
-static inline uint32_t emu_alignbyte(uint32_t hi, uint32_t lo, uint32_t b) { return (uint32_t)(((((uint64_t)hi) << 32) | lo) >> (8 * (b & 3))); }
-#define __builtin_amdgcn_alignbyte emu_alignbyte
-#define __builtin_amdgcn_readfirstlane(x) (x)
-struct uint4 { uint32_t x, y, z, w; };
-static inline uint4 make_uint4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return uint4{a, b, c, d}; }
-static inline uint4 load_u4_unaligned(const uint8_t* p) { uint4 v; memcpy(&v, p, 16); return v; }
-static inline uint32_t load_u32_unaligned(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
+#include "hip_on_cpu.h"
 template <int NT> static inline uint32_t block_exclusive_scan(uint32_t v, uint32_t*, uint32_t* total) {
   static uint32_t arr[NT];
   arr[threadIdx.x] = v;
@@ -50,6 +31,7 @@ template <int NT> static inline uint32_t block_exclusive_scan(uint32_t v, uint32
   *total = tot;
   return pre;
 }
+#include "chunkmap.h"
 #include "findset_kernels.inc"
 
 static void launch(uint32_t grid, const std::function<void()>& f) {
@@ -252,7 +234,7 @@ int main(int argc, char** argv) {
       status = 0;
       FsetDev none; memset(&none, 0, sizeof none);
       launch(1, [&] { findset_validate_kernel(raw_off.data(), n_rec, ~0ull, cuts.data(), slot.data(), n_chunks, chunk_out.data(), none, std::max(n_rec, n_chunks), &status); });
-      launch((uint32_t)std::max<uint64_t>(1, (total + FSET_NT - 1) / FSET_NT), [&] { findset_place_kernel(hs.data(), hs.size(), raw_off.data(), cuts.data(), slot.data(), n_chunks, chunk_out.data(), out.data(), total, &status); });
+      launch((uint32_t)std::max<uint64_t>(1, (total + FSET_NT - 1) / FSET_NT), [&] { place_kernel<HMSE_FINDSET_ID_BITS, FSET_NT>(hs.data(), hs.size(), raw_off.data(), cuts.data(), slot.data(), n_chunks, chunk_out.data(), out.data(), total, &status); });
       bool pok = status == 0 && total == win.size();
       for (uint64_t i = 0; pok && i < total; i++) pok = (out[i] >> HMSE_FINDSET_ID_BITS) == win[i].first && (out[i] & IDM) == win[i].second;
       for (uint64_t i = total; i < total + 8; i++) pok = pok && out[i] == ~0ull;

@@ -25,6 +25,7 @@ def main():
         open(os.path.join(td, "findset_kernels.inc"), "w").write(kernels)
         exe = os.path.join(td, "findset_emu")
         cmd = ["g++", "-std=c++20", "-O1", "-g", "-pthread", "-Wno-attributes", "-I", td, "-I", os.path.join(ROOT, "include"),
+               "-I", os.path.join(ROOT, "hmse_amd", "csrc"),
                os.path.join(ROOT, "tools", "findset_emu.cpp"), "-o", exe]
         if a.sanitize:
             cmd[1:1] = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]

@@ -4,7 +4,8 @@
 // table and raw in heap blocks of exactly the declared size (a sanitizer sees a read one byte outside), outputs that start poisoned
 // with a guard behind them, bad positions, inconsistent tables, refused gathers.  No GPU: this checks the kernels' LOGIC and bounds
 // (build it with a sanitizer), not their code object.  Driven by tools/lines_emu.py, which cuts the kernels out of lines.hip
-// (everything between the geometry constants and the entry points) into lines_kernels.inc.
+// (everything between the geometry constants and the entry points) into lines_kernels.inc; the validate kernel comes from
+// hmse_amd/csrc/chunkmap.h and gets cuts as its chunk_out as well, as lines.hip's launcher hands it over.
 #include <barrier>
 #include <cstdint>
 #include <cstdio>
@@ -18,20 +19,9 @@
 #include <thread>
 #include <vector>
 #include "hmse.h"
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-#define __launch_bounds__(...)
-struct uint4 { uint32_t x, y, z, w; };
-struct Idx { uint32_t x; };
-static thread_local Idx threadIdx, blockIdx;
-static Idx gridDim;
+#include "hip_on_cpu.h"
 static inline uint32_t lane_id() { return threadIdx.x & 63u; }
-#define __builtin_amdgcn_readfirstlane(x) (x)
 static inline uint32_t mbcnt64(uint64_t m) { return (uint32_t)__builtin_popcountll(m & ((1ull << lane_id()) - 1ull)); }
-static inline uint4 load_u4_unaligned(const uint8_t* p) { uint4 v; memcpy(&v, p, 16); return v; }
-static inline uint32_t atomicOr(uint32_t* p, uint32_t v) { return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST); }
 // a ballot of the 64 lanes of one wavefront: every lane of the wavefront must arrive (the kernels' loops are wave-uniform, or this hangs)
 static unsigned long long g_bits[4];
 static std::barrier<>* g_wave[4];
@@ -45,6 +35,7 @@ static inline unsigned long long __ballot(int p) {
   g_wave[w]->arrive_and_wait();
   return v;
 }
+#include "chunkmap.h"
 #include "lines_kernels.inc"
 
 static void launch(uint32_t grid, const std::function<void()>& f) {
@@ -148,7 +139,7 @@ int main(int argc, char** argv) {
       std::vector<uint8_t> fl(n + 2, 0xA5);
       auto ST = exact(st); auto EN = exact(en); auto FL = exact(fl);
       uint32_t status = 0, want_status = broken ? 2u : 0u;
-      launch(1, [&] { lines_validate_kernel(RO.get(), n_rec, raw_bytes, CU.get(), SL.get(), n_chunks, &status); });
+      launch(1, [&] { tables_validate_kernel<LINES_NT>(RO.get(), n_rec, raw_bytes, CU.get(), SL.get(), n_chunks, CU.get(), &status); });
       launch((uint32_t)((n + LINES_NT / 64 - 1) / (LINES_NT / 64)), [&] {
         lines_extent_kernel(RAW.get(), RO.get(), CU.get(), SL.get(), n_chunks, POS.get(), n, d, b, a, reach, ST.get(), EN.get(), FL.get(), &status);
       });
@@ -194,7 +185,7 @@ int main(int argc, char** argv) {
       std::unique_ptr<uint8_t[]> OUT(new uint8_t[mis + out_cap + 1]);      // (+ 1: a block of its own also when nothing is to be written)
       memset(OUT.get(), 0xA5, mis + out_cap + 1);
       uint32_t status = 0;
-      launch(1, [&] { lines_validate_kernel(RO.get(), n_rec, raw_bytes, CU.get(), SL.get(), n_chunks, &status); });
+      launch(1, [&] { tables_validate_kernel<LINES_NT>(RO.get(), n_rec, raw_bytes, CU.get(), SL.get(), n_chunks, CU.get(), &status); });
       launch(1, [&] { lines_ranges_kernel(CU.get(), n_chunks, S.get(), E.get(), OFF.get(), n, out_cap, &status); });
       launch((uint32_t)((n + LINES_NT / 64 - 1) / (LINES_NT / 64)), [&] {
         lines_gather_kernel(RAW.get(), RO.get(), CU.get(), SL.get(), n_chunks, S.get(), E.get(), OFF.get(), n, OUT.get() + mis, &status);

@@ -26,6 +26,7 @@ def main():
         open(os.path.join(td, "lines_kernels.inc"), "w").write(kernels)
         exe = os.path.join(td, "lines_emu")
         cmd = ["g++", "-std=c++20", "-O1", "-g", "-pthread", "-Wno-attributes", "-I", td, "-I", os.path.join(ROOT, "include"),
+               "-I", os.path.join(ROOT, "hmse_amd", "csrc"),
                os.path.join(ROOT, "tools", "lines_emu.cpp"), "-o", exe]
         if a.sanitize:
             cmd[1:1] = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]

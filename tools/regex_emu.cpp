@@ -1,6 +1,6 @@
 // regex_emu.cpp — the kernels of hmse_amd/csrc/regex.hip run on the CPU, one std::thread per lane and a barrier for __syncthreads,
 // against a brute-force walk of the same automaton: random corpora with tiny and empty chunks, deduplicated into records with junk
-// around them in raw, runs of one byte over tile edges, full / short / no hit lists; then find_place_kernel (cut from find.hip) over
+// around them in raw, runs of one byte over tile edges, full / short / no hit lists; then place_kernel<8> (hmse_amd/csrc/chunkmap.h) over
 // the sorted scan hits and the seams over the same chunk map, and a damaged automaton that the validate kernel must refuse.  No GPU:
 // this checks the kernels' LOGIC and their bounds (build it with a sanitizer), not their code objects.  Driven by tools/regex_emu.py,
 // which cuts the kernels out and writes the automata (compiled by hmse_amd/regex.py) into a file.
@@ -17,24 +17,7 @@
 #include <thread>
 #include <vector>
 #include "hmse.h"
-#define __global__
-#define __device__
-#define __host__
-#define __forceinline__ inline
-#define __shared__ static
-#define __restrict__
-#define __launch_bounds__(...)
-struct Idx { uint32_t x; };
-static thread_local Idx threadIdx, blockIdx;
-static Idx gridDim;
-static std::barrier<>* g_bar;
-static inline void __syncthreads() { g_bar->arrive_and_wait(); }
-static inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
-static inline uint32_t atomicOr(uint32_t* p, uint32_t v) { return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST); }
-#define __builtin_amdgcn_readfirstlane(x) (x)
-struct uint4 { uint32_t x, y, z, w; };
-static inline uint4 make_uint4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return uint4{a, b, c, d}; }
-static inline uint4 load_u4_unaligned(const uint8_t* p) { uint4 v; memcpy(&v, p, 16); return v; }
+#include "hip_on_cpu.h"
 template <int NT> static inline uint32_t block_exclusive_scan(uint32_t v, uint32_t*, uint32_t* total) {
   static uint32_t arr[NT];
   arr[threadIdx.x] = v;
@@ -45,8 +28,8 @@ template <int NT> static inline uint32_t block_exclusive_scan(uint32_t v, uint32
   *total = tot;
   return pre;
 }
+#include "chunkmap.h"
 #include "regex_kernels.inc"
-#include "place_kernel.inc"
 
 static void launch(uint32_t grid, const std::function<void()>& f) {
   gridDim.x = grid;
@@ -195,14 +178,14 @@ int main(int argc, char** argv) {
       else for (auto g : gs) sok = sok && std::binary_search(wseam.begin(), wseam.end(), g);
       for (uint64_t i = scap; i < scap + 8; i++) sok = sok && sh[i] == ~0ull;
       if (!sok) { printf("it %d: SEAMS mismatch n=%llu chunks=%llu reach=%u got=%llu want=%zu status=%u\n", it, (ull)n, (ull)n_chunks, A.reach, snh, wseam.size(), status); fails++; break; }
-      // place (needs the full sorted scan list): find_place_kernel passes the low byte through
+      // place (needs the full sorted scan list): place_kernel<8> passes the low byte through
       std::vector<uint64_t> per(n_rec, 0), chunk_out{0};
       for (auto w : want) { uint64_t r = std::upper_bound(raw_off.begin(), raw_off.end(), w >> 8) - raw_off.begin() - 1; per[r]++; }
       for (uint64_t k = 0; k < n_chunks; k++) chunk_out.push_back(chunk_out.back() + per[slot[k]]);
       const uint64_t total = chunk_out.back();
       std::vector<ull> out(total + 8, ~0ull);
       status = 0;
-      launch((uint32_t)std::max<uint64_t>(1, (total + FIND_NT - 1) / FIND_NT), [&] { find_place_kernel(want.data(), want.size(), raw_off.data(), cuts.data(), slot.data(), n_chunks, chunk_out.data(), out.data(), total, &status); });
+      launch((uint32_t)std::max<uint64_t>(1, (total + RX_NT - 1) / RX_NT), [&] { place_kernel<8, RX_NT>(want.data(), want.size(), raw_off.data(), cuts.data(), slot.data(), n_chunks, chunk_out.data(), out.data(), total, &status); });
       bool pok = status == 0 && total == win.size() && total == wc;
       for (uint64_t i = 0; pok && i < total; i++) pok = out[i] == win[i];
       for (uint64_t i = total; i < total + 8; i++) pok = pok && out[i] == ~0ull;

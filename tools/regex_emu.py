@@ -1,6 +1,6 @@
 """The regex-search kernels (hmse_amd/csrc/regex.hip) on the CPU against a brute-force search: no GPU needed.
     python tools/regex_emu.py [--iters 20] [--seed 12345] [--sanitize]
-Cuts the kernels out of regex.hip (everything between its geometry constants and its entry points) and find_place_kernel out of find.hip,
+Cuts the kernels out of regex.hip (everything between its geometry constants and its entry points; the place kernel comes with chunkmap.h),
 compiles them with tools/regex_emu.cpp (g++ -std=c++20: one std::thread per lane, std::barrier for __syncthreads, a plain prefix sum
 for block_exclusive_scan) and runs random cases through validate, scan, place and seams (and a damaged automaton the validate kernel
 must refuse).  The automata come from hmse_amd/regex.py (numpy only) and are handed to the program in a file.  --sanitize builds that
@@ -27,11 +27,8 @@ def main():
     csrc = os.path.join(ROOT, "hmse_amd", "csrc")
     src = open(os.path.join(csrc, "regex.hip")).read()
     kernels = src[src.index("constexpr int RX_NT"): src.index("// ---- entry points")]
-    fsrc = open(os.path.join(csrc, "find.hip")).read()
-    place = "constexpr int FIND_NT = 256;\n" + fsrc[fsrc.index("// ---- place"): fsrc.index("// ---- entry points")]
     with tempfile.TemporaryDirectory() as td:
         open(os.path.join(td, "regex_kernels.inc"), "w").write(kernels)
-        open(os.path.join(td, "place_kernel.inc"), "w").write(place)
         with open(os.path.join(td, "automata.txt"), "w") as f:      # per automaton: n_states n_classes reach, 256 classes, the table
             f.write(f"{len(PATTERNS)}\n")
             for pat, fl in PATTERNS:
@@ -39,6 +36,7 @@ def main():
                 f.write(f"{r.n_states} {r.n_classes} {r.reach}\n" + " ".join(map(str, r.classmap.tolist())) + "\n" + " ".join(map(str, r.table.tolist())) + "\n")
         exe = os.path.join(td, "regex_emu")
         cmd = ["g++", "-std=c++20", "-O1", "-g", "-pthread", "-Wno-attributes", "-I", td, "-I", os.path.join(ROOT, "include"),
+               "-I", os.path.join(ROOT, "hmse_amd", "csrc"),
                os.path.join(ROOT, "tools", "regex_emu.cpp"), "-o", exe]
         if a.sanitize:
             cmd[1:1] = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
