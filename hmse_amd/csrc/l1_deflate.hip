@@ -684,12 +684,22 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     // [anchor, anchor + run), and not at anchor + run", from which the matcher below knows the exact common prefix of any
     // position p in that run with its candidate p - d WITHOUT reading a byte.  The match results stay those of the
     // definition (the oracle's serial walk): a hint only replaces one candidate's byte compare by its known outcome.
-    uint32_t* const anch = mark;   // u32[ceil(L / 64)]: d | run << 16, 0 = none (DICT only)
+    //
+    // Backward extent (anchb): the same wavefront also compares up to 128 bytes BEHIND the anchor along the same diagonal and
+    // records back = number of x in [pa - back, pa) with W[x] == W[x - d], counted down from pa - 1, never below the chunk's first
+    // position or the window's first byte.  Together with the run this is the same kind of statement about the window, about the
+    // stretch [pa - back, pa + run).  It makes NO position hinted (rule 2c and hint_of read the forward runs only): the walk of
+    // an unhinted position in front of the anchor — the positions between an edit and the end of its 64-byte block, whose own
+    // anchors' runs ended at the edit — uses it for the ONE candidate on that diagonal, see known_of below.
+    uint32_t* const anch = mark;   // u32[ceil(L / 64) + 2]: d | run << 16, 0 = none (DICT only); two zero words behind the last anchor
+    uint8_t* const anchb = (uint8_t*)(mark + (LCAP / 64 + 2));   // u8[ceil(L / 64) + 2]: back, 0 = none (the mark words hold one BIT per position: room for both)
+    static_assert(LCAP % 64 == 0 && (LCAP / 64 + 2) * 4 + LCAP / 64 + 2 <= LY::MARK_SZ, "anchors and their backward extents share the mark area");
     if constexpr (DICT) {
       const uint32_t n_anch = (L + 63u) >> 6;
+      if (t < 2u) { anch[n_anch + t] = 0; anchb[n_anch + t] = 0; }
       for (uint32_t a0 = wave; a0 < n_anch; a0 += NT / 64) {
         const uint32_t pa = Dl + (a0 << 6);
-        uint32_t word = 0;
+        uint32_t word = 0, back = 0;
         if (pa + 4 <= T) {
           const uint32_t h = hash4(ld32a(W, pa));
           const uint32_t lo = h ? cur_get(cur, h - 1) : 0u, hi = cur_get(cur, h);
@@ -726,9 +736,31 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
             if (mm) { const uint32_t fl = (uint32_t)__builtin_ctzll(mm); run = 8u * fl + (uint32_t)__builtin_amdgcn_readlane((int)n, (int)fl); }
             if (run > T - pa) run = T - pa;
             word = d | (run << 16);
+            // 128 bytes behind the anchor, 8 per lane of the first 16 (lane j: [pa - 8j - 8, pa - 8j), counted from its top byte down);
+            // a lane whose candidate side would begin in front of the window's first byte does not compare: the stretch then ends
+            // up to 7 bytes early, which is still a true statement
+            const uint32_t qa0 = pa - d;
+            uint32_t nb = 8;
+            if (lane < 16u) {
+              nb = 0;
+              if (qa0 >= off + 8u) {
+                uint64_t ya[1], yb[1];
+                ldNa<1>(W, qa0 - off - 8u, ya); ldNa<1>(W, pa - off - 8u, yb);
+                const uint64_t y = ya[0] ^ yb[0];
+                nb = y ? (uint32_t)__builtin_clzll(y) >> 3 : 8u;
+              }
+            }
+            const uint64_t mb = __ballot(nb < 8u);
+            back = 128;
+            if (mb) {   // (the first mismatching lane's count, 0..7, read out of three ballots: scalar work, no cross-lane read)
+              const uint32_t fl = (uint32_t)__builtin_ctzll(mb);
+              const uint64_t n0 = __ballot((nb & 1u) != 0), n1 = __ballot((nb & 2u) != 0), n2 = __ballot((nb & 4u) != 0);
+              back = 8u * fl + (uint32_t)((n0 >> fl) & 1ull) + 2u * (uint32_t)((n1 >> fl) & 1ull) + 4u * (uint32_t)((n2 >> fl) & 1ull);
+            }
+            if (back > (a0 << 6)) back = a0 << 6;   // chunk positions only
           }
         }
-        anch[a0] = word;   // every lane, same value
+        anch[a0] = word; anchb[a0] = (uint8_t)back;   // every lane, same values
       }
       __syncthreads();
     }
@@ -762,6 +794,27 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         if (m > bm) { bm = m; bq = p - d; }
       }
       return bm;
+    };
+    // What the anchors of the NEXT two blocks know about chunk position p (an unhinted one: the walk asks): p lies in the backward
+    // stretch of anchor a' = (pa', d', run', back') iff pa' - p <= back', and then its common prefix with the candidate p - d' is
+    // known without a read: it ends where the anchor's run does, min(pa' + run' - p, maxlen) — a run of 512 saw no mismatch and
+    // means maxlen, as in hint_of; a shorter one ends AT a mismatch or at the window's end, so the length is exact either way.
+    // Returns candidate | length << 16 of the longer statement, 0 = none (anchb is 0 where there is no anchor).
+    [[maybe_unused]] auto known_of = [&](uint32_t p, uint32_t maxlen) -> uint32_t {
+      const uint32_t a1 = ((p - Dl) >> 6) + 1u;
+      uint32_t kf = 0;
+#pragma unroll
+      for (uint32_t f = 0; f < 2; f++) {
+        const uint32_t w = anch[a1 + f], bk = anchb[a1 + f], pa = Dl + ((a1 + f) << 6);
+        if (pa - p <= bk) {
+          const uint32_t d = w & 0xFFFFu, run = w >> 16;
+          uint32_t m = pa + run - p;
+          if (run >= 512u || m > maxlen) m = maxlen;
+          const uint32_t v = (p - d) | (m << 16);
+          if (v > kf) kf = v;
+        }
+      }
+      return kf;
     };
     if constexpr (DICT) {
       uint8_t* const mlen = mlen_of(); uint16_t* const mdist = mdist_of();
@@ -904,6 +957,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
       uint32_t pw2 = 0, pw3 = 0;   // bytes 8..15 of the position: a candidate that agrees on 8 bytes is compared on 8 more in the same trip
 #endif
       uint32_t pkey = 0;   // classes with the filter array: this position's own filter byte
+      [[maybe_unused]] uint32_t kf = 0;   // dictionary jobs: the one candidate whose common length the next anchors know (known_of), per lane
       // Can candidate with filter byte kb be skipped without a window read?  Filter array classes: kb = (byte 4 & 15) | 4 further
       // bits of the hash product << 4 — a candidate whose high nibble differs holds a DIFFERENT 4-gram in the same bucket
       // (a quarter of all candidates on text) and can never match; one whose low nibble differs has a different byte 4 and cannot
@@ -936,6 +990,9 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         kmax = i - lo;
         if (kmax > depth) kmax = depth;
         best = MINM - 1; bd = 0; probe = pw0; kk = 1;
+#ifndef HMSE_NO_PROBE16
+        if constexpr (DICT) kf = known_of(p, maxlen);   // (asked where a candidate has agreed on 16 bytes: the 8-byte experiment build has no such place)
+#endif
 #ifdef HMSE_DFL_STAMPS
         if (DICT && t == 0) stamp_acc[7]++;  // lane 0's walked positions
 #endif
@@ -959,6 +1016,9 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         }
         maxlen = (T - p) < MAXM ? (T - p) : MAXM;
         best = MINM - 1; bd = 0; probe = pw0; kk = 1;
+#ifndef HMSE_NO_PROBE16
+        if constexpr (DICT) kf = known_of(p, maxlen);   // (asked where a candidate has agreed on 16 bytes: the 8-byte experiment build has no such place)
+#endif
 #ifdef HMSE_DFL_STAMPS
         if (DICT && t == 0) stamp_acc[7]++;
 #endif
@@ -1089,6 +1149,8 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
               ld64a(W, q + 8, c2, c3);
               if ((x = c2 ^ pw2) != 0) ml = 8 + ((uint32_t)__builtin_ctz(x) >> 3);
               else if ((x = c3 ^ pw3) != 0) ml = 12 + ((uint32_t)__builtin_ctz(x) >> 3);
+              // (dictionary jobs) 16 bytes agree and this is the candidate the next anchors speak about: its length is known, no EXTEND
+              else if (DICT && kf >= (16u << 16) && (kf & 0xFFFFu) == q) ml = kf >> 16;
               else { ml = 16; if (maxlen > 16) { fin = false; st = EXTEND; } }
             } else ml = 8;
 #else

@@ -285,3 +285,90 @@ void study_walk_hist(const uint8_t* chunk, uint32_t len, uint32_t D, uint64_t* h
   }
   idx_free(&x);
 }
+
+/* ---- dictionary jobs: what the anchors of the NEXT blocks know about the long compares of unhinted positions -------------------
+ * Rule 2b's anchors as the oracle defines them, plus each anchor's BACKWARD extent along its diagonal as the match kernel records it
+ * (phase 4b: up to 128 bytes, 8 per lane, not in front of the chunk's first position nor of the window's first byte).  Every
+ * position WITHOUT a hint of 16 bytes or more is walked (rule 2); a candidate that agrees on 16 bytes enters the kernel's EXTEND
+ * block and costs one lane-trip per 32 bytes compared.  Those lane-trips are counted and attributed:
+ *   out[0] dictionary-job chunk positions   [1] positions walked (no hint)   [2] candidates that enter EXTEND   [3] EXTEND lane-trips
+ *   [4] candidates / [5] lane-trips on the diagonal of anchor a0+1, inside its backward stretch
+ *   [6] / [7] the same for anchor a0+2, where a0+1 does not cover the position with that candidate
+ *   [8] / [9] not covered by either: candidates on the diagonal of this block's or the previous block's anchor, BEHIND the end of
+ *             its run (the diagonal resumed after a substitution)
+ *   [10] probe trips of the walked positions (filter of the kernel, two entries per trip)   [11] walked positions with a fact
+ *   [12] candidates whose known length differs from the compared one (a check of the statement itself: must stay 0) */
+void study_dict_known(const uint8_t* chunk, uint32_t len, const uint8_t* dict, uint32_t dlen, uint32_t D, uint64_t* out) {
+  idx_t x; idx_build(&x, chunk, len, dict, dlen);
+  const uint8_t* W = x.W; uint32_t T = x.T, Dl = x.Dl;
+  uint32_t n_anch = (len + 63) / 64;
+  uint32_t* ad = (uint32_t*)calloc(n_anch + 3, 4); uint32_t* ar = (uint32_t*)calloc(n_anch + 3, 4); uint32_t* ab = (uint32_t*)calloc(n_anch + 3, 4);
+  for (uint32_t a = 0; a < n_anch; a++) {
+    uint32_t pa = Dl + 64 * a;
+    if (pa + 4 > T) continue;
+    uint32_t h = hash4(le32(W + pa)), lo = x.start[h], hi = x.start[h + 1], l = lo;
+    while (l < hi && x.S[l] < Dl) l++;
+    uint32_t first = l > lo + 64 ? l - 64 : lo, bml = 0, bq = 0;
+    for (uint32_t i = first; i < l; i++) {
+      uint32_t q = x.S[i], ml = 0;
+      if (pa - q > WMAX) continue;
+      while (ml < 32 && W[q + ml] == W[pa + ml]) ml++;
+      if (ml >= bml) { bml = ml; bq = q; }
+    }
+    if (bml < 32) continue;
+    uint32_t d = pa - bq, lim = T - pa < 512 ? T - pa : 512, run = 0;
+    while (run < lim && W[pa + run] == W[pa + run - d]) run++;
+    uint32_t blim = 128; if (blim > 64 * a) blim = 64 * a; if (blim > 8 * (bq / 8)) blim = 8 * (bq / 8);
+    uint32_t back = 0;
+    while (back < blim && W[pa - back - 1] == W[pa - back - 1 - d]) back++;
+    ad[a] = d; ar[a] = run; ab[a] = back;
+  }
+  out[0] += len;
+  for (uint32_t p = Dl; p + 4 <= T; p++) {
+    uint32_t maxlen = T - p < MAXM ? T - p : MAXM, a0 = (p - Dl) >> 6, hm = 0;
+    for (uint32_t b = 0; b < 2; b++) {
+      if (a0 < b) continue;
+      uint32_t d = ad[a0 - b], run = ar[a0 - b], pa = Dl + ((a0 - b) << 6), m = 0;
+      if (d == 0 || d > p || p - d >= Dl) continue;
+      if (run >= 512) m = maxlen; else if (pa + run > p) m = pa + run - p < maxlen ? pa + run - p : maxlen;
+      if (m > hm) hm = m;
+    }
+    if (hm >= 16) continue;
+    out[1]++;
+    uint64_t tr[8] = {0}; walk_trips(&x, p, D, 0, 2, tr); out[10] += tr[0];
+    /* the facts of the two next anchors */
+    uint32_t kq[2] = {0xFFFFFFFFu, 0xFFFFFFFFu}, kl[2] = {0, 0};
+    for (uint32_t f = 0; f < 2; f++) {
+      uint32_t a = a0 + 1 + f, pa = Dl + (a << 6);
+      if (a < n_anch && ad[a] && pa - p <= ab[a]) {
+        kq[f] = p - ad[a];
+        kl[f] = (ar[a] >= 512 || pa + ar[a] - p > maxlen) ? maxlen : pa + ar[a] - p;   /* the kernel's known length */
+      }
+    }
+    out[11] += kq[0] != 0xFFFFFFFFu || kq[1] != 0xFFFFFFFFu;
+    uint32_t h = hash4(le32(W + p)), r = x.rank[p], g = x.start[h], best = MINM - 1;
+    for (uint32_t k = 1; k <= D && r >= g + k; k++) {
+      uint32_t q = x.S[r - k];
+      if (p - q > WMAX) break;
+      uint32_t ml = 0;
+      while (ml < maxlen && W[q + ml] == W[p + ml]) ml++;
+      /* (the kernel only compares a candidate that passes its filter and agrees with the probe at best - 3: one that agrees on 16 bytes and
+         can still beat `best`; a candidate no longer than `best` leaves at the probe) */
+      for (uint32_t f = 0; f < 2; f++) if (q == kq[f] && kl[f] != ml) out[12]++;   /* the statement must be exact: stays 0 */
+      if (ml >= 16 && maxlen > 16 && ml > best) {
+        uint32_t n = 0, cur = 16;
+        do { n++; if (ml < cur + 32) break; cur += 32; } while (cur < maxlen);
+        out[2]++; out[3] += n;
+        if (q == kq[0]) { out[4]++; out[5] += n; }
+        else if (q == kq[1]) { out[6]++; out[7] += n; }
+        else for (uint32_t b = 0; b < 2; b++) {
+          if (a0 < b) continue;
+          uint32_t d = ad[a0 - b], run = ar[a0 - b], pa = Dl + ((a0 - b) << 6);
+          if (d && p - q == d && run < 512 && pa + run < p) { out[8]++; out[9] += n; break; }
+        }
+      }
+      if (ml > best) { best = ml; if (ml == maxlen) break; }
+    }
+  }
+  free(ad); free(ar); free(ab); idx_free(&x);
+}
