@@ -13,6 +13,7 @@
 // offset lives in device memory and a one-thread kernel advances it after each band.  The only host sync is the caller's
 // read of out_bytes.
 #include "common.h"
+#include "blockops.h"
 
 constexpr int BT_NT = 256;
 constexpr int BT_SCAN_NT = 1024;
@@ -21,8 +22,6 @@ constexpr uint64_t BT_HEAD = 32;          // "HMSEBAND" + u32 x4 + u64
 
 enum { BT_CURSOR = 0, BT_RUNS = 1, BT_HDRS = 2, BT_HIST = 3, BT_META = 4 };
 
-static uint64_t bt_blocks(uint64_t n) { return (n + BT_NT - 1) / BT_NT; }
-
 extern "C" uint64_t hmse_band_tables_bound(uint64_t n, uint32_t bands, uint32_t band_bits, uint32_t n_hashes) {
   (void)band_bits;
   // a band holds at most n headers (a piece holds at least one id)
@@ -30,10 +29,10 @@ extern "C" uint64_t hmse_band_tables_bound(uint64_t n, uint32_t bands, uint32_t 
 }
 
 extern "C" size_t hmse_band_tables_workspace_bytes(uint64_t n) {
-  const uint64_t nt = bt_blocks(n);
+  const uint64_t nt = hmse_blocks(n, BT_NT);
   const uint64_t scan_len = 256 * nt > n + 1 ? 256 * nt : n + 1;
   // bkt/id ping-pong (4 x n), run flags, piece flags, run starts (n + 1), histogram (256 per tile), block sums, meta
-  return 6 * hmse_align_up(4 * (n + 1), 256) + hmse_align_up(4 * 256 * nt, 256) + hmse_align_up(4 * (bt_blocks(scan_len) + 1), 256) +
+  return 6 * hmse_align_up(4 * (n + 1), 256) + hmse_align_up(4 * 256 * nt, 256) + hmse_align_up(4 * (hmse_blocks(scan_len, BT_NT) + 1), 256) +
          hmse_align_up(8 * BT_META, 256) + 256;
 }
 
@@ -103,49 +102,6 @@ __global__ __launch_bounds__(BT_NT) void bt_scatter_kernel(const uint32_t* __res
     const uint64_t dst = (uint64_t)hist[(uint64_t)d * n_tiles + blockIdx.x] + r;
     if (dst < n) { bkt_out[dst] = v; ids_out[dst] = ids[i]; }
   }
-}
-
-// exclusive scan of a u32 array in place: block sums, one workgroup over them, then per block (trip counts: kernel arguments)
-__global__ __launch_bounds__(BT_NT) void bt_reduce_kernel(const uint32_t* __restrict__ a, uint64_t len, uint32_t* __restrict__ bsum) {
-  __shared__ uint32_t red[BT_NT / 64 + 1];
-  const uint64_t i = (uint64_t)blockIdx.x * BT_NT + threadIdx.x;
-  uint32_t tot;
-  block_exclusive_scan<BT_NT>(i < len ? a[i] : 0u, red, &tot);
-  if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(BT_SCAN_NT) void bt_scan_kernel(uint32_t* __restrict__ bsum, uint64_t nb, uint64_t* __restrict__ total) {
-  __shared__ uint32_t red[BT_SCAN_NT / 64 + 1];
-  uint32_t carry = 0;
-  for (uint64_t b0 = 0; b0 < nb; b0 += BT_SCAN_NT) {
-    const uint64_t i = b0 + threadIdx.x;
-    const uint32_t v = i < nb ? bsum[i] : 0u;
-    uint32_t tot;
-    const uint32_t ex = block_exclusive_scan<BT_SCAN_NT>(v, red, &tot);
-    if (i < nb) bsum[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) *total = carry;
-}
-
-__global__ __launch_bounds__(BT_NT) void bt_apply_kernel(uint32_t* __restrict__ a, uint64_t len, const uint32_t* __restrict__ bsum) {
-  __shared__ uint32_t red[BT_NT / 64 + 1];
-  const uint64_t i = (uint64_t)blockIdx.x * BT_NT + threadIdx.x;
-  const uint32_t v = i < len ? a[i] : 0u;
-  uint32_t tot;
-  const uint32_t ex = bsum[blockIdx.x] + block_exclusive_scan<BT_NT>(v, red, &tot);
-  if (i < len) a[i] = ex;
-}
-
-static int bt_scan(uint32_t* a, uint64_t len, uint32_t* bsum, uint64_t* total, hipStream_t stream) {
-  const uint64_t nb = bt_blocks(len);
-  bt_reduce_kernel<<<dim3((uint32_t)nb), dim3(BT_NT), 0, stream>>>(a, len, bsum);
-  HMSE_LAUNCH_CHECK();
-  bt_scan_kernel<<<dim3(1), dim3(BT_SCAN_NT), 0, stream>>>(bsum, nb, total);
-  HMSE_LAUNCH_CHECK();
-  bt_apply_kernel<<<dim3((uint32_t)nb), dim3(BT_NT), 0, stream>>>(a, len, bsum);
-  HMSE_LAUNCH_CHECK();
-  return HMSE_OK;
 }
 
 __device__ __forceinline__ bool bt_is_start(const uint32_t* bkt, uint64_t i) { return i == 0 || bkt[i] != bkt[i - 1]; }
@@ -249,7 +205,7 @@ extern "C" int hmse_band_tables_write(const uint32_t* band_keys, uint64_t n, uin
   const uint32_t nh = n_hashes;            // 0: no signature section
   if (out_cap < BT_HEAD) return HMSE_ENOSPC;
   if (!ws || ws_bytes < hmse_band_tables_workspace_bytes(n)) return HMSE_ENOSPC;
-  const uint64_t nt = bt_blocks(n);
+  const uint64_t nt = hmse_blocks(n, BT_NT);
   WsCarver c(ws, ws_bytes);
   uint32_t* bkt_a = c.take<uint32_t>(n + 1);
   uint32_t* id_a = c.take<uint32_t>(n + 1);
@@ -259,7 +215,7 @@ extern "C" int hmse_band_tables_write(const uint32_t* band_keys, uint64_t n, uin
   uint32_t* run_start = c.take<uint32_t>(n + 1);
   uint32_t* hist = c.take<uint32_t>(256 * nt);
   const uint64_t scan_len = 256 * nt > n + 1 ? 256 * nt : n + 1;
-  uint32_t* bsum = c.take<uint32_t>(bt_blocks(scan_len) + 1);
+  uint32_t* bsum = c.take<uint32_t>(hmse_blocks(scan_len, BT_NT) + 1);
   uint64_t* meta = c.take<uint64_t>(BT_META);
   if (!c.ok()) return HMSE_ENOSPC;
   uint32_t* pf = hist;            // the piece flags reuse the histogram (256 per tile >= n)
@@ -277,7 +233,7 @@ extern "C" int hmse_band_tables_write(const uint32_t* band_keys, uint64_t n, uin
       for (int p = 0; p < passes; p++) {
         bt_hist_kernel<<<dim3((uint32_t)nt), dim3(BT_NT), 0, stream>>>(bi, n, 8u * p, nt, hist);
         HMSE_LAUNCH_CHECK();
-        int rc = bt_scan(hist, 256 * nt, bsum, meta + BT_HIST, stream);
+        int rc = device_exclusive_scan<uint32_t, BT_NT, BT_SCAN_NT>(hist, 256 * nt, bsum, meta + BT_HIST, stream);
         if (rc != HMSE_OK) return rc;
         bt_scatter_kernel<<<dim3((uint32_t)nt), dim3(BT_NT), 0, stream>>>(bi, ii, n, 8u * p, nt, hist, bo, io);
         HMSE_LAUNCH_CHECK();
@@ -286,13 +242,13 @@ extern "C" int hmse_band_tables_write(const uint32_t* band_keys, uint64_t n, uin
       }
       bt_start_kernel<<<dim3((uint32_t)nt), dim3(BT_NT), 0, stream>>>(bi, n, runf);
       HMSE_LAUNCH_CHECK();
-      int rc = bt_scan(runf, n, bsum, meta + BT_RUNS, stream);
+      int rc = device_exclusive_scan<uint32_t, BT_NT, BT_SCAN_NT>(runf, n, bsum, meta + BT_RUNS, stream);
       if (rc != HMSE_OK) return rc;
       bt_runs_kernel<<<dim3((uint32_t)nt), dim3(BT_NT), 0, stream>>>(bi, n, runf, meta, run_start);
       HMSE_LAUNCH_CHECK();
       bt_piece_kernel<<<dim3((uint32_t)nt), dim3(BT_NT), 0, stream>>>(bi, n, runf, run_start, pf);
       HMSE_LAUNCH_CHECK();
-      rc = bt_scan(pf, n, bsum, meta + BT_HDRS, stream);
+      rc = device_exclusive_scan<uint32_t, BT_NT, BT_SCAN_NT>(pf, n, bsum, meta + BT_HDRS, stream);
       if (rc != HMSE_OK) return rc;
       bt_emit_kernel<<<dim3((uint32_t)nt), dim3(BT_NT), 0, stream>>>(bi, ii, n, runf, run_start, pf, meta, out, out_cap, status);
       HMSE_LAUNCH_CHECK();
@@ -303,7 +259,7 @@ extern "C" int hmse_band_tables_write(const uint32_t* band_keys, uint64_t n, uin
   uint64_t tail = 0;
   if (nh) {
     const uint64_t nk = n * bands, ns = n * nh;
-    uint64_t blocks = bt_blocks(nk + ns);
+    uint64_t blocks = hmse_blocks(nk + ns, BT_NT);
     if (blocks > 8192) blocks = 8192;
     if (blocks == 0) blocks = 1;
     bt_sigs_kernel<<<dim3((uint32_t)blocks), dim3(BT_NT), 0, stream>>>(band_keys, nk, sig, ns, nh, meta, out, out_cap, status);
@@ -318,9 +274,9 @@ extern "C" int hmse_band_tables_write(const uint32_t* band_keys, uint64_t n, uin
 // ---- near-duplicate index (hmse_l4_index_build, include/hmse.h): per band the stored ids sorted stably by the whole 32-bit key —
 // the kernels above with mask 0xFFFFFFFF and four 8-bit passes.
 size_t hmse_l4_index_workspace_bytes_impl(uint64_t n) {
-  const uint64_t nt = bt_blocks(n);
+  const uint64_t nt = hmse_blocks(n, BT_NT);
   // key/id ping-pong partner (2 x n), histogram (256 per tile), block sums, meta
-  return 2 * hmse_align_up(4 * (n + 1), 256) + hmse_align_up(4 * 256 * nt, 256) + hmse_align_up(4 * (bt_blocks(256 * nt) + 1), 256) +
+  return 2 * hmse_align_up(4 * (n + 1), 256) + hmse_align_up(4 * 256 * nt, 256) + hmse_align_up(4 * (hmse_blocks(256 * nt, BT_NT) + 1), 256) +
          hmse_align_up(8 * BT_META, 256) + 256;
 }
 
@@ -328,12 +284,12 @@ size_t hmse_l4_index_workspace_bytes_impl(uint64_t n) {
 static int bt_sort_u32(const uint32_t* keys, uint64_t n, uint32_t stride, uint32_t col, uint32_t* out_keys, uint32_t* out_ids, void* ws,
                        size_t ws_bytes, hipStream_t stream) {
   if (n == 0) return HMSE_OK;
-  const uint64_t nt = bt_blocks(n);
+  const uint64_t nt = hmse_blocks(n, BT_NT);
   WsCarver c(ws, ws_bytes);
   uint32_t* bkt = c.take<uint32_t>(n + 1);
   uint32_t* ids = c.take<uint32_t>(n + 1);
   uint32_t* hist = c.take<uint32_t>(256 * nt);
-  uint32_t* bsum = c.take<uint32_t>(bt_blocks(256 * nt) + 1);
+  uint32_t* bsum = c.take<uint32_t>(hmse_blocks(256 * nt, BT_NT) + 1);
   uint64_t* meta = c.take<uint64_t>(BT_META);
   if (!c.ok()) return HMSE_ENOSPC;
   bt_load_kernel<<<dim3((uint32_t)nt), dim3(BT_NT), 0, stream>>>(keys, n, stride, col, 0xFFFFFFFFu, out_keys, out_ids);
@@ -342,7 +298,7 @@ static int bt_sort_u32(const uint32_t* keys, uint64_t n, uint32_t stride, uint32
   for (int p = 0; p < 4; p++) {
     bt_hist_kernel<<<dim3((uint32_t)nt), dim3(BT_NT), 0, stream>>>(bi, n, 8u * p, nt, hist);
     HMSE_LAUNCH_CHECK();
-    int rc = bt_scan(hist, 256 * nt, bsum, meta + BT_HIST, stream);
+    int rc = device_exclusive_scan<uint32_t, BT_NT, BT_SCAN_NT>(hist, 256 * nt, bsum, meta + BT_HIST, stream);
     if (rc != HMSE_OK) return rc;
     bt_scatter_kernel<<<dim3((uint32_t)nt), dim3(BT_NT), 0, stream>>>(bi, ii, n, 8u * p, nt, hist, bo, io);
     HMSE_LAUNCH_CHECK();

@@ -17,6 +17,8 @@
   } while (0)
 
 static inline size_t hmse_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// workgroups of nt threads for n elements, one each
+static inline uint64_t hmse_blocks(uint64_t n, uint64_t nt) { return (n + nt - 1) / nt; }
 
 // A workspace is 256-byte aligned (include/hmse.h): the carver below hands out 256-byte pieces and the kernels store 16 bytes at a time
 // into them.  First statement of every entry point that takes one: HMSE_EINVAL before anything is cleared or launched.
@@ -57,6 +59,13 @@ __device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t* p) {
   __builtin_memcpy(&v, p, 4);
   return v;
 }
+// A value that IS the same in every lane, told to the compiler (SGPRs): control flow that depends only on such values becomes
+// scalar branches — no EXEC masking, so a cross-lane read inside it (readfirstlane, bpermute from lane 0) always finds its source
+// lane active.  (Round 3: the DEFLATE dictionary jobs' work queue was wave-uniform in fact but divergent in the compiler's analysis — the
+// chunk length it compared against came from a vector load — and the structurised loop it produced never finished on the first
+// shard with more class-S dictionary jobs than resident workgroups; profiles/r3/r3_deflate_dict_queue_hang_isa.txt.)
+__device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t uni64(uint64_t v) { return ((uint64_t)uni32((uint32_t)(v >> 32)) << 32) | uni32((uint32_t)v); }
 __device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return __builtin_rotateleft32(x, r); }
 __device__ __forceinline__ uint32_t rotr32(uint32_t x, int r) { return __builtin_rotateright32(x, r); }
 
@@ -72,6 +81,12 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
   return v;
 }
 
+// the same for u64, where a DPP step would be two moves and a carry chain: the shuffle ladder (only the small scan kernels use it)
+__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v) {
+  for (int d = 1; d < 64; d <<= 1) { const uint64_t t = __shfl_up((unsigned long long)v, d, 64); if (lane_id() >= (uint32_t)d) v += t; }
+  return v;
+}
+
 // the maximum over the 64 lanes, in every lane (same DPP ladder; 0 is the identity)
 __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 #define HMSE_DPP_MAX(ctrl, rows) { const uint32_t o__ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rows, 0xF, false); v = v > o__ ? v : o__; }
@@ -81,17 +96,17 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 }
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(v), 63); }
 
-// workgroup exclusive scan of one u32 per thread (NT threads, NT <= 1024). `red` = LDS u32[NT/64 + 1].
-template <int NT>
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* red, uint32_t* total) {
+// workgroup exclusive scan of one T (u32 or u64) per thread (NT threads, NT <= 1024). `red` = LDS T[NT/64 + 1].
+template <int NT, typename T>
+__device__ __forceinline__ T block_exclusive_scan(T v, T* red, T* total) {
   const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
-  const uint32_t inc = wave_incl_scan(v);
+  const T inc = wave_incl_scan(v);
   if (lane == 63) red[wave] = inc;
   __syncthreads();
-  uint32_t wbase = 0, tot = 0;
+  T wbase = 0, tot = 0;
 #pragma unroll
   for (int w = 0; w < NT / 64; w++) {
-    uint32_t c = red[w];
+    T c = red[w];
     if ((uint32_t)w < wave) wbase += c;
     tot += c;
   }

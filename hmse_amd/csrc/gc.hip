@@ -14,15 +14,14 @@
 // hmse_record_gather: the dense DEFLATE streams of the surviving store from two sources (records reused from the old blob,
 // records re-encoded by hmse_l1_deflate), one wavefront per record, 16-byte stores at 16-byte aligned destinations.
 #include "common.h"
+#include "blockops.h"
 
 constexpr uint32_t GC_EMPTY = 0xFFFFFFFFu;
 constexpr int GC_NT = 256;
 constexpr int GC_SCAN_NT = 1024;
 
-static uint64_t gc_blocks(uint64_t n) { return (n + GC_NT - 1) / GC_NT; }
-
 size_t hmse_gc_plan_workspace_bytes_impl(uint64_t n_chunks) {
-  const uint64_t nb = gc_blocks(n_chunks) + 1;
+  const uint64_t nb = hmse_blocks(n_chunks, GC_NT) + 1;
   // cnt u32[n_slots] + first u32[n_slots] + slot_at u32[n] + alive u8[n] + two block-sum arrays (n_slots <= n_chunks)
   return hmse_align_up(4 * n_chunks, 256) * 3 + hmse_align_up(n_chunks, 256) + 2 * hmse_align_up(4 * nb, 256) + 256;
 }
@@ -47,21 +46,6 @@ __global__ __launch_bounds__(GC_NT) void gc_survive_kernel(const uint64_t* __res
   }
   const int c = __syncthreads_count(a);
   if (threadIdx.x == 0) bsum[blockIdx.x] = (uint32_t)c;
-}
-
-// exclusive scan of nb block counts in place, total to *total (one workgroup; the loop's trip count is a kernel argument)
-__global__ __launch_bounds__(GC_SCAN_NT) void gc_scan_kernel(uint32_t* __restrict__ bsum, uint64_t nb, uint64_t* __restrict__ total) {
-  __shared__ uint32_t red[GC_SCAN_NT / 64 + 1];
-  uint32_t carry = 0;
-  for (uint64_t b0 = 0; b0 < nb; b0 += GC_SCAN_NT) {
-    const uint64_t i = b0 + threadIdx.x;
-    const uint32_t v = i < nb ? bsum[i] : 0u;
-    uint32_t tot;
-    const uint32_t ex = block_exclusive_scan<GC_SCAN_NT>(v, red, &tot);
-    if (i < nb) bsum[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) *total = carry;
 }
 
 __global__ __launch_bounds__(GC_NT) void gc_rank_kernel(uint64_t n, const uint32_t* __restrict__ slot, const uint8_t* __restrict__ alive,
@@ -137,7 +121,7 @@ extern "C" int hmse_gc_plan(const uint64_t* cuts, uint64_t n_chunks, const uint3
   if (!cuts || !slot || !digests_old || !old_chunk || !first_occ || !refcount || !digests || !uniq_ids || !old_slot || !new_slot_of_old)
     return HMSE_EINVAL;
   if (!ws || ws_bytes < hmse_gc_plan_workspace_bytes_impl(n_chunks)) return HMSE_ENOSPC;
-  const uint64_t nb = gc_blocks(n_chunks), nbs = gc_blocks(n_slots);
+  const uint64_t nb = hmse_blocks(n_chunks, GC_NT), nbs = hmse_blocks(n_slots, GC_NT);
   WsCarver c(ws, ws_bytes);
   uint32_t* cnt = c.take<uint32_t>(n_chunks);
   uint32_t* first = c.take<uint32_t>(n_chunks);
@@ -152,7 +136,7 @@ extern "C" int hmse_gc_plan(const uint64_t* cuts, uint64_t n_chunks, const uint3
   if (n_slots) HMSE_FILL(new_slot_of_old, 0xFF, 8 * n_slots, stream);
   gc_survive_kernel<<<dim3((uint32_t)nb), dim3(GC_NT), 0, stream>>>(cuts, n_chunks, slot, n_slots, seg_off, n_seg, drop, alive, cnt, bsum_a, status);
   HMSE_LAUNCH_CHECK();
-  gc_scan_kernel<<<dim3(1), dim3(GC_SCAN_NT), 0, stream>>>(bsum_a, nb, counts);
+  block_sums_scan_kernel<GC_SCAN_NT><<<dim3(1), dim3(GC_SCAN_NT), 0, stream>>>(bsum_a, nb, counts, nullptr);
   HMSE_LAUNCH_CHECK();
   gc_rank_kernel<<<dim3((uint32_t)nb), dim3(GC_NT), 0, stream>>>(n_chunks, slot, alive, bsum_a, first, old_chunk);
   HMSE_LAUNCH_CHECK();
@@ -162,7 +146,7 @@ extern "C" int hmse_gc_plan(const uint64_t* cuts, uint64_t n_chunks, const uint3
   }
   gc_count_kernel<<<dim3((uint32_t)nb), dim3(GC_NT), 0, stream>>>(counts, slot_at, bsum_b);
   HMSE_LAUNCH_CHECK();
-  gc_scan_kernel<<<dim3(1), dim3(GC_SCAN_NT), 0, stream>>>(bsum_b, nb, counts + 1);
+  block_sums_scan_kernel<GC_SCAN_NT><<<dim3(1), dim3(GC_SCAN_NT), 0, stream>>>(bsum_b, nb, counts + 1, nullptr);
   HMSE_LAUNCH_CHECK();
   gc_emit_kernel<<<dim3((uint32_t)nb), dim3(GC_NT), 0, stream>>>(counts, slot, cnt, first, slot_at, bsum_b, old_chunk, digests_old, first_occ,
                                                                  refcount, digests, uniq_ids, old_slot, new_slot_of_old);
@@ -171,8 +155,7 @@ extern "C" int hmse_gc_plan(const uint64_t* cuts, uint64_t n_chunks, const uint3
 }
 
 // ---- record gather: one wavefront per record ------------------------------------------------------------------------------
-// head: the bytes up to the destination's next 16-byte boundary, one per lane; body: 16-byte stores at aligned destinations
-// (loads from wherever the source record starts: lba_unit may be 1); tail: the last < 16 bytes, one per lane.
+// wave_copy (blockops.h): 16-byte stores at aligned destinations, loads from wherever the source record starts (lba_unit may be 1).
 __global__ __launch_bounds__(GC_NT) void gc_gather_kernel(const uint8_t* __restrict__ src0, uint64_t src0_bytes, const uint8_t* __restrict__ src1,
                                                          uint64_t src1_bytes, const uint64_t* __restrict__ src_off, const uint8_t* __restrict__ src_sel,
                                                          const uint64_t* __restrict__ dst_off, uint64_t n, uint8_t* __restrict__ dst,
@@ -189,16 +172,7 @@ __global__ __launch_bounds__(GC_NT) void gc_gather_kernel(const uint8_t* __restr
     return;
   }
   const uint8_t* s = src + s0;
-  uint8_t* d = dst + d0;
-  uint64_t head = (16 - ((uintptr_t)d & 15)) & 15;
-  if (head > len) head = len;
-  if (lane < head) d[lane] = s[lane];
-  const uint64_t body = (len - head) & ~(uint64_t)15;
-  const uint8_t* sb = s + head;
-  uint4* db = (uint4*)(d + head);
-  for (uint64_t o = (uint64_t)lane * 16; o < body; o += 64 * 16) db[o >> 4] = load_u4_unaligned(sb + o);
-  const uint64_t t0 = head + body;
-  if (t0 + lane < len) d[t0 + lane] = s[t0 + lane];
+  wave_copy(dst + d0, s, len, lane);
 }
 
 extern "C" int hmse_record_gather(const uint8_t* src0, uint64_t src0_bytes, const uint8_t* src1, uint64_t src1_bytes, const uint64_t* src_off,

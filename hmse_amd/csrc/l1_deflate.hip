@@ -21,6 +21,7 @@
 // length; encode kernel: one 256-thread workgroup per job, six per CU.  Persistent workgroups pull jobs from
 // per-class lists.
 #include "common.h"
+#include "blockops.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <mutex>
@@ -32,7 +33,6 @@ constexpr int NBK = 1 << HB;
 constexpr uint32_t MINM = 4, MAXM = 258, WMAX = 32768;
 
 __device__ __forceinline__ uint32_t hash4(uint32_t x) { return (x * 0x9E3779B1u) >> (32 - HB); }
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 
 // Window bytes at an ARBITRARY byte offset, fetched with naturally aligned dword reads and shifted into place in registers
 // (v_alignbyte_b32).  Measured on gfx950 (tools/ubench/lds_unaligned.hip, profiles/r2/lds_unaligned_gfx950.txt): an LDS read
@@ -94,14 +94,6 @@ __device__ __forceinline__ uint32_t len_extra_bits(uint32_t code) {  // code 257
 }
 __device__ __forceinline__ uint32_t dist_extra_bits(uint32_t code) { return code < 4 ? 0 : (code >> 1) - 1; }
 __device__ __forceinline__ uint32_t fixed_len(uint32_t s) { return s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8; }
-
-// A value that IS the same in every lane, told to the compiler (SGPRs): control flow that depends only on such values becomes
-// scalar branches — no EXEC masking, so a cross-lane read inside it (readfirstlane, bpermute from lane 0) always finds its source
-// lane active.  (Round 3: the dictionary jobs' work queue was wave-uniform in fact but divergent in the compiler's analysis — the
-// chunk length it compared against came from a vector load — and the structurised loop it produced never finished on the first
-// shard with more class-S dictionary jobs than resident workgroups; profiles/r3/r3_deflate_dict_queue_hang_isa.txt.)
-__device__ __forceinline__ uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) { return ((uint64_t)uni32((uint32_t)(v >> 32)) << 32) | uni32((uint32_t)v); }
 
 // order LDS traffic between the lanes of one wavefront (no instruction is emitted for the barrier itself)
 __device__ __forceinline__ void wave_sync() {
@@ -1934,7 +1926,9 @@ __global__ __launch_bounds__(256) void gather_kernel(const uint64_t* __restrict_
   }
 }
 
-// ---- u64 exclusive scan (three small kernels) ---------------------------------------------------------------
+// ---- u64 exclusive scan: reduce and apply here, the block sums by blockops.h's block_sums_scan_kernel --------------------------------
+// (The reduce and apply kernels keep bodies of their own: as instances of blockops.h's u32 pair they measured 0.5 and 1.3 us slower per
+// call at 1 073 081 elements, outside the spread of three runs)
 constexpr int SC_NT = 1024;
 __global__ __launch_bounds__(SC_NT) void scan_reduce_kernel(const uint64_t* __restrict__ in, uint64_t n, uint64_t* __restrict__ bsum,
                                                             const uint64_t* __restrict__ n_dev) {
@@ -1947,37 +1941,13 @@ __global__ __launch_bounds__(SC_NT) void scan_reduce_kernel(const uint64_t* __re
   __syncthreads();
   if (threadIdx.x == 0) { unsigned long long tt = 0; for (int w = 0; w < SC_NT / 64; w++) tt += s[w]; bsum[blockIdx.x] = tt; }
 }
-__global__ __launch_bounds__(SC_NT) void scan_blocks_kernel(uint64_t* bsum, uint64_t nb, uint64_t* total_out, const uint64_t* __restrict__ n_dev) {
-  if (n_dev) nb = (*n_dev + SC_NT - 1) / SC_NT;
-  __shared__ unsigned long long s[SC_NT / 64 + 1];
-  __shared__ unsigned long long run;
-  if (threadIdx.x == 0) run = 0;
-  __syncthreads();
-  for (uint64_t b0 = 0; b0 < nb; b0 += SC_NT) {
-    const uint64_t i = b0 + threadIdx.x;
-    const unsigned long long v = i < nb ? bsum[i] : 0ull;
-    unsigned long long inc = v;
-    for (int d = 1; d < 64; d <<= 1) { unsigned long long tt = __shfl_up(inc, d, 64); if (lane_id() >= (uint32_t)d) inc += tt; }
-    if (lane_id() == 63) s[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    unsigned long long wb = 0, tot = 0;
-    for (int w = 0; w < SC_NT / 64; w++) { if ((uint32_t)w < (threadIdx.x >> 6)) wb += s[w]; tot += s[w]; }
-    const unsigned long long r = run;
-    if (i < nb) bsum[i] = r + wb + inc - v;
-    __syncthreads();
-    if (threadIdx.x == 0) run = r + tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && total_out) *total_out = run;
-}
 __global__ __launch_bounds__(SC_NT) void scan_apply_kernel(const uint64_t* __restrict__ in, uint64_t n, const uint64_t* __restrict__ bsum,
                                                             uint64_t* __restrict__ out, const uint64_t* __restrict__ n_dev) {
   if (n_dev) n = *n_dev;
   __shared__ unsigned long long s[SC_NT / 64];
   const uint64_t i = (uint64_t)blockIdx.x * SC_NT + threadIdx.x;
   const unsigned long long v = i < n ? in[i] : 0ull;
-  unsigned long long inc = v;
-  for (int d = 1; d < 64; d <<= 1) { unsigned long long tt = __shfl_up(inc, d, 64); if (lane_id() >= (uint32_t)d) inc += tt; }
+  const unsigned long long inc = wave_incl_scan((uint64_t)v);
   if (lane_id() == 63) s[threadIdx.x >> 6] = inc;
   __syncthreads();
   unsigned long long wb = 0;
@@ -1993,7 +1963,7 @@ static int exclusive_scan_u64(const uint64_t* in, uint64_t n, uint64_t* out, uin
                               const uint64_t* n_dev = nullptr) {
   const uint64_t nb = (n + SC_NT - 1) / SC_NT;
   scan_reduce_kernel<<<dim3((uint32_t)nb), dim3(SC_NT), 0, stream>>>(in, n, bsum, n_dev);
-  scan_blocks_kernel<<<dim3(1), dim3(SC_NT), 0, stream>>>(bsum, nb, total, n_dev);
+  block_sums_scan_kernel<SC_NT, 0, uint64_t, SC_NT><<<dim3(1), dim3(SC_NT), 0, stream>>>(bsum, nb, total, n_dev);
   scan_apply_kernel<<<dim3((uint32_t)nb), dim3(SC_NT), 0, stream>>>(in, n, bsum, out, n_dev);
   return hipGetLastError() == hipSuccess ? HMSE_OK : HMSE_EHIP;
 }

@@ -17,6 +17,7 @@
 // The bit reader keeps a 64-bit window refilled from global memory; the output is re-read (match sources)
 // with agent-scope (L1-bypassing) loads after the wave's own stores have drained.
 #include "common.h"
+#include "blockops.h"
 #include <atomic>
 
 namespace ifl {
@@ -52,8 +53,6 @@ struct Args {
 // value to the same address (the hardware merges them).
 // Everything that steers control flow is wave-uniform and is kept in SGPRs: values that arrive through a vector
 // load (same address in every lane) are made scalar with readfirstlane, so the decoder's loops are scalar branches.
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uni64(uint64_t v) { return ((uint64_t)uni((uint32_t)(v >> 32)) << 32) | uni((uint32_t)v); }
 __device__ __forceinline__ uint64_t uload64(const uint64_t* p) { return uni64(*p); }
 
 // bit reader over streams[p, end): 64-bit window, LSB first (RFC 1951 §3.1.1); all state scalar
@@ -70,7 +69,7 @@ struct Bits {
     }
     while (n <= 56) {  // last bytes of the stream; zeros behind it (the final length check catches their use)
       uint32_t b = 0;
-      if (p < end) b = uni(s[p]);
+      if (p < end) b = uni32(s[p]);
       p++;
       acc |= (uint64_t)b << n; n += 8;
     }
@@ -148,7 +147,7 @@ __device__ __forceinline__ uint32_t decode_sym(Bits& br, const LaneCode& lc, con
   const uint32_t len = (uint32_t)__builtin_ctzll(m);
   const uint32_t idx = (uint32_t)__builtin_amdgcn_readlane((int)(lc.offs + rel), (int)len);
   br.drop(len);
-  return uni(sym[idx]);
+  return uni32(sym[idx]);
 }
 
 __global__ __launch_bounds__(NT, 8) void l1_inflate_kernel(Args a) {
@@ -158,7 +157,7 @@ __global__ __launch_bounds__(NT, 8) void l1_inflate_kernel(Args a) {
   for (;;) {
     // one pull per wavefront: every lane takes part (lane 0 adds 1, the others 0; the compiler folds this into a
     // single atomic) so that no lane-dependent branch precedes the readfirstlane
-    const uint32_t k = uni(atomicAdd(a.counter, lane == 0 ? 1u : 0u));
+    const uint32_t k = uni32(atomicAdd(a.counter, lane == 0 ? 1u : 0u));
     IFL_TRACE(0, 1); IFL_TRACE(1, k);
     if (k >= a.n_sel) break;
     const uint64_t o0 = uload64(a.raw_off + k), o1 = uload64(a.raw_off + k + 1);
@@ -169,13 +168,13 @@ __global__ __launch_bounds__(NT, 8) void l1_inflate_kernel(Args a) {
     // out in index order and base < k, so that wavefront is running or done; the wait is bounded all the same
     // (a wavefront must always reach its exit) and running out of polls is reported as status bit 1.
     const uint8_t* dict = nullptr; uint32_t Dl = 0;
-    if (!bad && uni(a.kind[k]) == HMSE_KIND_DELTA) {
+    if (!bad && uni32(a.kind[k]) == HMSE_KIND_DELTA) {
       const int64_t b = a.base ? (int64_t)uload64((const uint64_t*)a.base + k) : -1;
       if (b < 0 || (uint64_t)b >= k) bad = true;
       else {
         IFL_TRACE(0, 2);
         uint32_t polls = 0, st;
-        while ((st = uni(__hip_atomic_load(&a.done[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) == 0u && ++polls < (1u << 21))
+        while ((st = uni32(__hip_atomic_load(&a.done[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) == 0u && ++polls < (1u << 21))
           __builtin_amdgcn_s_sleep(16);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         if (st == 0u) { bad = true; atomicOr(a.status, 2u); }
@@ -188,7 +187,7 @@ __global__ __launch_bounds__(NT, 8) void l1_inflate_kernel(Args a) {
       }
     }
     const uint64_t s0 = uload64(a.stream_off + k);
-    const uint64_t s1 = a.stream_len ? s0 + uni(a.stream_len[k]) : uload64(a.stream_off + k + 1);
+    const uint64_t s1 = a.stream_len ? s0 + uni32(a.stream_len[k]) : uload64(a.stream_off + k + 1);
     if (s1 < s0 || s1 > a.streams_bytes) bad = true;
     Bits br; br.s = a.streams; br.p = s0; br.end = bad ? s0 : s1; br.acc = 0; br.n = 0;
     uint32_t pos = 0;      // bytes decoded, including literals still pending in `pend`
@@ -263,7 +262,7 @@ __global__ __launch_bounds__(NT, 8) void l1_inflate_kernel(Args a) {
         }
         if (bad) break;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-        if (uni(T.lens[256]) == 0) { bad = true; break; }  // no end-of-block code
+        if (uni32(T.lens[256]) == 0) { bad = true; break; }  // no end-of-block code
         if (!build_table(T.lens, nlit, T.lsym, false, LL)) { bad = true; break; }
         if (!build_table(T.lens + nlit, ndist, T.dsym, false, LD)) { bad = true; break; }
       }
@@ -974,13 +973,8 @@ __global__ __launch_bounds__(256) void assemble_kernel(const uint64_t* __restric
     if (threadIdx.x == 0) atomicOr(status, 1u);
     return;
   }
-  const uint64_t len = d1 - d0;
   const uint8_t* src = raw + raw_off[s];
-  uint8_t* dst = data_out + d0;
-  for (uint64_t b = (uint64_t)threadIdx.x * 16; b < len; b += 256 * 16) {
-    if (b + 16 <= len) { const uint4 v = load_u4_unaligned(src + b); __builtin_memcpy(dst + b, &v, 16); }
-    else for (uint64_t j = b; j < len; j++) dst[j] = src[j];
-  }
+  block_copy<256, uint64_t>(data_out + d0, src, d1 - d0);
 }
 
 }  // namespace ifl

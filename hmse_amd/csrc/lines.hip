@@ -11,12 +11,12 @@
 //       the chunk and to `reach`; one ballot gives the trip's delimiter mask, the count still needed lives in an SGPR, and the trip that
 //       holds the wanted delimiter picks it by rank (the popcount of the mask above the lane going backward, below it going forward)
 //       with one more ballot.  Every loop — trips inside a chunk, chunks with the empty ones skipped — has a scalar counter and exit.
-//   (2) lines_gather_kernel — one wavefront per range [start, end): per chunk piece one byte per lane up to the destination's next
-//       16-byte boundary, 16 bytes per lane between (aligned stores, loads from wherever the piece starts in raw), one byte per lane
-//       for the rest.  lines_ranges_kernel proves every range and the prefix sum first: a refused call writes nothing.
+//   (2) lines_gather_kernel — one wavefront per range [start, end): per chunk piece one wave_copy (blockops.h: aligned 16-byte stores,
+//       loads from wherever the piece starts in raw).  lines_ranges_kernel proves every range and the prefix sum first: a refused call writes nothing.
 // No kernel holds an atomic or a cross-lane operation inside a loop that lanes leave at different times (tools/isa_audit.py).
 #include "common.h"
 #include "chunkmap.h"
+#include "blockops.h"
 
 constexpr int LINES_NT = 256;                // four wavefronts = four hits (or ranges) per workgroup
 constexpr uint32_t LINES_TRIP = 64;          // bytes one trip looks at: one per lane
@@ -142,18 +142,7 @@ __global__ __launch_bounds__(LINES_NT) void lines_gather_kernel(const uint8_t* _
     const uint64_t c0 = cuts[c], c1 = cuts[c + 1];
     if (p == c1) { c++; continue; }                    // p < e <= N: a chunk follows
     const uint64_t q = c1 < e ? c1 : e, len = q - p;   // the piece [p, q) of chunk c
-    const uint8_t* sp = raw + raw_off[slot[c]] + (p - c0);
-    uint8_t* dp = dst + (p - s);
-    uint64_t head = (16 - ((uintptr_t)dp & 15)) & 15;
-    if (head > len) head = len;
-    if (lane < head) dp[lane] = sp[lane];
-    const uint64_t body = (len - head) & ~(uint64_t)15;
-    for (uint64_t b0 = 0; b0 < body; b0 += 64 * 16) {
-      const uint64_t b = b0 + (uint64_t)lane * 16;
-      if (b < body) *(uint4*)(dp + head + b) = load_u4_unaligned(sp + head + b);
-    }
-    const uint64_t t0 = head + body;
-    if (t0 + lane < len) dp[t0 + lane] = sp[t0 + lane];
+    wave_copy(dst + (p - s), raw + raw_off[slot[c]] + (p - c0), len, lane);
     p = q;
   }
 }

@@ -14,6 +14,7 @@
 // Two kernels: one workgroup per stored chunk copies its stream into the blob behind the DeltaChunk header and writes its
 // ChunkIndex entry; one thread per chunk writes the map entry and, for a duplicate, the pointer record.
 #include "common.h"
+#include "blockops.h"
 
 namespace mfp {
 
@@ -62,11 +63,7 @@ __global__ __launch_bounds__(256) void records_kernel(Args a) {
     }
     dst += 8;
   }
-  const uint8_t* src = a.streams + s0;
-  for (uint32_t i = t * 16; i < slen; i += 256 * 16) {
-    if (i + 16 <= slen) { const uint4 v = load_u4_unaligned(src + i); __builtin_memcpy(dst + i, &v, 16); }
-    else for (uint32_t b = i; b < slen; b++) dst[b] = src[b];
-  }
+  block_copy<256, uint32_t>(dst, a.streams + s0, slen);
   for (uint64_t p = o0 + rlen + t; p < o1; p += 256) a.blob[p] = 0;   // padding up to the next record
   // ChunkIndex entry
   uint8_t* e = a.index + 40 * k;

@@ -16,16 +16,15 @@
 // No value read from the blob indexes memory: base_lba is only ever compared with the index's LBAs.  Every loop bound is
 // wave-uniform and scalar (a kernel argument, or the wave maximum taken before the loop), as in l4_query.hip.
 #include "common.h"
+#include "blockops.h"
 
 constexpr int SC_NT = 256;
 constexpr int SC_SCAN_NT = 1024;
 constexpr uint32_t SC_NONE = 0xFFFFFFFFu;
 
-static uint64_t sc_blocks(uint64_t n) { return (n + SC_NT - 1) / SC_NT; }
-
 size_t hmse_scrub_attribute_workspace_bytes_impl(uint64_t n_records, uint64_t n_chunks) {
   // anc / far ping-pong (u32 x 4 per record), the live flag, block counts of the boundary scan
-  return 4 * hmse_align_up(4 * (n_records + 1), 256) + 256 + hmse_align_up(4 * (sc_blocks(n_chunks + 1) + 1), 256);
+  return 4 * hmse_align_up(4 * (n_records + 1), 256) + 256 + hmse_align_up(4 * (hmse_blocks(n_chunks + 1, SC_NT) + 1), 256);
 }
 
 // ---- records ---------------------------------------------------------------------------------------------------------------
@@ -124,7 +123,7 @@ extern "C" int hmse_scrub_records(const uint8_t* blob, uint64_t blob_bytes, uint
     return HMSE_EINVAL;
   const uint64_t threads = n > n_shards ? n : n_shards;                    // (a shard without records is covered by thread `shard`)
   PROF_BEGIN(HMSE_STAGE_SCRUB_RECORDS, stream);
-  sc_records_kernel<<<dim3((uint32_t)sc_blocks(threads)), dim3(SC_NT), 0, stream>>>(blob, n, rec_shard, shard_blob, shard_slot, lba_unit, lba,
+  sc_records_kernel<<<dim3((uint32_t)hmse_blocks(threads, SC_NT)), dim3(SC_NT), 0, stream>>>(blob, n, rec_shard, shard_blob, shard_slot, lba_unit, lba,
                                                                                     rec_len, kind, remote, sorted_lba, sorted_slot, steps, meta,
                                                                                     status, dict, blob_bytes, n_shards,
                                                                                     (unsigned long long*)padding);
@@ -225,21 +224,6 @@ __global__ __launch_bounds__(SC_NT) void sc_chunks_kernel(uint64_t n_chunks, con
   if (threadIdx.x == 0) bsum[blockIdx.x] = (uint32_t)c;
 }
 
-// exclusive scan of nb block counts in place, total to *total (one workgroup; the loop's trip count is a kernel argument)
-__global__ __launch_bounds__(SC_SCAN_NT) void sc_scan_kernel(uint32_t* __restrict__ bsum, uint64_t nb, unsigned long long* __restrict__ total) {
-  __shared__ uint32_t red[SC_SCAN_NT / 64 + 1];
-  uint32_t carry = 0;
-  for (uint64_t b0 = 0; b0 < nb; b0 += SC_SCAN_NT) {
-    const uint64_t i = b0 + threadIdx.x;
-    const uint32_t v = i < nb ? bsum[i] : 0u;
-    uint32_t tot;
-    const uint32_t ex = block_exclusive_scan<SC_SCAN_NT>(v, red, &tot);
-    if (i < nb) bsum[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) *total = carry / 2;          // boundaries come in pairs: (start, end) of every damaged run
-}
-
 // boundary j at chunk i -> ranges[j] = cuts[i] (an even j starts a run, an odd one ends it)
 __global__ __launch_bounds__(SC_NT) void sc_emit_kernel(uint64_t n_chunks, const int64_t* __restrict__ chunk_root, const uint64_t* __restrict__ cuts,
                                                        const uint32_t* __restrict__ bsum, uint64_t* __restrict__ ranges) {
@@ -282,7 +266,7 @@ extern "C" int hmse_scrub_attribute(uint64_t n, const uint8_t* status, const int
   uint32_t* anc[2] = {c.take<uint32_t>(n + 1), c.take<uint32_t>(n + 1)};
   uint32_t* far[2] = {c.take<uint32_t>(n + 1), c.take<uint32_t>(n + 1)};
   uint32_t* live = c.take<uint32_t>(64);
-  const uint64_t nbc = sc_blocks(n_chunks + 1);
+  const uint64_t nbc = hmse_blocks(n_chunks + 1, SC_NT);
   uint32_t* bsum = c.take<uint32_t>(nbc + 1);
   if (!c.ok()) return HMSE_ENOSPC;
   unsigned long long* cnt = (unsigned long long*)counts;
@@ -294,7 +278,7 @@ extern "C" int hmse_scrub_attribute(uint64_t n, const uint8_t* status, const int
     HMSE_FILL(root_bytes, 0, 8 * n, stream);
     HMSE_FILL(live, 0, 4 * 64, stream);
     HMSE_FILL(live, 0x01, 4, stream);                    // round 0 runs
-    const uint32_t nb = (uint32_t)sc_blocks(n);
+    const uint32_t nb = (uint32_t)hmse_blocks(n, SC_NT);
     sc_init_kernel<<<dim3(nb), dim3(SC_NT), 0, stream>>>(n, status, dict, ok, got_sha, want_sha, check_digest, status_out, anc[0], far[0]);
     HMSE_LAUNCH_CHECK();
     int cur = 0;
@@ -311,12 +295,13 @@ extern "C" int hmse_scrub_attribute(uint64_t n, const uint8_t* status, const int
     sc_chunks_kernel<<<dim3(nb), dim3(SC_NT), 0, stream>>>(n_chunks, chunk_slot, n, cuts, root, chunk_root, (unsigned long long*)root_chunks,
                                                            (unsigned long long*)root_bytes, cnt, bsum);
     HMSE_LAUNCH_CHECK();
-    sc_scan_kernel<<<dim3(1), dim3(SC_SCAN_NT), 0, stream>>>(bsum, nbc, cnt);
+    // boundaries come in pairs, (start, end) of every damaged run: counts[0] = half their number
+    block_sums_scan_kernel<SC_SCAN_NT, 1><<<dim3(1), dim3(SC_SCAN_NT), 0, stream>>>(bsum, nbc, counts, nullptr);
     HMSE_LAUNCH_CHECK();
     sc_emit_kernel<<<dim3(nb), dim3(SC_NT), 0, stream>>>(n_chunks, chunk_root, cuts, bsum, ranges);
     HMSE_LAUNCH_CHECK();
     const uint64_t cap = n_chunks / 2 + 1;
-    sc_lengths_kernel<<<dim3((uint32_t)sc_blocks(cap)), dim3(SC_NT), 0, stream>>>(cap, cnt, ranges);
+    sc_lengths_kernel<<<dim3((uint32_t)hmse_blocks(cap, SC_NT)), dim3(SC_NT), 0, stream>>>(cap, cnt, ranges);
     HMSE_LAUNCH_CHECK();
   }
   PROF_END(HMSE_STAGE_SCRUB_ATTRIBUTE, stream);

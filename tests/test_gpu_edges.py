@@ -295,6 +295,21 @@ def test_l1_encode_lists_split_at_12288_and_end_at_32768(delta, name, cfg, orc, 
         assert enc[mine] > 0 and all(v == 0 for s, v in enc.items() if s != mine), enc
 
 
+@pytest.mark.parametrize("n", [1023, 1024, 1025, 2049])
+def test_l1_deflate_record_offsets_across_the_blocks_of_the_device_scan(n, orc, dev):
+    """n chunks of two bytes: the two exclusive scans inside hmse_l1_deflate (record offsets in the workspace, stream offsets in out_off)
+    run 1024 elements per workgroup, so n = 1023 / 1024 / 1025 / 2049 is one block short of full, full, two and three blocks.  Offsets,
+    kinds and every stream byte equal the oracle's."""
+    from hmse_amd import IngestConfig, ops
+    cfg = IngestConfig()
+    data = words_text(2 * n, seed=n)
+    cuts = np.arange(0, 2 * n + 1, 2, dtype=np.uint64)
+    w_out, w_off, w_kind = orc.deflate_chunks(data, cuts, ocfg(orc, cfg))
+    out, off, kind = ops.l1_deflate(to_dev(data, dev), to_dev(cuts.astype(np.int64), dev), cfg)
+    assert off.numel() == n + 1 and np.array_equal(off.cpu().numpy().astype(np.uint64), w_off)
+    assert np.array_equal(kind.cpu().numpy(), w_kind) and np.array_equal(out.cpu().numpy(), w_out)
+
+
 def test_l1_deflate_signals_a_chunk_above_32768_bytes(orc, dev):
     """A chunk of 32769 bytes next to normal ones: no crash; status bit 2 (include/hmse.h); the oversized chunk gets an EMPTY record
     (out_off[k + 1] == out_off[k]); every other record is exactly the oracle's.  ops.l1_deflate raises on that status."""

@@ -212,7 +212,7 @@ def test_gc_refuses_a_store_written_under_other_lsh_parameters(dev):
         gc.drop_segments(m, [0], cfg, dev, band_tables=side)
 
 
-@pytest.mark.parametrize("n,u", [(5000, 1200), (300000, 40000)])
+@pytest.mark.parametrize("n,u", [(255, 60), (256, 60), (257, 60), (5000, 1200), (300000, 40000)])   # one block of 256 chunks and one either side; 300000: the block sums need a second trip of the 1024-wide scan
 def test_plan_kernel_equals_l3_dedup_over_the_surviving_digests(dev, n, u):
     import torch
     from hmse_amd import ops

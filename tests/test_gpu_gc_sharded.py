@@ -277,7 +277,7 @@ def _keys(rng, n, bands):
 @pytest.mark.parametrize("with_sig", [False, True])
 @pytest.mark.parametrize("band_bits", [12, 16])
 @pytest.mark.parametrize("bands", [4, 8, 16])
-@pytest.mark.parametrize("n", [0, 1, 5000, 300000])
+@pytest.mark.parametrize("n", [0, 1, 255, 256, 257, 5000, 262145, 300000])   # a tile of 256 ids and one either side; 262145 = 256 x 1024 + 1: the scan of the run flags takes the second trip over its block sums
 def test_band_tables_kernel_equals_numpy_writer(dev, n, bands, band_bits, with_sig):
     import torch
     from hmse_amd import bandtable

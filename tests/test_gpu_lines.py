@@ -253,6 +253,24 @@ def test_gather_over_tiny_chunks_empty_ranges_and_every_misalignment(dev):
     assert out.data_ptr() % 16 == 0 and {(p % 16, q % 16) for p, q in zip(s, off)} == {(i, j) for i in range(16) for j in range(16)}
 
 
+def test_gather_pieces_of_0_1_15_16_17_bytes_at_odd_destinations(dev):
+    """The head, body and tail of the per-piece copy: pieces of 0, 1, 15, 16 and 17 bytes that each start at an odd byte of `out` (one-byte
+    fillers in front where needed) — once as ranges of their own inside one chunk, once as the chunks that one range crosses."""
+    corpus = _text(400, seed=8)
+    lens, odd = [3], []                                      # 3 bytes first: what follows starts at an odd offset
+    for L in (0, 1, 15, 16, 17):
+        if sum(lens) % 2 == 0:
+            lens.append(1)
+        odd.append(len(lens))
+        lens.append(L)
+    bounds = np.concatenate([[0], np.cumsum(lens)]).tolist()
+    assert all(bounds[k] % 2 == 1 for k in odd) and [lens[k] for k in odd] == [0, 1, 15, 16, 17]
+    s = [100 + 7 * k for k in range(len(lens))]
+    out = check_gather(dev, corpus, [0, len(corpus)], s, [p + L for p, L in zip(s, lens)])
+    assert out.data_ptr() % 16 == 0 and ref.text(corpus, s, [p + L for p, L in zip(s, lens)])[1][:len(lens) + 1] == bounds
+    check_gather(dev, corpus, bounds + [len(corpus)], [0, 0], [bounds[-1], len(corpus)])
+
+
 def test_gather_one_range_is_the_whole_corpus(dev):
     corpus = _text(100_003, seed=4, every=40)
     cuts = _chunkings(corpus)["ragged"]

@@ -404,3 +404,31 @@ def test_records_pass_counts_the_blob_of_a_shard_without_records(dev):
     e32, e64, e8 = i32([]), i64([]), torch.zeros(0, dtype=torch.uint8, device=dev)
     _, _, pad = ops.scrub_records(blob, e32, i64([0, 3, 99]), i64([0, 0, 0]), i32([1, 1]), e32, e32, e8, e64, e32, e32, 0, e8)
     assert int(pad.item()) == 3                                        # [0, 3) holds 1 non-zero byte, [3, 8) (clamped from 99) 2
+
+
+
+@pytest.mark.parametrize("n_chunks", [255, 256, 257, 262145])
+def test_attribute_ranges_of_damaged_chunk_runs_equal_a_run_length_count(dev, n_chunks):
+    """ops.scrub_attribute on synthetic tables: every record good, no dictionary, chunk_slot -1 (a damaged chunk, root -2) in seeded random
+    runs, the last chunk damaged (its run ends at the boundary thread n_chunks).  n_chunks = 255 / 256 / 257: that thread is the last of
+    the first block, the first of a second, and inside it; 262145 = 256 x 1024 + 1 blocks of boundaries: the scan over the block counts
+    takes its second trip.  ranges and counts[0, 4, 5] equal numpy's run lengths."""
+    import torch
+    from hmse_amd import ops
+    rng = np.random.default_rng(n_chunks)
+    n = 7
+    runs = rng.integers(1, 9, n_chunks)                                       # lengths of alternating good / damaged runs
+    bad = (np.repeat(np.arange(n_chunks) % 2, runs)[:n_chunks] == (n_chunks % 2)).copy()
+    bad[-1] = True
+    slot = np.where(bad, -1, rng.integers(0, n, n_chunks)).astype(np.int64)
+    cuts = np.concatenate([[0], np.cumsum(rng.integers(1, 100, n_chunks))]).astype(np.int64)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    sha = t(np.zeros((n, 32), np.uint8))
+    r = ops.scrub_attribute(t(np.zeros(n, np.uint8)), t(np.full(n, -1, np.int64)), t(np.ones(n, np.uint8)), sha, sha, False, t(slot), t(cuts), 0)
+    edge = np.diff(np.concatenate([[0], bad.astype(np.int8), [0]]))
+    start, end = np.flatnonzero(edge == 1), np.flatnonzero(edge == -1)
+    want = np.stack([cuts[start], cuts[end] - cuts[start]], axis=1).reshape(-1)
+    counts = r["counts"].cpu().numpy()
+    assert counts[0] == start.size and counts[4] == bad.sum() and counts[5] == (cuts[1:] - cuts[:-1])[bad].sum()
+    assert np.array_equal(r["ranges"].cpu().numpy()[: want.size], want)
+    assert np.array_equal(r["chunk_root"].cpu().numpy()[:n_chunks], np.where(bad, -2, -1))

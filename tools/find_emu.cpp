@@ -18,29 +18,8 @@
 #include <vector>
 #include "hmse.h"
 #include "hip_on_cpu.h"
-template <int NT> static inline uint32_t block_exclusive_scan(uint32_t v, uint32_t*, uint32_t* total) {
-  static uint32_t arr[NT];
-  arr[threadIdx.x] = v;
-  __syncthreads();
-  uint32_t pre = 0, tot = 0;
-  for (int i = 0; i < NT; i++) { if ((uint32_t)i < threadIdx.x) pre += arr[i]; tot += arr[i]; }
-  __syncthreads();
-  *total = tot;
-  return pre;
-}
 #include "chunkmap.h"
 #include "find_kernels.inc"
-
-static void launch(uint32_t grid, const std::function<void()>& f) {
-  gridDim.x = grid;
-  for (uint32_t b = 0; b < grid; b++) {
-    std::barrier<> bar(FIND_NT);
-    g_bar = &bar;
-    std::vector<std::thread> th;
-    for (int t = 0; t < FIND_NT; t++) th.emplace_back([&, t, b] { threadIdx.x = t; blockIdx.x = b; f(); bar.arrive_and_drop(); });
-    for (auto& x : th) x.join();
-  }
-}
 typedef unsigned long long ull;
 static uint32_t foldb(uint32_t b) { return (b >= 'A' && b <= 'Z') ? b + 32 : b; }
 static bool eq(const uint8_t* a, const uint8_t* b, uint32_t m, bool ic) { for (uint32_t i = 0; i < m; i++) if ((ic ? foldb(a[i]) : a[i]) != (ic ? foldb(b[i]) : b[i])) return false; return true; }
@@ -123,13 +102,13 @@ int main(int argc, char** argv) {
     const uint64_t cap = R(3) == 0 ? 0 : (R(2) ? want.size() : R(want.size() + 1));
     std::vector<ull> hits(cap + 8, ~0ull), counts(np, 0);
     ull nh = 0; uint32_t status = 0;
-    launch(1, [&] { tables_validate_kernel<FIND_NT>(raw_off.data(), n_rec, raw_bytes, nullptr, nullptr, 0, nullptr, &status); });
+    launch_block<FIND_NT>(1, [&] { tables_validate_kernel<FIND_NT>(raw_off.data(), n_rec, raw_bytes, nullptr, nullptr, 0, nullptr, &status); });
     if (status) { printf("it %d: validate status %u\n", it, status); fails++; break; }
     if (n_rec && raw_bytes) {
       const uint64_t n_tiles = (raw_bytes + FIND_TILE - 1) / FIND_TILE;
       const uint32_t grid = (uint32_t)std::min<uint64_t>(n_tiles, 1 + R(3));
       const bool few = np <= FIND_FEW;
-      auto call = [&](auto F, auto I) { launch(grid, [&] { find_scan_kernel<decltype(F)::value, decltype(I)::value>(raw.data(), raw_bytes, raw_off.data(), n_rec, mult.data(), flat.data(), P, cap ? hits.data() : nullptr, cap, &nh, counts.data(), &status, n_tiles); }); };
+      auto call = [&](auto F, auto I) { launch_block<FIND_NT>(grid, [&] { find_scan_kernel<decltype(F)::value, decltype(I)::value>(raw.data(), raw_bytes, raw_off.data(), n_rec, mult.data(), flat.data(), P, cap ? hits.data() : nullptr, cap, &nh, counts.data(), &status, n_tiles); }); };
       if (few) { if (ic) call(std::true_type{}, std::true_type{}); else call(std::true_type{}, std::false_type{}); }
       else { if (ic) call(std::false_type{}, std::true_type{}); else call(std::false_type{}, std::false_type{}); }
     }
@@ -155,13 +134,13 @@ int main(int argc, char** argv) {
     if (n_chunks) {
       std::vector<ull> sh(wseam.size() + 8, ~0ull), sc(np, 0);
       ull snh = 0; status = 0;
-      launch(2, [&] { tables_validate_kernel<FIND_NT>(raw_off.data(), n_rec, raw_bytes, cuts.data(), slot.data(), n_chunks, nullptr, &status); });
+      launch_block<FIND_NT>(2, [&] { tables_validate_kernel<FIND_NT>(raw_off.data(), n_rec, raw_bytes, cuts.data(), slot.data(), n_chunks, nullptr, &status); });
       if (status) { printf("it %d: validate(seams) status %u\n", it, status); fails++; break; }
       if (P.max_len >= 2) {
         const uint64_t nt = n_chunks * (P.max_len - 1);
         const uint32_t grid = (uint32_t)std::min<uint64_t>((nt + FIND_NT - 1) / FIND_NT, 1 + R(3));
-        if (ic) launch(grid, [&] { find_seams_kernel<true>(raw.data(), raw_off.data(), cuts.data(), slot.data(), n_chunks, flat.data(), P, sh.data(), wseam.size(), &snh, sc.data(), &status, nt); });
-        else launch(grid, [&] { find_seams_kernel<false>(raw.data(), raw_off.data(), cuts.data(), slot.data(), n_chunks, flat.data(), P, sh.data(), wseam.size(), &snh, sc.data(), &status, nt); });
+        if (ic) launch_block<FIND_NT>(grid, [&] { find_seams_kernel<true>(raw.data(), raw_off.data(), cuts.data(), slot.data(), n_chunks, flat.data(), P, sh.data(), wseam.size(), &snh, sc.data(), &status, nt); });
+        else launch_block<FIND_NT>(grid, [&] { find_seams_kernel<false>(raw.data(), raw_off.data(), cuts.data(), slot.data(), n_chunks, flat.data(), P, sh.data(), wseam.size(), &snh, sc.data(), &status, nt); });
       }
       std::vector<std::pair<uint64_t, uint32_t>> gs;
       for (uint64_t i = 0; i < std::min<uint64_t>(snh, wseam.size()); i++) gs.push_back({sh[i] >> 8, (uint32_t)(sh[i] & 255)});
@@ -179,8 +158,8 @@ int main(int argc, char** argv) {
       const uint64_t total = chunk_out.back();
       std::vector<ull> out(total + 8, ~0ull);
       status = 0;
-      launch(1, [&] { tables_validate_kernel<FIND_NT>(raw_off.data(), n_rec, ~0ull, cuts.data(), slot.data(), n_chunks, chunk_out.data(), &status); });
-      launch((uint32_t)std::max<uint64_t>(1, (total + FIND_NT - 1) / FIND_NT), [&] { place_kernel<8, FIND_NT>(hs.data(), hs.size(), raw_off.data(), cuts.data(), slot.data(), n_chunks, chunk_out.data(), out.data(), total, &status); });
+      launch_block<FIND_NT>(1, [&] { tables_validate_kernel<FIND_NT>(raw_off.data(), n_rec, ~0ull, cuts.data(), slot.data(), n_chunks, chunk_out.data(), &status); });
+      launch_block<FIND_NT>((uint32_t)std::max<uint64_t>(1, (total + FIND_NT - 1) / FIND_NT), [&] { place_kernel<8, FIND_NT>(hs.data(), hs.size(), raw_off.data(), cuts.data(), slot.data(), n_chunks, chunk_out.data(), out.data(), total, &status); });
       bool pok = status == 0 && total == win.size();
       for (uint64_t i = 0; pok && i < total; i++) pok = (out[i] >> 8) == win[i].first && (out[i] & 255) == win[i].second;
       for (uint64_t i = total; i < total + 8; i++) pok = pok && out[i] == ~0ull;

@@ -21,29 +21,8 @@
 #include <vector>
 #include "hmse.h"
 #include "hip_on_cpu.h"
-template <int NT> static inline uint32_t block_exclusive_scan(uint32_t v, uint32_t*, uint32_t* total) {
-  static uint32_t arr[NT];
-  arr[threadIdx.x] = v;
-  __syncthreads();
-  uint32_t pre = 0, tot = 0;
-  for (int i = 0; i < NT; i++) { if ((uint32_t)i < threadIdx.x) pre += arr[i]; tot += arr[i]; }
-  __syncthreads();
-  *total = tot;
-  return pre;
-}
 #include "chunkmap.h"
 #include "findset_kernels.inc"
-
-static void launch(uint32_t grid, const std::function<void()>& f) {
-  gridDim.x = grid;
-  for (uint32_t b = 0; b < grid; b++) {
-    std::barrier<> bar(FSET_NT);
-    g_bar = &bar;
-    std::vector<std::thread> th;
-    for (int t = 0; t < FSET_NT; t++) th.emplace_back([&, t, b] { threadIdx.x = t; blockIdx.x = b; f(); bar.arrive_and_drop(); });
-    for (auto& x : th) x.join();
-  }
-}
 typedef unsigned long long ull;
 static uint32_t foldb(uint32_t b) { return (b >= 'A' && b <= 'Z') ? b + 32 : b; }
 static bool eq(const uint8_t* a, const uint8_t* b, uint32_t m, bool ic) { for (uint32_t i = 0; i < m; i++) if ((ic ? foldb(a[i]) : a[i]) != (ic ? foldb(b[i]) : b[i])) return false; return true; }
@@ -153,13 +132,13 @@ int main(int argc, char** argv) {
     std::vector<ull> hits(cap + 8, ~0ull), counts(np, 0);
     ull nh = 0; uint32_t status = 0;
     const uint64_t nv = std::max<uint64_t>({n_rec, (uint64_t)F.n, 1ull << F.bits});
-    launch(2, [&] { findset_validate_kernel(raw_off.data(), n_rec, raw_bytes, nullptr, nullptr, 0, nullptr, F, nv, &status); });
+    launch_block<FSET_NT>(2, [&] { findset_validate_kernel(raw_off.data(), n_rec, raw_bytes, nullptr, nullptr, 0, nullptr, F, nv, &status); });
     if (status) { printf("it %d: validate status %u\n", it, status); fails++; break; }
     const uint64_t n_tiles = (raw_bytes + FSET_TILE - 1) / FSET_TILE;
     auto scan = [&](const FsetDev& G, ull* h, uint64_t c, ull* pn, ull* cn, uint32_t* st) {
       const uint32_t grid = (uint32_t)std::min<uint64_t>(n_tiles, 1 + R(2));
-      if (ic) launch(grid, [&] { findset_scan_kernel<true>(raw.data(), raw_bytes, raw_off.data(), n_rec, mult.data(), G, c ? h : nullptr, c, pn, cn, st, n_tiles); });
-      else launch(grid, [&] { findset_scan_kernel<false>(raw.data(), raw_bytes, raw_off.data(), n_rec, mult.data(), G, c ? h : nullptr, c, pn, cn, st, n_tiles); });
+      if (ic) launch_block<FSET_NT>(grid, [&] { findset_scan_kernel<true>(raw.data(), raw_bytes, raw_off.data(), n_rec, mult.data(), G, c ? h : nullptr, c, pn, cn, st, n_tiles); });
+      else launch_block<FSET_NT>(grid, [&] { findset_scan_kernel<false>(raw.data(), raw_bytes, raw_off.data(), n_rec, mult.data(), G, c ? h : nullptr, c, pn, cn, st, n_tiles); });
     };
     if (n_rec && raw_bytes) scan(F, hits.data(), cap, &nh, counts.data(), &status);
     bool ok = nh == want.size() && counts == wc && ((status & 1) != 0) == (cap && want.size() > cap);
@@ -183,7 +162,7 @@ int main(int argc, char** argv) {
       else D.uoff[F.n] = D.upat.size() + 1 + R(1000);
       uint32_t st = 0; ull dn = 0;
       std::vector<ull> dh(want.size() + 8, ~0ull), dc(np, 0);
-      launch(1, [&] { findset_validate_kernel(raw_off.data(), n_rec, raw_bytes, nullptr, nullptr, 0, nullptr, D.F, nv, &st); });
+      launch_block<FSET_NT>(1, [&] { findset_validate_kernel(raw_off.data(), n_rec, raw_bytes, nullptr, nullptr, 0, nullptr, D.F, nv, &st); });
       scan(D.F, dh.data(), want.size(), &dn, dc.data(), &st);
       bool dok = (st & 2) && dn == 0;
       for (auto v : dh) dok = dok && v == ~0ull;
@@ -206,12 +185,12 @@ int main(int argc, char** argv) {
       std::vector<ull> sh(scap + 8, ~0ull), sc(np, 0);
       ull snh = 0; status = 0;
       const uint64_t nv2 = std::max<uint64_t>(nv, n_chunks);
-      launch(2, [&] { findset_validate_kernel(raw_off.data(), n_rec, raw_bytes, cuts.data(), slot.data(), n_chunks, nullptr, F, nv2, &status); });
+      launch_block<FSET_NT>(2, [&] { findset_validate_kernel(raw_off.data(), n_rec, raw_bytes, cuts.data(), slot.data(), n_chunks, nullptr, F, nv2, &status); });
       if (status) { printf("it %d: validate(seams) status %u\n", it, status); fails++; break; }
       const uint64_t nt = n_chunks * (F.max_len - 1);
       const uint32_t grid = (uint32_t)std::min<uint64_t>((nt + FSET_NT - 1) / FSET_NT, 1 + R(3));
-      if (ic) launch(grid, [&] { findset_seams_kernel<true>(raw.data(), raw_off.data(), cuts.data(), slot.data(), n_chunks, F, scap ? sh.data() : nullptr, scap, &snh, sc.data(), &status, nt); });
-      else launch(grid, [&] { findset_seams_kernel<false>(raw.data(), raw_off.data(), cuts.data(), slot.data(), n_chunks, F, scap ? sh.data() : nullptr, scap, &snh, sc.data(), &status, nt); });
+      if (ic) launch_block<FSET_NT>(grid, [&] { findset_seams_kernel<true>(raw.data(), raw_off.data(), cuts.data(), slot.data(), n_chunks, F, scap ? sh.data() : nullptr, scap, &snh, sc.data(), &status, nt); });
+      else launch_block<FSET_NT>(grid, [&] { findset_seams_kernel<false>(raw.data(), raw_off.data(), cuts.data(), slot.data(), n_chunks, F, scap ? sh.data() : nullptr, scap, &snh, sc.data(), &status, nt); });
       std::vector<std::pair<uint64_t, uint32_t>> gs;
       for (uint64_t i = 0; i < std::min<uint64_t>(snh, scap); i++) gs.push_back({sh[i] >> HMSE_FINDSET_ID_BITS, (uint32_t)(sh[i] & IDM)});
       std::sort(gs.begin(), gs.end());
@@ -233,8 +212,8 @@ int main(int argc, char** argv) {
       std::vector<ull> out(total + 8, ~0ull);
       status = 0;
       FsetDev none; memset(&none, 0, sizeof none);
-      launch(1, [&] { findset_validate_kernel(raw_off.data(), n_rec, ~0ull, cuts.data(), slot.data(), n_chunks, chunk_out.data(), none, std::max(n_rec, n_chunks), &status); });
-      launch((uint32_t)std::max<uint64_t>(1, (total + FSET_NT - 1) / FSET_NT), [&] { place_kernel<HMSE_FINDSET_ID_BITS, FSET_NT>(hs.data(), hs.size(), raw_off.data(), cuts.data(), slot.data(), n_chunks, chunk_out.data(), out.data(), total, &status); });
+      launch_block<FSET_NT>(1, [&] { findset_validate_kernel(raw_off.data(), n_rec, ~0ull, cuts.data(), slot.data(), n_chunks, chunk_out.data(), none, std::max(n_rec, n_chunks), &status); });
+      launch_block<FSET_NT>((uint32_t)std::max<uint64_t>(1, (total + FSET_NT - 1) / FSET_NT), [&] { place_kernel<HMSE_FINDSET_ID_BITS, FSET_NT>(hs.data(), hs.size(), raw_off.data(), cuts.data(), slot.data(), n_chunks, chunk_out.data(), out.data(), total, &status); });
       bool pok = status == 0 && total == win.size();
       for (uint64_t i = 0; pok && i < total; i++) pok = (out[i] >> HMSE_FINDSET_ID_BITS) == win[i].first && (out[i] & IDM) == win[i].second;
       for (uint64_t i = total; i < total + 8; i++) pok = pok && out[i] == ~0ull;

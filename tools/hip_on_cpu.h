@@ -1,11 +1,15 @@
-// hip_on_cpu.h — what the search emulators (find_emu, findset_emu, lines_emu, regex_emu) put under a HIP kernel to run it on the CPU: one
-// std::thread per lane.  Include it after "hmse.h" and in front of hmse_amd/csrc/chunkmap.h and the kernels cut out of a .hip file.
-// What differs stays with each emulator: its launcher (which sets g_bar where the kernels use __syncthreads), its stand-in for
-// block_exclusive_scan, and the per-wavefront __ballot of lines_emu.
+// hip_on_cpu.h — what the emulators (find_emu, findset_emu, lines_emu, regex_emu, sync_emu) put under a HIP kernel to run it on the CPU:
+// one std::thread per lane, a std::barrier under __syncthreads and one per wavefront under __ballot (a loop that is not wave-uniform hangs
+// it), a plain prefix sum for block_exclusive_scan, and the launcher.  Include it after "hmse.h" and in front of hmse_amd/csrc/chunkmap.h,
+// blockops.h and the kernels cut out of a .hip file.
 #pragma once
 #include <barrier>
 #include <cstdint>
 #include <cstring>
+#include <functional>
+#include <memory>
+#include <thread>
+#include <vector>
 #define __global__
 #define __device__
 #define __host__
@@ -27,3 +31,51 @@ struct uint4 { uint32_t x, y, z, w; };
 static inline uint4 make_uint4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return uint4{a, b, c, d}; }
 static inline uint4 load_u4_unaligned(const uint8_t* p) { uint4 v; memcpy(&v, p, 16); return v; }
 static inline uint32_t load_u32_unaligned(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
+static inline uint32_t lane_id() { return threadIdx.x & 63u; }
+static inline uint32_t mbcnt64(uint64_t m) { return (uint32_t)__builtin_popcountll(m & ((1ull << lane_id()) - 1ull)); }
+template <int NT, typename T> static inline T block_exclusive_scan(T v, T*, T* total) {
+  static T arr[NT];
+  arr[threadIdx.x] = v;
+  __syncthreads();
+  T pre = 0, tot = 0;
+  for (int i = 0; i < NT; i++) { if ((uint32_t)i < threadIdx.x) pre += arr[i]; tot += arr[i]; }
+  __syncthreads();
+  *total = tot;
+  return pre;
+}
+// a ballot of the 64 lanes of one wavefront: every lane of the wavefront must arrive (the kernels' loops are wave-uniform, or this hangs)
+static unsigned long long g_bits[16];
+static std::barrier<>* g_wave[16];
+static inline unsigned long long __ballot(int p) {
+  const uint32_t w = threadIdx.x >> 6;
+  if (p) __atomic_fetch_or(&g_bits[w], 1ull << lane_id(), __ATOMIC_SEQ_CST);
+  g_wave[w]->arrive_and_wait();
+  const unsigned long long v = __atomic_load_n(&g_bits[w], __ATOMIC_SEQ_CST);
+  g_wave[w]->arrive_and_wait();
+  if (lane_id() == 0) __atomic_store_n(&g_bits[w], 0ull, __ATOMIC_SEQ_CST);
+  g_wave[w]->arrive_and_wait();
+  return v;
+}
+// grid workgroups of NT threads, one after the other.  launch_block: for kernels that meet at __syncthreads (a thread that returns leaves
+// the barrier: arrive_and_drop).  launch_waves: for kernels whose wavefronts meet only at __ballot and return as a whole.
+template <int NT> static void launch_block(uint32_t grid, const std::function<void()>& f) {
+  gridDim.x = grid;
+  for (uint32_t b = 0; b < grid; b++) {
+    std::barrier<> bar(NT);
+    g_bar = &bar;
+    std::vector<std::thread> th;
+    for (int t = 0; t < NT; t++) th.emplace_back([&, t, b] { threadIdx.x = t; blockIdx.x = b; f(); bar.arrive_and_drop(); });
+    for (auto& x : th) x.join();
+  }
+}
+template <int NT> static void launch_waves(uint32_t grid, const std::function<void()>& f) {
+  gridDim.x = grid;
+  for (uint32_t b = 0; b < grid; b++) {
+    std::unique_ptr<std::barrier<>> wave[NT / 64];
+    for (int w = 0; w < NT / 64; w++) { wave[w].reset(new std::barrier<>(64)); g_wave[w] = wave[w].get(); }
+    memset(g_bits, 0, sizeof g_bits);
+    std::vector<std::thread> th;
+    for (int t = 0; t < NT; t++) th.emplace_back([&, t, b] { threadIdx.x = t; blockIdx.x = b; f(); });
+    for (auto& x : th) x.join();
+  }
+}

@@ -5,7 +5,8 @@
 // with a guard behind them, bad positions, inconsistent tables, refused gathers.  No GPU: this checks the kernels' LOGIC and bounds
 // (build it with a sanitizer), not their code object.  Driven by tools/lines_emu.py, which cuts the kernels out of lines.hip
 // (everything between the geometry constants and the entry points) into lines_kernels.inc; the validate kernel comes from
-// hmse_amd/csrc/chunkmap.h and gets cuts as its chunk_out as well, as lines.hip's launcher hands it over.
+// hmse_amd/csrc/chunkmap.h and gets cuts as its chunk_out as well, as lines.hip's launcher hands it over; the gather kernel's per-piece
+// copy is wave_copy of hmse_amd/csrc/blockops.h, included as it is (the same function gc.hip's record gather runs).
 #include <barrier>
 #include <cstdint>
 #include <cstdio>
@@ -20,35 +21,9 @@
 #include <vector>
 #include "hmse.h"
 #include "hip_on_cpu.h"
-static inline uint32_t lane_id() { return threadIdx.x & 63u; }
-static inline uint32_t mbcnt64(uint64_t m) { return (uint32_t)__builtin_popcountll(m & ((1ull << lane_id()) - 1ull)); }
-// a ballot of the 64 lanes of one wavefront: every lane of the wavefront must arrive (the kernels' loops are wave-uniform, or this hangs)
-static unsigned long long g_bits[4];
-static std::barrier<>* g_wave[4];
-static inline unsigned long long __ballot(int p) {
-  const uint32_t w = threadIdx.x >> 6;
-  if (p) __atomic_fetch_or(&g_bits[w], 1ull << lane_id(), __ATOMIC_SEQ_CST);
-  g_wave[w]->arrive_and_wait();
-  const unsigned long long v = __atomic_load_n(&g_bits[w], __ATOMIC_SEQ_CST);
-  g_wave[w]->arrive_and_wait();
-  if (lane_id() == 0) __atomic_store_n(&g_bits[w], 0ull, __ATOMIC_SEQ_CST);
-  g_wave[w]->arrive_and_wait();
-  return v;
-}
 #include "chunkmap.h"
+#include "blockops.h"
 #include "lines_kernels.inc"
-
-static void launch(uint32_t grid, const std::function<void()>& f) {
-  gridDim.x = grid;
-  for (uint32_t b = 0; b < grid; b++) {
-    std::barrier<> w0(64), w1(64), w2(64), w3(64);
-    g_wave[0] = &w0; g_wave[1] = &w1; g_wave[2] = &w2; g_wave[3] = &w3;
-    memset(g_bits, 0, sizeof g_bits);
-    std::vector<std::thread> th;
-    for (int t = 0; t < LINES_NT; t++) th.emplace_back([&, t, b] { threadIdx.x = t; blockIdx.x = b; f(); });
-    for (auto& x : th) x.join();
-  }
-}
 
 static std::mt19937_64 rng(12345);
 static uint64_t R(uint64_t n) { return n ? rng() % n : 0; }
@@ -139,8 +114,8 @@ int main(int argc, char** argv) {
       std::vector<uint8_t> fl(n + 2, 0xA5);
       auto ST = exact(st); auto EN = exact(en); auto FL = exact(fl);
       uint32_t status = 0, want_status = broken ? 2u : 0u;
-      launch(1, [&] { tables_validate_kernel<LINES_NT>(RO.get(), n_rec, raw_bytes, CU.get(), SL.get(), n_chunks, CU.get(), &status); });
-      launch((uint32_t)((n + LINES_NT / 64 - 1) / (LINES_NT / 64)), [&] {
+      launch_waves<LINES_NT>(1, [&] { tables_validate_kernel<LINES_NT>(RO.get(), n_rec, raw_bytes, CU.get(), SL.get(), n_chunks, CU.get(), &status); });
+      launch_waves<LINES_NT>((uint32_t)((n + LINES_NT / 64 - 1) / (LINES_NT / 64)), [&] {
         lines_extent_kernel(RAW.get(), RO.get(), CU.get(), SL.get(), n_chunks, POS.get(), n, d, b, a, reach, ST.get(), EN.get(), FL.get(), &status);
       });
       for (uint64_t i = 0; i < n && !fails; i++) {
@@ -185,9 +160,9 @@ int main(int argc, char** argv) {
       std::unique_ptr<uint8_t[]> OUT(new uint8_t[mis + out_cap + 1]);      // (+ 1: a block of its own also when nothing is to be written)
       memset(OUT.get(), 0xA5, mis + out_cap + 1);
       uint32_t status = 0;
-      launch(1, [&] { tables_validate_kernel<LINES_NT>(RO.get(), n_rec, raw_bytes, CU.get(), SL.get(), n_chunks, CU.get(), &status); });
-      launch(1, [&] { lines_ranges_kernel(CU.get(), n_chunks, S.get(), E.get(), OFF.get(), n, out_cap, &status); });
-      launch((uint32_t)((n + LINES_NT / 64 - 1) / (LINES_NT / 64)), [&] {
+      launch_waves<LINES_NT>(1, [&] { tables_validate_kernel<LINES_NT>(RO.get(), n_rec, raw_bytes, CU.get(), SL.get(), n_chunks, CU.get(), &status); });
+      launch_waves<LINES_NT>(1, [&] { lines_ranges_kernel(CU.get(), n_chunks, S.get(), E.get(), OFF.get(), n, out_cap, &status); });
+      launch_waves<LINES_NT>((uint32_t)((n + LINES_NT / 64 - 1) / (LINES_NT / 64)), [&] {
         lines_gather_kernel(RAW.get(), RO.get(), CU.get(), SL.get(), n_chunks, S.get(), E.get(), OFF.get(), n, OUT.get() + mis, &status);
       });
       if (status != want_status) { printf("it %d: gather status %u, want %u (refuse %d, broken %d)\n", it, status, want_status, refuse, broken); fails++; }

@@ -18,29 +18,8 @@
 #include <vector>
 #include "hmse.h"
 #include "hip_on_cpu.h"
-template <int NT> static inline uint32_t block_exclusive_scan(uint32_t v, uint32_t*, uint32_t* total) {
-  static uint32_t arr[NT];
-  arr[threadIdx.x] = v;
-  __syncthreads();
-  uint32_t pre = 0, tot = 0;
-  for (int i = 0; i < NT; i++) { if ((uint32_t)i < threadIdx.x) pre += arr[i]; tot += arr[i]; }
-  __syncthreads();
-  *total = tot;
-  return pre;
-}
 #include "chunkmap.h"
 #include "regex_kernels.inc"
-
-static void launch(uint32_t grid, const std::function<void()>& f) {
-  gridDim.x = grid;
-  for (uint32_t b = 0; b < grid; b++) {
-    std::barrier<> bar(RX_NT);
-    g_bar = &bar;
-    std::vector<std::thread> th;
-    for (int t = 0; t < RX_NT; t++) th.emplace_back([&, t, b] { threadIdx.x = t; blockIdx.x = b; f(); bar.arrive_and_drop(); });
-    for (auto& x : th) x.join();
-  }
-}
 typedef unsigned long long ull;
 static std::mt19937_64 rng(12345);
 static uint64_t R(uint64_t n) { return n ? rng() % n : 0; }
@@ -122,11 +101,11 @@ int main(int argc, char** argv) {
     const uint64_t cap = R(3) == 0 ? 0 : (R(2) ? want.size() : R(want.size() + 1));
     std::vector<ull> hits(cap + 8, ~0ull);
     ull nh = 0, cnt = 0; uint32_t status = 0;
-    launch(2, [&] { regex_validate_kernel(raw_off.data(), n_rec, raw_bytes, nullptr, nullptr, 0, X, nv, &status); });
+    launch_block<RX_NT>(2, [&] { regex_validate_kernel(raw_off.data(), n_rec, raw_bytes, nullptr, nullptr, 0, X, nv, &status); });
     if (status) { printf("it %d: validate status %u\n", it, status); fails++; break; }
     const uint64_t n_tiles = (raw_bytes + RX_TILE - 1) / RX_TILE;
     auto scan = [&](const RxDev& G, ull* h, uint64_t c, ull* pn, ull* cn, uint32_t* st) {
-      launch((uint32_t)std::min<uint64_t>(n_tiles, 1 + R(2)), [&] { regex_scan_kernel(raw.data(), raw_bytes, raw_off.data(), n_rec, R(4) ? mult.data() : mult.data(), G, c ? h : nullptr, c, pn, cn, st, n_tiles); });
+      launch_block<RX_NT>((uint32_t)std::min<uint64_t>(n_tiles, 1 + R(2)), [&] { regex_scan_kernel(raw.data(), raw_bytes, raw_off.data(), n_rec, R(4) ? mult.data() : mult.data(), G, c ? h : nullptr, c, pn, cn, st, n_tiles); });
     };
     if (n_rec && raw_bytes) scan(X, hits.data(), cap, &nh, &cnt, &status);
     bool ok = nh == want.size() && cnt == wc && ((status & 1) != 0) == (cap && want.size() > cap) && !(status & 6);
@@ -147,7 +126,7 @@ int main(int argc, char** argv) {
       const RxDev Y{D.tab.data(), D.cm.data(), D.ns, D.nc, D.reach};
       uint32_t st = 0; ull dn = 0, dc = 0;
       std::vector<ull> dh(want.size() + 8, ~0ull);
-      launch(1, [&] { regex_validate_kernel(raw_off.data(), n_rec, raw_bytes, nullptr, nullptr, 0, Y, nv, &st); });
+      launch_block<RX_NT>(1, [&] { regex_validate_kernel(raw_off.data(), n_rec, raw_bytes, nullptr, nullptr, 0, Y, nv, &st); });
       scan(Y, dh.data(), want.size(), &dn, &dc, &st);
       bool dok = st == 4 && dn == 0 && dc == 0;
       for (auto v : dh) dok = dok && v == ~0ull;
@@ -164,12 +143,12 @@ int main(int argc, char** argv) {
       const uint64_t scap = R(4) == 0 ? R(wseam.size() + 1) : wseam.size();
       std::vector<ull> sh(scap + 8, ~0ull);
       ull snh = 0, sc = 0; status = 0;
-      launch(2, [&] { regex_validate_kernel(raw_off.data(), n_rec, raw_bytes, cuts.data(), slot.data(), n_chunks, X, nv, &status); });
+      launch_block<RX_NT>(2, [&] { regex_validate_kernel(raw_off.data(), n_rec, raw_bytes, cuts.data(), slot.data(), n_chunks, X, nv, &status); });
       if (status) { printf("it %d: validate(seams) status %u\n", it, status); fails++; break; }
       if (A.reach > 1) {
         const uint64_t nt = n_chunks * (A.reach - 1);
         const uint32_t grid = (uint32_t)std::min<uint64_t>((nt + RX_NT - 1) / RX_NT, 1 + R(3));
-        launch(grid, [&] { regex_seams_kernel(raw.data(), raw_off.data(), cuts.data(), slot.data(), n_chunks, X, scap ? sh.data() : nullptr, scap, &snh, &sc, &status, nt); });
+        launch_block<RX_NT>(grid, [&] { regex_seams_kernel(raw.data(), raw_off.data(), cuts.data(), slot.data(), n_chunks, X, scap ? sh.data() : nullptr, scap, &snh, &sc, &status, nt); });
       }
       std::vector<ull> gs(sh.begin(), sh.begin() + std::min<uint64_t>(snh, scap));
       std::sort(gs.begin(), gs.end());
@@ -185,7 +164,7 @@ int main(int argc, char** argv) {
       const uint64_t total = chunk_out.back();
       std::vector<ull> out(total + 8, ~0ull);
       status = 0;
-      launch((uint32_t)std::max<uint64_t>(1, (total + RX_NT - 1) / RX_NT), [&] { place_kernel<8, RX_NT>(want.data(), want.size(), raw_off.data(), cuts.data(), slot.data(), n_chunks, chunk_out.data(), out.data(), total, &status); });
+      launch_block<RX_NT>((uint32_t)std::max<uint64_t>(1, (total + RX_NT - 1) / RX_NT), [&] { place_kernel<8, RX_NT>(want.data(), want.size(), raw_off.data(), cuts.data(), slot.data(), n_chunks, chunk_out.data(), out.data(), total, &status); });
       bool pok = status == 0 && total == win.size() && total == wc;
       for (uint64_t i = 0; pok && i < total; i++) pok = out[i] == win[i];
       for (uint64_t i = total; i < total + 8; i++) pok = pok && out[i] == ~0ull;

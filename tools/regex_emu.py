@@ -5,44 +5,27 @@ compiles them with tools/regex_emu.cpp (g++ -std=c++20: one std::thread per lane
 for block_exclusive_scan) and runs random cases through validate, scan, place and seams (and a damaged automaton the validate kernel
 must refuse).  The automata come from hmse_amd/regex.py (numpy only) and are handed to the program in a file.  --sanitize builds that
 program with -fsanitize=address,undefined (host code only).  Prints how many cases ran; exit status 0 = all equal."""
-import argparse
 import os
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from emu_common import ROOT, run
+
 sys.path.insert(0, ROOT)
 PATTERNS = [(rb"q", 0), (rb"ab", 0), (rb"ab", 1), (rb"a+", 0), (rb"[ab]+c", 0), (rb"(a|aa)*b", 0), (rb"a{2,4}[^a]", 0), (rb"[^\n]*c", 0),
             (rb"a.{0,7}b", 2), (rb"(ab|b)c?", 1), (rb"b{255}a", 0), (rb"[ab]{16}", 0), (rb"\w+\s", 0)]
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--seed", type=int, default=12345)
-    ap.add_argument("--sanitize", action="store_true")
-    a = ap.parse_args()
+def automata(td):
+    """per automaton: n_states n_classes reach, 256 classes, the table"""
     from hmse_amd.regex import Regex
-    csrc = os.path.join(ROOT, "hmse_amd", "csrc")
-    src = open(os.path.join(csrc, "regex.hip")).read()
-    kernels = src[src.index("constexpr int RX_NT"): src.index("// ---- entry points")]
-    with tempfile.TemporaryDirectory() as td:
-        open(os.path.join(td, "regex_kernels.inc"), "w").write(kernels)
-        with open(os.path.join(td, "automata.txt"), "w") as f:      # per automaton: n_states n_classes reach, 256 classes, the table
-            f.write(f"{len(PATTERNS)}\n")
-            for pat, fl in PATTERNS:
-                r = Regex(pat, bool(fl & 1), bool(fl & 2))
-                f.write(f"{r.n_states} {r.n_classes} {r.reach}\n" + " ".join(map(str, r.classmap.tolist())) + "\n" + " ".join(map(str, r.table.tolist())) + "\n")
-        exe = os.path.join(td, "regex_emu")
-        cmd = ["g++", "-std=c++20", "-O1", "-g", "-pthread", "-Wno-attributes", "-I", td, "-I", os.path.join(ROOT, "include"),
-               "-I", os.path.join(ROOT, "hmse_amd", "csrc"),
-               os.path.join(ROOT, "tools", "regex_emu.cpp"), "-o", exe]
-        if a.sanitize:
-            cmd[1:1] = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-        subprocess.check_call(cmd)
-        return subprocess.call([exe, str(a.iters), str(a.seed), os.path.join(td, "automata.txt")])
+    path = os.path.join(td, "automata.txt")
+    with open(path, "w") as f:
+        f.write(f"{len(PATTERNS)}\n")
+        for pat, fl in PATTERNS:
+            r = Regex(pat, bool(fl & 1), bool(fl & 2))
+            f.write(f"{r.n_states} {r.n_classes} {r.reach}\n" + " ".join(map(str, r.classmap.tolist())) + "\n" + " ".join(map(str, r.table.tolist())) + "\n")
+    return [path]
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(run(__doc__, "regex", "constexpr int RX_NT", "// ---- entry points", 20, automata))

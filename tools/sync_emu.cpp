@@ -15,43 +15,8 @@
 #include <thread>
 #include <vector>
 #include "hmse.h"
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __restrict__
-#define __launch_bounds__(...)
-struct uint4 { uint32_t x, y, z, w; };
-struct Idx { uint32_t x; };
-static thread_local Idx threadIdx, blockIdx;
-static inline uint32_t lane_id() { return threadIdx.x & 63u; }
-#define __builtin_amdgcn_readfirstlane(x) (x)
-static inline uint4 load_u4_unaligned(const uint8_t* p) { uint4 v; memcpy(&v, p, 16); return v; }
-static inline uint32_t atomicOr(uint32_t* p, uint32_t v) { return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST); }
-// a ballot of the 64 lanes of one wavefront: every lane of the wavefront must arrive (the kernel's loop is wave-uniform, or this hangs)
-static unsigned long long g_bits[4];
-static std::barrier<>* g_wave[4];
-static inline unsigned long long __ballot(int p) {
-  const uint32_t w = threadIdx.x >> 6;
-  if (p) __atomic_fetch_or(&g_bits[w], 1ull << lane_id(), __ATOMIC_SEQ_CST);
-  g_wave[w]->arrive_and_wait();
-  const unsigned long long v = __atomic_load_n(&g_bits[w], __ATOMIC_SEQ_CST);
-  g_wave[w]->arrive_and_wait();
-  if (lane_id() == 0) __atomic_store_n(&g_bits[w], 0ull, __ATOMIC_SEQ_CST);
-  g_wave[w]->arrive_and_wait();
-  return v;
-}
+#include "hip_on_cpu.h"
 #include "sync_kernels.inc"
-
-static void launch(uint32_t grid, const std::function<void()>& f) {
-  for (uint32_t b = 0; b < grid; b++) {
-    std::barrier<> w0(64), w1(64), w2(64), w3(64);
-    g_wave[0] = &w0; g_wave[1] = &w1; g_wave[2] = &w2; g_wave[3] = &w3;
-    memset(g_bits, 0, sizeof g_bits);
-    std::vector<std::thread> th;
-    for (int t = 0; t < SYNC_NT; t++) th.emplace_back([&, t, b] { threadIdx.x = t; blockIdx.x = b; f(); });
-    for (auto& x : th) x.join();
-  }
-}
 
 static std::mt19937_64 rng(12345);
 static uint64_t R(uint64_t n) { return n ? rng() % n : 0; }
@@ -108,7 +73,7 @@ int main(int argc, char** argv) {
     std::unique_ptr<uint8_t[]> same(new uint8_t[n + 8]);
     memset(same.get(), 0xA5, n + 8);
     uint32_t status = 0, want_status = 0;
-    launch((uint32_t)((n + SYNC_NT / 64 - 1) / (SYNC_NT / 64)),
+    launch_waves<SYNC_NT>((uint32_t)((n + SYNC_NT / 64 - 1) / (SYNC_NT / 64)),
            [&] { sync_match_kernel(A.get(), a_bytes, a_off.data(), a_len.data(), n, B.get(), b_bytes, b_off.data(), b_len.data(), n_b, cand.data(), same.get(), &status); });
     uint64_t n_same = 0;
     for (uint64_t k = 0; k < n && !fails; k++) {
