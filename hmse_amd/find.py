@@ -33,6 +33,16 @@ answered by StoreFinder.count_regex / find_regex / grep_regex with the same thre
 start, the last reach - 1 starts of every chunk are seam starts.  The result is a RegexFound: a Found with the lengths of the matches.
 Out of scope: anchors and \\b, captures, lazy matching, matches over 256 bytes, Unicode classes, several regexes fused into one
 automaton, multi-byte line delimiters, routing find / find_set through the DFA.
+
+Approximate search: StoreFinder.count_approx / find_approx / grep_approx answer "where does something within k edits of this string
+occur?" (Levenshtein distance: insertion, deletion and substitution cost 1 each; patterns of 1..64 bytes, 0 <= k <= 16, k < len(pattern))
+with the same three steps — scan, place, seams (hmse_amd/csrc/approx.hip, Myers' bit-vector algorithm; include/hmse.h hmse_approx_* has
+the definitions, tests/approx_ref.py restates them in plain Python) — split by END: an end with m + k bytes of its record in front of it
+is a scan end, the first m + k - 1 ends of every chunk are seam ends.  The result is an ApproxFound: a Found with the errors of every
+occurrence, whose `offsets` are the matches' LAST bytes (every end within k edits counts, so the neighbouring ends of one fuzzy match
+are each reported; best_ends keeps one per run).  With k = 0 they are find's offsets + m - 1.  StoreFinder.spans gives the (start, end)
+of every occurrence, as text() accepts them.  Out of scope: patterns over 64 bytes, Hamming-only and transposition distances, weighted
+costs, errors inside a regex, a dictionary of approximate patterns (PatternSet), routing find through this path.
 """
 from __future__ import annotations
 
@@ -48,6 +58,7 @@ from .regex import Regex, RegexError  # noqa: F401
 
 MAX_PATTERN_LEN = ops.FIND_MAX_LEN
 GROUP = ops.FIND_MAX_PATTERNS      # patterns per launch; more are answered in groups
+APPROX_GROUP, APPROX_MAX_LEN, APPROX_MAX_K = ops.APPROX_MAX_PATTERNS, ops.APPROX_MAX_LEN, ops.APPROX_MAX_K
 HMSE_FINDSET_MAX_PATTERNS = ops.FINDSET_MAX_PATTERNS     # distinct patterns of a PatternSet
 
 
@@ -61,6 +72,13 @@ class Found:
 @dataclass
 class RegexFound(Found):
     lengths: torch.Tensor = None  # int64, aligned with offsets: occurrence i is corpus[offsets[i] : offsets[i] + lengths[i]]
+
+
+@dataclass
+class ApproxFound(Found):
+    errors: torch.Tensor = None   # int64, aligned with offsets: the edit distance of occurrence i; offsets[i] is the match's LAST byte
+    patterns: tuple = ()          # the patterns (bytes) and ignore_case the occurrences were found with: what spans() needs
+    ignore_case: bool = False
 
 
 @dataclass
@@ -490,6 +508,96 @@ class StoreFinder:
         _lines_args(delim, before, after, reach)
         return self.lines(self.find_regex(rx, max_hits), delim, before, after, reach)
 
+    # ------------------------------------------------------------------ approximate search
+    def _groups_approx(self, patterns, k):
+        """_groups for the approximate search: 8 patterns per launch, each with its error bound -> (pat, [(bounds, ks)], n, the
+        patterns as bytes).  ValueError before any device work."""
+        flat, off = pack_patterns(patterns)
+        n = len(off) - 1
+        ks = [int(k)] * n if isinstance(k, (int, np.integer)) else [int(v) for v in k]
+        if len(ks) != n:
+            raise ValueError(f"find_approx: k has {len(ks)} entries for {n} patterns (an int, or one per pattern)")
+        for j in range(n):
+            m = off[j + 1] - off[j]
+            if m > APPROX_MAX_LEN:
+                raise ValueError(f"find_approx: pattern {j} has {m} bytes; an approximate pattern has 1 to HMSE_APPROX_MAX_LEN = {APPROX_MAX_LEN}")
+            if not 0 <= ks[j] <= APPROX_MAX_K:
+                raise ValueError(f"find_approx: k = {ks[j]} of pattern {j} lies outside 0..HMSE_APPROX_MAX_K = {APPROX_MAX_K}")
+            if ks[j] >= m:
+                raise ValueError(f"find_approx: k = {ks[j]} of pattern {j} is not below its length {m} (every position would match)")
+        pat = torch.from_numpy(flat.copy()).to(self.dev) if n else None
+        blob = flat.tobytes()
+        groups = [(off[g: min(g + APPROX_GROUP, n) + 1], ks[g: g + APPROX_GROUP]) for g in range(0, n, APPROX_GROUP)]
+        return pat, groups, n, tuple(blob[off[j]: off[j + 1]] for j in range(n))
+
+    def _q_approx(self, pat, off, ks, ignore_case) -> _Query:
+        return _Query(lambda cap: ops.approx_scan(self.raw, self.raw_off, self.mult, pat, off, ks, ignore_case, hits_cap=cap),
+                      lambda cap: ops.approx_seams(self.raw, self.raw_off, self.cuts, self.slot, pat, off, ks, ignore_case, hits_cap=cap),
+                      lambda *a: ops.find_place(*a), 8)                          # (the hit word's low byte: errors << 3 | pattern)
+
+    def count_approx(self, patterns, k, ignore_case: bool = False) -> torch.Tensor:
+        """Per pattern the ends within k edits of it (module docstring), int64[P] on the device: two count-only launches per 8
+        patterns, nothing is materialised.  k: an int, or one per pattern."""
+        pat, groups, n, _ = self._groups_approx(patterns, k)
+        if n == 0 or self.n_records == 0:
+            return torch.zeros(n, dtype=torch.int64, device=self.dev)
+        return torch.cat([self._count(self._q_approx(pat, off, ks, ignore_case))[0] for off, ks in groups])
+
+    def find_approx(self, patterns, k, ignore_case: bool = False, max_hits: int = 1 << 24) -> ApproxFound:
+        """Every end within k edits of every pattern, with its errors; `offsets` are the matches' LAST bytes.  Counts first:
+        ValueError naming the counts if their sum exceeds max_hits."""
+        pat, groups, n, pats = self._groups_approx(patterns, k)
+        z = lambda m: torch.zeros(m, dtype=torch.int64, device=self.dev)
+        if n == 0 or self.n_records == 0:
+            return ApproxFound(z(n + 1), z(0), z(n), z(0), pats, bool(ignore_case))
+        qs = [self._q_approx(pat, off, ks, ignore_case) for off, ks in groups]
+        counted = [self._count(q) for q in qs]
+        counts = torch.cat([c[0] for c in counted])
+        total = self._total_within(counts, max_hits)
+        offs, errs = [], []
+        for q, (c, n_scan, n_seam) in zip(qs, counted):
+            found = self._locate(q, n_scan, n_seam)
+            if found:
+                h = torch.cat(found)
+                order = torch.sort(((h & 7) << 56) | (h >> 8))[1]             # by (pattern, offset): offsets stay below 2^56
+                offs.append((h >> 8)[order])
+                errs.append(((h >> 3) & 31)[order])                           # the errors split out of the low byte
+        offsets, errors = (torch.cat(offs), torch.cat(errs)) if offs else (z(0), z(0))
+        self._all_located(offsets.numel(), total)
+        return ApproxFound(self._ptr(counts), offsets, counts, errors, pats, bool(ignore_case))
+
+    def spans(self, found: ApproxFound):
+        """-> (start, end) int64 device tensors, aligned with found.offsets: occurrence i is corpus[start[i] : end[i]], end = offsets + 1
+        and start the LARGEST one whose text has the occurrence's errors — the shortest best match.  The pair is what text() accepts.
+        One hmse_approx_spans call per 8 patterns.  ValueError for a hit that cannot be (an offset outside the corpus, errors that no
+        text ending there attains)."""
+        if not isinstance(found, ApproxFound) or len(found.patterns) != found.counts.numel():
+            raise ValueError("spans: found is the ApproxFound of find_approx")
+        end = found.offsets + 1
+        start = torch.empty_like(end)
+        if end.numel() == 0:
+            return start, end
+        pat, groups, n, _ = self._groups_approx(list(found.patterns), 0)
+        ptr = found.ptr.tolist()
+        for g, (off, _) in enumerate(groups):
+            a, b = ptr[g * APPROX_GROUP], ptr[min((g + 1) * APPROX_GROUP, n)]
+            if a == b:
+                continue
+            j = torch.repeat_interleave(torch.arange(len(off) - 1, dtype=torch.int64, device=self.dev), found.counts[g * APPROX_GROUP: (g + 1) * APPROX_GROUP])
+            words = (found.offsets[a:b] << 8) | (found.errors[a:b] << 3) | j
+            s, st = ops.approx_spans(self.raw, self.raw_off, self.cuts, self.slot, pat, off, found.ignore_case, words.contiguous())
+            if st & 1:
+                raise ValueError("spans: an occurrence lies outside the corpus or has errors that no text ending there attains")
+            start[a:b] = s
+        return start, end
+
+    def grep_approx(self, patterns, k, ignore_case: bool = False, delim: bytes = b"\n", before: int = 0, after: int = 0, reach: int = 1 << 16,
+                    max_hits: int = 1 << 24) -> Lines:
+        """lines(best_ends(find_approx(patterns, k, ignore_case, max_hits)), delim, before, after, reach): per pattern the lines that
+        hold the last byte of a best end."""
+        _lines_args(delim, before, after, reach)
+        return self.lines(best_ends(self.find_approx(patterns, k, ignore_case, max_hits)), delim, before, after, reach)
+
     nonoverlapping = staticmethod(lambda found: nonoverlapping(found))
 
 
@@ -516,6 +624,40 @@ def nonoverlapping(found: RegexFound) -> RegexFound:
     ptr = torch.zeros(P + 1, dtype=torch.int64, device=dev)
     torch.cumsum(counts, 0, out=ptr[1:])
     return RegexFound(ptr, off[kept], counts, ln[kept])
+
+
+def best_ends(found: ApproxFound) -> ApproxFound:
+    """Per pattern the ascending offsets fall into runs of consecutive integers — the neighbouring ends of one fuzzy match; of every
+    run the end with the fewest errors is kept, the leftmost on ties.  Torch plumbing on the tensors' device: run ids by a prefix sum,
+    the minimum of (errors, offset) per run by scatter_reduce — no host loop over the occurrences."""
+    off, err = found.offsets, found.errors
+    n, dev, P = off.numel(), off.device, found.counts.numel()
+    if n == 0:
+        return found
+    pat = torch.repeat_interleave(torch.arange(P, dtype=torch.int64, device=dev), found.counts)
+    new = torch.ones(n, dtype=torch.bool, device=dev)
+    new[1:] = (pat[1:] != pat[:-1]) | (off[1:] != off[:-1] + 1)
+    run = torch.cumsum(new, 0) - 1
+    idx = torch.arange(n, dtype=torch.int64, device=dev)
+    key = (err << 56) | idx                                                      # fewest errors, then leftmost (indices ascend with offsets)
+    best = torch.full((int(run[-1]) + 1,), (1 << 62), dtype=torch.int64, device=dev).scatter_reduce_(0, run, key, "amin")
+    keep = best & ((1 << 56) - 1)
+    counts = torch.bincount(pat[keep], minlength=P)
+    ptr = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, out=ptr[1:])
+    return ApproxFound(ptr, off[keep], counts, err[keep], found.patterns, found.ignore_case)
+
+
+def find_approx(store, patterns, k, device, ignore_case: bool = False, max_hits: int = 1 << 24, verify: bool = True) -> ApproxFound:
+    """One-off form of StoreFinder(store, device, verify).find_approx(patterns, k, ignore_case, max_hits)."""
+    return StoreFinder(store, device, verify).find_approx(patterns, k, ignore_case, max_hits)
+
+
+def grep_approx(store, patterns, k, device, ignore_case: bool = False, delim: bytes = b"\n", before: int = 0, after: int = 0,
+                reach: int = 1 << 16, max_hits: int = 1 << 24, verify: bool = True) -> Lines:
+    """One-off form of StoreFinder(store, device, verify).grep_approx(patterns, k, ignore_case, delim, before, after, reach, max_hits)."""
+    _lines_args(delim, before, after, reach)
+    return StoreFinder(store, device, verify).grep_approx(patterns, k, ignore_case, delim, before, after, reach, max_hits)
 
 
 def find_regex(store, rx, device, max_hits: int = 1 << 24, verify: bool = True) -> RegexFound:

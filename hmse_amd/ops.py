@@ -1020,3 +1020,74 @@ def regex_seams(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, sl
                                                                 n_chunks, C.byref(hdr), _ptr(hits) if cap else None, cap, meta.data_ptr(),
                                                                 _ptr(counts), meta.data_ptr() + 8, _stream())
     return _hit_list(call, "hmse_regex_seams", 1, hits_cap, cuts.device, _BAD_TABLES_OR_AUTOMATON)
+
+
+APPROX_MAX_PATTERNS, APPROX_MAX_LEN, APPROX_MAX_K = 8, 64, 16
+
+
+def _approx_bounds(pat: torch.Tensor, pat_off, k=None):
+    """The patterns' bounds and error bounds as the HOST arrays hmse_approx_* read during the call."""
+    bounds, n_pat = _find_bounds(pat, pat_off)
+    if k is None:
+        return bounds, None, n_pat
+    ks = [int(v) for v in k]
+    if len(ks) != n_pat or any(not 0 <= v <= 255 for v in ks):
+        raise HmseError(-1, "approx: k is one value of 0..255 per pattern")
+    return bounds, (C.c_uint8 * max(n_pat, 1))(*ks), n_pat
+
+
+def approx_scan(raw: torch.Tensor, raw_off: torch.Tensor, mult: torch.Tensor | None, pat: torch.Tensor, pat_off, k, ignore_case: bool = False,
+                hits_cap: int | None = None, raw_bytes: int | None = None):
+    """hmse_approx_scan: every SCAN end of every record [raw_off[r], raw_off[r + 1]) of `raw` — a position p with some text ending at p
+    within k[j] edits of pattern j and p + 1 - raw_off[r] >= m_j + k[j] (`pat` uint8 on the device, `pat_off` and `k` host values).
+    -> (hits int64[n] = position of the match's last byte in raw << 8 | errors << 3 | pattern, any order; n_hits; counts int64[P] = per
+    pattern the sum of mult[record] (int32, None: 1 each)).  hits_cap 0: count only; None: sized by a count-only call.  HmseError for
+    inconsistent tables (device status bit 1).  Replaces the read_store + host dynamic-programme loop."""
+    n_rec = _records_args("approx_scan", raw, raw_off, mult, ((pat, "pat"),))
+    bounds, ks, n_pat = _approx_bounds(pat, pat_off, k)
+    nb = raw.numel() if raw_bytes is None else int(raw_bytes)
+    flags = FIND_IGNORE_CASE if ignore_case else 0
+    lib = _lib.hip_lib()
+    call = lambda hits, cap, meta, counts: lib.hmse_approx_scan(_ptr(raw) if raw.numel() else None, nb, _ptr(raw_off), max(n_rec, 0), _ptr(mult),
+                                                                _ptr(pat), bounds, ks, n_pat, flags, _ptr(hits) if cap else None, cap,
+                                                                meta.data_ptr(), _ptr(counts), meta.data_ptr() + 8, _stream())
+    return _hit_list(call, "hmse_approx_scan", n_pat, hits_cap, raw_off.device)
+
+
+def approx_seams(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, pat: torch.Tensor, pat_off, k,
+                 ignore_case: bool = False, hits_cap: int | None = None):
+    """hmse_approx_seams: every SEAM end of every chunk — the first m_j + k[j] - 1 ends of the chunk, walked through the chunk map from
+    m_j + k[j] bytes in front.  -> (hits int64[n] = corpus offset of the match's last byte << 8 | errors << 3 | pattern, any order;
+    n_hits; counts int64[P] = the seam hits per pattern)."""
+    n_chunks = _chunk_map_args("approx_seams", raw, raw_off, cuts, slot, ((pat, "pat"),))
+    bounds, ks, n_pat = _approx_bounds(pat, pat_off, k)
+    flags = FIND_IGNORE_CASE if ignore_case else 0
+    lib = _lib.hip_lib()
+    keep = lambda t: _ptr(t) if t.numel() else None
+    call = lambda hits, cap, meta, counts: lib.hmse_approx_seams(keep(raw), raw.numel(), _ptr(raw_off), raw_off.numel() - 1, _ptr(cuts), keep(slot),
+                                                                 n_chunks, _ptr(pat), bounds, ks, n_pat, flags, _ptr(hits) if cap else None, cap,
+                                                                 meta.data_ptr(), _ptr(counts), meta.data_ptr() + 8, _stream())
+    return _hit_list(call, "hmse_approx_seams", n_pat, hits_cap, cuts.device)
+
+
+def approx_spans(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, pat: torch.Tensor, pat_off,
+                 ignore_case: bool, hits: torch.Tensor):
+    """hmse_approx_spans: for every hit word (CORPUS offset of the last byte << 8 | errors << 3 | pattern; int64, any order) the start
+    of its shortest best match.  -> (start int64[n], status: bit 0 = some hit lies outside the corpus, names no pattern or has errors
+    that no text ending there attains; its start is offset + 1).  Inconsistent tables (status bit 1) raise HmseError."""
+    _chunk_map_args("approx_spans", raw, raw_off, cuts, slot, ((pat, "pat"), (hits, "hits")))
+    if hits.dtype != torch.int64:
+        raise HmseError(-1, "approx_spans: hits must be torch.int64 (the bits of the u64 hit words)")
+    bounds, _, n_pat = _approx_bounds(pat, pat_off)
+    n, dev = hits.numel(), cuts.device
+    start = _buf(max(n, 1), torch.int64, dev)
+    status = _buf(1, torch.int32, dev, fill=0)
+    keep = lambda t: _ptr(t) if t.numel() else None
+    rc = _lib.hip_lib().hmse_approx_spans(keep(raw), raw.numel(), _ptr(raw_off), raw_off.numel() - 1, _ptr(cuts), keep(slot), slot.numel(),
+                                          _ptr(pat), bounds, n_pat, FIND_IGNORE_CASE if ignore_case else 0, keep(hits), n,
+                                          _ptr(start) if n else None, _ptr(status), _stream())
+    _check(rc, "hmse_approx_spans")
+    st = int(status.item()) & 0xFFFFFFFF
+    if st & 2:
+        raise HmseError(-1, f"hmse_approx_spans device status {st:#x}: inconsistent tables")
+    return start[:n], st

@@ -946,6 +946,63 @@ int hmse_regex_seams(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* raw
                      uint64_t* n_hits, uint64_t* count, uint32_t* status, void* stream);
 
 /*
+ * Approximate search (hmse_amd/find.py StoreFinder.find_approx): where does something within k edits of this byte string occur?  —
+ * agrep's question, at byte granularity.  Replaces read_store -> host -> a dynamic programme over every duplicate chunk.  The matcher is
+ * Myers' bit-vector algorithm: one 64-bit column per pattern, a fixed number of integer operations per byte.
+ *
+ * Definitions (tests/approx_ref.py restates them in plain Python, with Sellers' DP).  C is the N bytes of the corpus.  Patterns are byte
+ * strings of 1..HMSE_APPROX_MAX_LEN bytes, pattern j with an error bound k_j, 0 <= k_j <= HMSE_APPROX_MAX_K and k_j < m_j (with
+ * k >= m every position would match); at most HMSE_APPROX_MAX_PATTERNS per call.  The distance ed is Levenshtein's: insertion,
+ * deletion and substitution cost 1 each.  HMSE_FIND_IGNORE_CASE folds A-Z to a-z on both sides, bytes >= 0x80 compare as they are.
+ *   d_j(e) = min over 0 <= s <= e of ed(pat_j, C[s .. e))   for an END e, 1 <= e <= N
+ *   e is an OCCURRENCE of pattern j iff d_j(e) <= k_j; its errors are d_j(e); its reported position is e - 1, the match's LAST byte
+ *   (below N).  Every end counts: the neighbouring ends of one fuzzy match are each reported.  With k = 0 the occurrences are
+ *   hmse_find_*'s offsets + m - 1.
+ * Window.  W_j = m_j + k_j.  A start in front of e - W_j never gives a distance <= k_j (the text would be more than k_j bytes longer
+ * than the pattern), so a column started fresh (D[i] = i) anywhere at or in front of e - W_j gives d_j(e) whenever that is <= k_j and
+ * some value > k_j otherwise, whatever bytes lie in front of the window.
+ * Partition by END (hmse_regex_*'s rule mirrored): end e lies in chunk c if byte e - 1 does.  It is a SCAN end iff e - cuts[c] >= W_j —
+ * the answer depends on the record only (hmse_approx_scan, laid out by hmse_find_place, which passes the low byte through) — and a
+ * SEAM end otherwise: the first min(W_j - 1, chunk length) ends of every chunk, walked through the chunk map from
+ * max(cuts[c] + 1 - W_j, 0) on, over any number of tiny or empty chunks (hmse_approx_seams: at most 2 W_j - 2 steps per chunk and
+ * pattern).  Scan ends placed plus seam ends of all chunks are every occurrence exactly once.
+ * Span.  The start of an occurrence is the largest s with ed(pat_j, C[s .. e)) == d_j(e): the shortest best match, of m - d .. m + d
+ * bytes.  hmse_approx_spans finds it with the anchored column (D[0][t] = t) of the reversed pattern over C[e-1], C[e-2], ...
+ *
+ * A hit is one u64: position << 8 | errors << 3 | pattern index; position = offset in raw (scan), corpus offset (seams) of the
+ * match's last byte.
+ *   pat      DEVICE u8: the patterns back to back;  pat_off HOST u32[n_pat + 1], k HOST u8[n_pat]: read during the call
+ *   flags    HMSE_FIND_IGNORE_CASE or 0
+ *   hits, hits_cap, n_hits as for hmse_find_*: hits_cap == 0 counts only; n_hits and counts stay exact when the list runs out
+ *   counts   DEVICE u64[n_pat]: scan = per pattern the sum of mult[record] over its hits (mult NULL: 1 each), seams = its hits
+ *   status   DEVICE u32[1]: bit0 = the hit list ran out, bit1 = inconsistent tables (hmse_find_*'s rules): nothing is read through
+ *            them, no hit is written, n_hits and counts are 0
+ * hmse_approx_spans: hits DEVICE u64[n] = hit words with CORPUS offsets, any order; start DEVICE u64[n], written for every i < n.
+ *   status bit0: some hit has an offset >= N, a pattern index >= n_pat or errors that no window of m_j + errors bytes ending there
+ *   attains — such a hit gets start = offset + 1, an empty span.  bit1 as above (nothing is written).  n == 0 clears the status word.
+ * The other arguments mean what they mean for hmse_find_scan / hmse_find_seams.  HMSE_EINVAL before anything is cleared or launched:
+ * n_pat of 0 or above HMSE_APPROX_MAX_PATTERNS, a pattern length of 0 or above HMSE_APPROX_MAX_LEN, k[j] >= its length or above
+ * HMSE_APPROX_MAX_K, unknown flag bits, raw_bytes >= 2^56, a NULL pointer to a non-empty array.  No workspace; stream-ordered,
+ * allocate nothing, never sync.  Profile slots: hmse_approx_scan reports in 30, hmse_approx_seams and hmse_approx_spans in 31.
+ * Out of scope: patterns over 64 bytes, Hamming-only and transposition distances, weighted costs, errors inside a regex, a
+ * dictionary of approximate patterns.
+ */
+#define HMSE_APPROX_MAX_PATTERNS 8
+#define HMSE_APPROX_MAX_LEN      64
+#define HMSE_APPROX_MAX_K        16
+
+int hmse_approx_scan(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* raw_off, uint64_t n_rec, const uint32_t* mult,
+                     const uint8_t* pat, const uint32_t* pat_off, const uint8_t* k, uint32_t n_pat, uint32_t flags, uint64_t* hits,
+                     uint64_t hits_cap, uint64_t* n_hits, uint64_t* counts, uint32_t* status, void* stream);
+int hmse_approx_seams(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* raw_off, uint64_t n_rec, const uint64_t* cuts,
+                      const uint64_t* slot, uint64_t n_chunks, const uint8_t* pat, const uint32_t* pat_off, const uint8_t* k,
+                      uint32_t n_pat, uint32_t flags, uint64_t* hits, uint64_t hits_cap, uint64_t* n_hits, uint64_t* counts,
+                      uint32_t* status, void* stream);
+int hmse_approx_spans(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* raw_off, uint64_t n_rec, const uint64_t* cuts,
+                      const uint64_t* slot, uint64_t n_chunks, const uint8_t* pat, const uint32_t* pat_off, uint32_t n_pat,
+                      uint32_t flags, const uint64_t* hits, uint64_t n, uint64_t* start, uint32_t* status, void* stream);
+
+/*
  * Diagnostics (bench.py's roofline leg): when enabled, every entry point brackets its DOMINANT
  * kernel launch with a HIP event pair on the caller's stream.  hmse_profile_read() waits for the
  * recorded events (a host sync — never call it inside a capture), adds their durations to the
@@ -955,7 +1012,7 @@ int hmse_regex_seams(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* raw
  * records) and 30 and 31 (DELTA records) (hmse_amd/csrc/l1_deflate.hip); hmse_find_scan also reports in 30, hmse_find_seams and
  * hmse_find_place in 31, hmse_sync_match in 19; hmse_findset_scan reports in 30 as well, hmse_findset_seams and hmse_findset_place in 31.
  * hmse_lines_extent and hmse_lines_gather report in 31 as well (reset the slot before reading one of them: it is shared).
- * hmse_regex_scan reports in 30 and hmse_regex_seams in 31, too.
+ * hmse_regex_scan reports in 30 and hmse_regex_seams in 31, too; so do hmse_approx_scan (30), hmse_approx_seams and hmse_approx_spans (31).
  * hmse_profile_counter(): work counted on the device while profiling is on — the DEFLATE match kernels add the TOKENS they
  * write to their slot (8..13, 18..23), the encode kernels the tokens they read (14, 15, 30, 31):
  * bench.py's algorithmic bytes come from these counts, not from an assumed token density.  A host sync; diagnostics only.
