@@ -200,6 +200,12 @@ def hip_lib():
         L.hmse_approx_seams.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _U64, _VP, u32p, u8p, _U32, _U32, _VP, _U64, _VP, _VP, _VP, _VP]
         L.hmse_approx_spans.restype = C.c_int
         L.hmse_approx_spans.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _U64, _VP, u32p, _U32, _U32, _VP, _U64, _VP, _VP, _VP]
+        L.hmse_crc32.restype = C.c_int
+        L.hmse_crc32.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _VP]
+        L.hmse_crc32_combine.restype = C.c_int
+        L.hmse_crc32_combine.argtypes = [_VP, _VP, _U64, _VP, _VP, _VP]
+        L.hmse_gzip_members.restype = C.c_int
+        L.hmse_gzip_members.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _VP, _VP, _VP, _U64, _VP, _U64, _VP, _U32, _VP, _U64, _VP, _VP]
         L.hmse_sync_match.restype = C.c_int
         L.hmse_sync_match.argtypes = [_VP, _U64, _VP, _VP, _U64, _VP, _U64, _VP, _VP, _U64, _VP, _VP, _VP, _VP]
         L.hmse_lines_extent.restype = C.c_int
@@ -231,4 +237,4 @@ EXPORTED_SYMBOLS = (
     "hmse_cfg_default", "hmse_cfg_validate", "hmse_abi_version", "hmse_strerror", "hmse_gear_table",
     "hmse_workspace_bytes", "hmse_l2_cdc", "hmse_l3_sha256", "hmse_l3_dedup", "hmse_l3_index_slots", "hmse_l3_index_update",
     "hmse_l4_lsh_slots", "hmse_l4_lsh_update", "hmse_l4_minhash",
-    "hmse_l4_lsh", "hmse_l1_deflate", "hmse_l1_deflate_ex", "hmse_l1_deflate_record_bytes", "hmse_l1_deflate_record_bytes_dict", "hmse_l1_inflate", "hmse_l1_inflate_mode", "hmse_read_assemble", "hmse_manifest_pack", "hmse_manifest_pack_ex", "hmse_stream_batch", "hmse_stream_batch_workspace_bytes", "hmse_stream_workspace_init", "hmse_stream_row_bytes", "hmse_stream_piece_hash", "hmse_stream_piece_encode", "hmse_stream_sig_cap", "hmse_stream_sig_row_bytes", "hmse_stream_piece_sign", "hmse_stream_piece_bases", "hmse_stream_piece_encode_g", "hmse_gc_plan", "hmse_record_gather", "hmse_band_tables_bound", "hmse_band_tables_workspace_bytes", "hmse_band_tables_write", "hmse_l4_index_build", "hmse_l4_query", "hmse_scrub_records", "hmse_scrub_attribute", "hmse_find_scan", "hmse_find_seams", "hmse_find_place", "hmse_findset_scan", "hmse_findset_seams", "hmse_findset_place", "hmse_sync_match", "hmse_lines_extent", "hmse_lines_gather", "hmse_regex_scan", "hmse_regex_seams", "hmse_approx_scan", "hmse_approx_seams", "hmse_approx_spans", "hmse_profile_enable", "hmse_profile_read", "hmse_profile_counter")
+    "hmse_l4_lsh", "hmse_l1_deflate", "hmse_l1_deflate_ex", "hmse_l1_deflate_record_bytes", "hmse_l1_deflate_record_bytes_dict", "hmse_l1_inflate", "hmse_l1_inflate_mode", "hmse_read_assemble", "hmse_manifest_pack", "hmse_manifest_pack_ex", "hmse_stream_batch", "hmse_stream_batch_workspace_bytes", "hmse_stream_workspace_init", "hmse_stream_row_bytes", "hmse_stream_piece_hash", "hmse_stream_piece_encode", "hmse_stream_sig_cap", "hmse_stream_sig_row_bytes", "hmse_stream_piece_sign", "hmse_stream_piece_bases", "hmse_stream_piece_encode_g", "hmse_gc_plan", "hmse_record_gather", "hmse_band_tables_bound", "hmse_band_tables_workspace_bytes", "hmse_band_tables_write", "hmse_l4_index_build", "hmse_l4_query", "hmse_scrub_records", "hmse_scrub_attribute", "hmse_find_scan", "hmse_find_seams", "hmse_find_place", "hmse_findset_scan", "hmse_findset_seams", "hmse_findset_place", "hmse_sync_match", "hmse_lines_extent", "hmse_lines_gather", "hmse_regex_scan", "hmse_regex_seams", "hmse_approx_scan", "hmse_approx_seams", "hmse_approx_spans", "hmse_crc32", "hmse_crc32_combine", "hmse_gzip_members", "hmse_profile_enable", "hmse_profile_read", "hmse_profile_counter")

@@ -22,6 +22,8 @@ STAGE_L4_INDEX, STAGE_L4_QUERY = 26, 27
 STAGE_SCRUB_RECORDS, STAGE_SCRUB_ATTRIBUTE = 28, 29
 STAGE_FIND_SCAN, STAGE_FIND_PLACE = 30, 31
 STAGE_SYNC_MATCH = 19
+STAGE_EXPORT_CRC, STAGE_EXPORT_MEMBERS = 0, 1
+GZIP_BGZF = 1
 QUERY_EXCLUDE_SELF = 1
 FIND_MAX_PATTERNS, FIND_MAX_LEN, FIND_IGNORE_CASE = 32, 256, 1
 LINES_START_CUT, LINES_END_CUT, LINES_BAD, LINES_MAX_REACH = 1, 2, 128, 1 << 24
@@ -1091,3 +1093,74 @@ def approx_spans(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, s
     if st & 2:
         raise HmseError(-1, f"hmse_approx_spans device status {st:#x}: inconsistent tables")
     return start[:n], st
+
+
+def crc32(data: torch.Tensor, cuts: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """hmse_crc32: the zlib / gzip CRC-32 of every range data[cuts[k], cuts[k + 1]) (`cuts` int64[n + 1], ascending; ranges may be empty,
+    start at any byte and have any length).  -> int32[n] (u32 bits; `out` if given).  Descending cuts or cuts[-1] > data.numel() are
+    refused and `out` is left as it was."""
+    _require_gpu(data, "data")
+    _require_gpu(cuts, "cuts")
+    n = cuts.numel() - 1
+    if n < 0:
+        raise HmseError(-1, "crc32: cuts is empty")
+    dev = cuts.device
+    if out is None:
+        out = _buf(n, torch.int32, dev)
+    _require_gpu(out, "out")
+    if out.numel() != n or out.dtype != torch.int32:
+        raise HmseError(-1, "crc32: out is not int32[n]")
+    status = _buf(1, torch.int32, dev, fill=0)
+    rc = _lib.hip_lib().hmse_crc32(_ptr(data) if data.numel() else None, data.numel(), _ptr(cuts), n, _ptr(out) if n else None, _ptr(status), _stream())
+    _check(rc, "hmse_crc32")
+    if n and int(status.item()):
+        raise HmseError(-1, "hmse_crc32: cuts descends or ends behind the data")
+    return out
+
+
+def crc32_combine(crc: torch.Tensor, lens: torch.Tensor) -> int:
+    """hmse_crc32_combine: the CRC-32 of the concatenation of ranges given only their CRCs (int32[n], u32 bits) and lengths (int64[n];
+    exponents only: any values whose sum stays below 2^61).  -> the CRC as a Python int (0 for n == 0)."""
+    _require_gpu(crc, "crc")
+    _require_gpu(lens, "lens")
+    n = crc.numel()
+    if lens.numel() != n or crc.dtype != torch.int32 or lens.dtype != torch.int64:
+        raise HmseError(-1, "crc32_combine: crc int32[n] / lens int64[n] do not match")
+    meta = _buf(2, torch.int32, crc.device, fill=0)       # [out, status]
+    rc = _lib.hip_lib().hmse_crc32_combine(_ptr(crc) if n else None, _ptr(lens) if n else None, n, meta.data_ptr(), meta.data_ptr() + 4, _stream())
+    _check(rc, "hmse_crc32_combine")
+    return int(meta[0].item()) & 0xFFFFFFFF
+
+
+def gzip_members(src0: torch.Tensor, src1: torch.Tensor | None, src_off: torch.Tensor, stream_len: torch.Tensor, src_sel: torch.Tensor,
+                 crc: torch.Tensor, raw_off: torch.Tensor, slot: torch.Tensor, member_off: torch.Tensor, bgzf: bool = False,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """hmse_gzip_members: one gzip (or BGZF) member per chunk at member_off (int64[n_chunks + 1], the caller's prefix sum of header +
+    stream + 8): header, the stream of record slot[i] — stream_len[r] bytes at src_off[r] of (src1 if src_sel[r] else src0) —, crc[r]
+    and the record's raw length raw_off[r + 1] - raw_off[r].  Returns the uint8 destination (`out`, or a new tensor of member_off[-1]
+    bytes).  A member outside its source or destination, or a size that is not header + stream + 8, is refused: nothing is written."""
+    srcs = [(src0, "src0")] + ([(src1, "src1")] if src1 is not None else [])
+    for t, nm in srcs + [(src_off, "src_off"), (stream_len, "stream_len"), (src_sel, "src_sel"), (crc, "crc"), (raw_off, "raw_off"), (slot, "slot"),
+                         (member_off, "member_off")]:
+        _require_gpu(t, nm)
+    n_rec, n_chunks = src_off.numel(), slot.numel()
+    if stream_len.numel() != n_rec or src_sel.numel() != n_rec or crc.numel() != n_rec or raw_off.numel() != n_rec + 1 or member_off.numel() != n_chunks + 1:
+        raise HmseError(-1, "gzip_members: the record tables / slot / member_off do not match")
+    if crc.dtype != torch.int32 or src_sel.dtype != torch.uint8 or any(t.dtype != torch.int64 for t in (src_off, stream_len, raw_off, slot, member_off)):
+        raise HmseError(-1, "gzip_members: crc int32, src_sel uint8, the other tables int64")
+    dev = member_off.device
+    if out is None:
+        out = _buf(int(member_off[-1].item()), torch.uint8, dev)
+    _require_gpu(out, "out")
+    status = _buf(1, torch.int32, dev, fill=0)
+    keep = lambda t: t if t is not None and t.numel() else None
+    rc = _lib.hip_lib().hmse_gzip_members(_ptr(keep(src0)), src0.numel(), _ptr(keep(src1)), 0 if src1 is None else src1.numel(), _ptr(src_off),
+                                          _ptr(stream_len), _ptr(src_sel), _ptr(crc), _ptr(raw_off), n_rec, _ptr(slot), n_chunks, _ptr(member_off),
+                                          GZIP_BGZF if bgzf else 0, _ptr(out) if out.numel() else None, out.numel(), _ptr(status), _stream())
+    _check(rc, "hmse_gzip_members")
+    st = int(status.item()) if n_chunks else 0
+    if st & 1:
+        raise HmseError(-2, "hmse_gzip_members: a member lies outside its source or the destination, or its size is not header + stream + 8")
+    if st & 2:
+        raise HmseError(-2, "hmse_gzip_members: a BGZF member above 65536 bytes")
+    return out

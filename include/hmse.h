@@ -60,6 +60,9 @@ enum {
 
 /* stage ids for hmse_workspace_bytes() */
 enum {
+  /* export as gzip (hmse_crc32, hmse_gzip_members: no workspace, 0 bytes); profile slots of their own */
+  HMSE_STAGE_EXPORT_CRC     = 0,
+  HMSE_STAGE_EXPORT_MEMBERS = 1,
   HMSE_STAGE_L2_CDC     = 2,
   HMSE_STAGE_L3_SHA256  = 3,
   HMSE_STAGE_L3_DEDUP   = 4,
@@ -1003,6 +1006,43 @@ int hmse_approx_spans(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* ra
                       uint32_t flags, const uint64_t* hits, uint64_t n, uint64_t* start, uint32_t* status, void* stream);
 
 /*
+ * Export (hmse_amd/export.py): a store as multi-member gzip (RFC 1952) or BGZF.  A stored FULL record is a complete raw DEFLATE stream,
+ * so its member is header + the stream as stored + CRC-32 + raw length; a DELTA record is encoded again without its dictionary first
+ * (hmse_l1_deflate), gzip has none.  One member per chunk of the corpus, in corpus order, POINTER chunks included.
+ *
+ * Definitions (tests/export_ref.py restates them in plain Python).  The CRC-32 is zlib's and gzip's: polynomial 0xEDB88320 (reflected),
+ * initial value and final xor 0xFFFFFFFF; an empty range gives 0.  With x^k the polynomial x^k modulo that one, in the register's bit
+ * order, and * the product modulo it:  crc(A | B) = crc(A) * x^(8 |B|) ^ crc(B).
+ *
+ * hmse_crc32: crc_out[k] = CRC-32 of data[cuts[k], cuts[k + 1]) for the n_chunks ranges of cuts (DEVICE u64[n_chunks + 1], ascending;
+ *   ranges may be empty, start at any byte and have any length).  status DEVICE u32[1]: bit0 = cuts descends somewhere or
+ *   cuts[n_chunks] > n — nothing is read through cuts, crc_out is left as it was.  n_chunks == 0 clears the status word.
+ * hmse_crc32_combine: out[0] = CRC-32 of the concatenation of n ranges given their CRCs (DEVICE u32[n]) and lengths (DEVICE u64[n], any
+ *   values whose sum stays below 2^61: they are exponents only).  n == 0 gives 0.  status is cleared; no bit is defined.
+ * hmse_gzip_members: member i (0 <= i < n_chunks) = header + stream of record r = slot[i] + crc[r] (u32 LE) + raw_off[r + 1] - raw_off[r]
+ *   (u32 LE) at dst + member_off[i]; the stream is stream_len[r] bytes at src_off[r] of src1 if src_sel[r] else of src0 (as for
+ *   hmse_record_gather: the store's blob and the streams encoded again).  All tables DEVICE: src_off, stream_len u64[n_rec], src_sel
+ *   u8[n_rec], crc u32[n_rec], raw_off u64[n_rec + 1], slot u64[n_chunks], member_off u64[n_chunks + 1] (the caller's prefix sum).
+ *   flags 0: the 10-byte header 1f 8b 08 00 | MTIME 0 | XFL 0 | OS ff.  HMSE_GZIP_BGZF: the 18-byte header 1f 8b 08 04 00 00 00 00 00 ff
+ *   06 00 42 43 02 00 + BSIZE (u16 LE) = the member's size - 1; the caller appends the 28-byte EOF block.
+ *   status DEVICE u32[1]: bit0 = slot[i] >= n_rec, a stream outside its source, a member outside dst_bytes, member_off descending or
+ *   member_off[i + 1] - member_off[i] != header + stream_len[r] + 8, a raw length above 2^32 - 1; bit1 = a BGZF member above 65536 bytes
+ *   (a chunk of at most 32768 bytes never gives one).  With either bit nothing is written to dst.
+ * HMSE_EINVAL before anything is cleared or launched: status NULL, unknown flag bits, a NULL pointer to a non-empty array, n_chunks
+ * above 2^40 (hmse_crc32), n above 2^32 (hmse_crc32_combine), n_chunks >= 2^33 (hmse_gzip_members).  No workspace; stream-ordered,
+ * allocate nothing, never sync.  Profile slots: hmse_crc32 reports in 0, hmse_gzip_members in 1.
+ * Out of scope: byte ranges or single documents, containers, other codecs, one member for the whole corpus, importing gzip.
+ */
+#define HMSE_GZIP_BGZF 1u
+
+int hmse_crc32(const uint8_t* data, uint64_t n, const uint64_t* cuts, uint64_t n_chunks, uint32_t* crc_out, uint32_t* status, void* stream);
+int hmse_crc32_combine(const uint32_t* crc, const uint64_t* len, uint64_t n, uint32_t* out, uint32_t* status, void* stream);
+int hmse_gzip_members(const uint8_t* src0, uint64_t src0_bytes, const uint8_t* src1, uint64_t src1_bytes, const uint64_t* src_off,
+                      const uint64_t* stream_len, const uint8_t* src_sel, const uint32_t* crc, const uint64_t* raw_off, uint64_t n_rec,
+                      const uint64_t* slot, uint64_t n_chunks, const uint64_t* member_off, uint32_t flags, uint8_t* dst, uint64_t dst_bytes,
+                      uint32_t* status, void* stream);
+
+/*
  * Diagnostics (bench.py's roofline leg): when enabled, every entry point brackets its DOMINANT
  * kernel launch with a HIP event pair on the caller's stream.  hmse_profile_read() waits for the
  * recorded events (a host sync — never call it inside a capture), adds their durations to the
@@ -1013,6 +1053,7 @@ int hmse_approx_spans(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* ra
  * hmse_find_place in 31, hmse_sync_match in 19; hmse_findset_scan reports in 30 as well, hmse_findset_seams and hmse_findset_place in 31.
  * hmse_lines_extent and hmse_lines_gather report in 31 as well (reset the slot before reading one of them: it is shared).
  * hmse_regex_scan reports in 30 and hmse_regex_seams in 31, too; so do hmse_approx_scan (30), hmse_approx_seams and hmse_approx_spans (31).
+ * hmse_crc32 reports in 0 and hmse_gzip_members in 1 (HMSE_STAGE_EXPORT_*): slots of their own.
  * hmse_profile_counter(): work counted on the device while profiling is on — the DEFLATE match kernels add the TOKENS they
  * write to their slot (8..13, 18..23), the encode kernels the tokens they read (14, 15, 30, 31):
  * bench.py's algorithmic bytes come from these counts, not from an assumed token density.  A host sync; diagnostics only.

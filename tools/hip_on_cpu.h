@@ -1,4 +1,4 @@
-// hip_on_cpu.h — what the emulators (find_emu, findset_emu, lines_emu, regex_emu, approx_emu, sync_emu) put under a HIP kernel to run it on the CPU:
+// hip_on_cpu.h — what the emulators (find_emu, findset_emu, lines_emu, regex_emu, approx_emu, export_emu, sync_emu) put under a HIP kernel to run it on the CPU:
 // one std::thread per lane, a std::barrier under __syncthreads and one per wavefront under __ballot (a loop that is not wave-uniform hangs
 // it), a plain prefix sum for block_exclusive_scan, and the launcher.  Include it after "hmse.h" and in front of hmse_amd/csrc/chunkmap.h,
 // blockops.h and the kernels cut out of a .hip file.
@@ -24,6 +24,7 @@ static std::barrier<>* g_bar;                            // the workgroup's barr
 static inline void __syncthreads() { g_bar->arrive_and_wait(); }
 static inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
 static inline uint32_t atomicOr(uint32_t* p, uint32_t v) { return __atomic_fetch_or(p, v, __ATOMIC_SEQ_CST); }
+static inline uint32_t atomicXor(uint32_t* p, uint32_t v) { return __atomic_fetch_xor(p, v, __ATOMIC_SEQ_CST); }
 static inline uint32_t emu_alignbyte(uint32_t hi, uint32_t lo, uint32_t b) { return (uint32_t)(((((uint64_t)hi) << 32) | lo) >> (8 * (b & 3))); }
 #define __builtin_amdgcn_alignbyte emu_alignbyte
 #define __builtin_amdgcn_readfirstlane(x) (x)
