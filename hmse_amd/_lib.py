@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+from typing import NamedTuple
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # HMSE_LIB_VARIANT=<tag> (diagnostics / A-B experiments only): load csrc/libhmse_hip_<tag>.so instead — e.g. the stamps or diag build
@@ -66,10 +67,162 @@ def build(force: bool = False) -> None:
     subprocess.check_call(args)
 
 
+# Every entry point of include/hmse.h, once: "<return>: <kind> <name>, ..." in the header's parameter order and under its parameter names
+# (tests/test_abi.py holds the table against the header).  A parameter's kind is one of
+#   u8* u32* i32* u64* i64*       a DEVICE pointer to elements of that width -> c_void_p; ops._call refuses a tensor of another element size
+#   void*                         a device pointer to opaque bytes (workspaces, exchange rows, packed records): no width to check
+#   u8*? ... void*?               the same, and ops._call passes NULL for an EMPTY tensor
+#   u8[] u32[] u64[] f64[]        a HOST array, read or written during the call -> POINTER(c_...)
+#   hmse_cfg* hmse_stream* hmse_gl4* hmse_findset* hmse_regex*      a HOST struct -> POINTER(its mirror above)
+#   u32 u64 size_t int            a scalar
+#   stream                        the HIP stream, always last: the entry point enqueues device work (ops._call appends the current stream)
+# and it returns int (a status), void, u64, size_t or str.  hmse_gear_table fills a host table; it takes its address like a device pointer's.
+SIGNATURES = {
+    "hmse_cfg_default": "void: hmse_cfg* cfg",
+    "hmse_cfg_validate": "int: hmse_cfg* cfg",
+    "hmse_abi_version": "int:",
+    "hmse_strerror": "str: int code",
+    "hmse_gear_table": "void: u64* table",
+    "hmse_workspace_bytes": "size_t: int stage, u64 n, hmse_cfg* cfg",
+    "hmse_l2_cdc": "int: u8* data, u64 n, u64* seg_off, u32 n_seg, hmse_cfg* cfg, u64* cuts, u64 cuts_cap, u64* n_cuts, u32* status, "
+                   "void* ws, size_t ws_bytes, stream",
+    "hmse_l3_sha256": "int: u8* data, u64 n, u64* cuts, u64 n_chunks, u8* digests, void* ws, size_t ws_bytes, stream",
+    "hmse_l3_dedup": "int: u8* digests_all, u64 n_all, u64* first_occ, u32* refcount, void* ws, size_t ws_bytes, stream",
+    "hmse_l3_index_slots": "u64: u64 capacity_chunks",
+    "hmse_l3_index_update": "int: u8* digests_all, u64 n_old, u64 n_new, u64* first_occ, u32* refcount, u32* table, u64 slots, stream",
+    "hmse_l4_minhash": "int: u8* data, u64 n, u64* cuts, u64* chunk_ids, u64 n_sel, hmse_cfg* cfg, u32* sig, void* ws, size_t ws_bytes, stream",
+    "hmse_l4_lsh": "int: u32* sig, u64 n_sel, hmse_cfg* cfg, u32* band_keys, i64* base, void* ws, size_t ws_bytes, stream",
+    "hmse_l4_lsh_slots": "u64: u64 capacity_chunks",
+    "hmse_l4_lsh_update": "int: u32* sig_all, u64 n_old, u64 n_new, hmse_cfg* cfg, u32* band_keys, i64* base, u32* tables, u64 slots, u32 keys_given, stream",
+    "hmse_l1_deflate": "int: u8* data, u64 n, u64* cuts, u64* chunk_ids, i64* base, u64 n_sel, hmse_cfg* cfg, u8* out, u64 out_cap, u64* out_off, "
+                       "u8* kind, u32* status, void* ws, size_t ws_bytes, stream",
+    "hmse_l1_deflate_record_bytes": "u64: u32 chunk_len",
+    "hmse_l1_deflate_record_bytes_dict": "u64: u32 chunk_len",
+    "hmse_l1_deflate_ex": "int: u8* data, u64 n, u64* cuts, u64* chunk_ids, i64* base, u64 n_sel, hmse_cfg* cfg, u32 flags, u8* out, u64 out_cap, "
+                          "u64* out_off, u8* kind, u32* status, void* ws, size_t ws_bytes, stream",
+    "hmse_l1_inflate": "int: u8* streams, u64 streams_bytes, u64* stream_off, u32* stream_len, u8* kind, i64* base, u64 n_sel, u64* raw_off, "
+                       "u8* raw_out, u64 raw_cap, u8* ok, u32* status, void* ws, size_t ws_bytes, stream",
+    "hmse_l1_inflate_mode": "int: int mode",
+    "hmse_read_assemble": "int: u64* cuts, u64 n_chunks, u64* slot_of_chunk, u64 n_slots, u64* raw_off, u8* raw, u8* data_out, u64 n, u32* status, stream",
+    "hmse_stream_batch_workspace_bytes": "u64: u64 batch_bytes, hmse_cfg* cfg",
+    "hmse_stream_workspace_init": "int: void* ws, size_t ws_bytes, u64 batch_bytes, hmse_cfg* cfg, stream",
+    "hmse_stream_batch": "int: u8* data, u64 data_cap, u64 batch_bytes, u64* seg_off, u32 n_seg, hmse_cfg* cfg, hmse_stream* s, "
+                         "void* ws, size_t ws_bytes, stream",
+    "hmse_stream_row_bytes": "u64: u64 cap_bytes, hmse_cfg* cfg",
+    "hmse_stream_piece_hash": "int: u8* data, u64 data_cap, u64 piece_bytes, u64 cap_bytes, u64* seg_off, u32 n_seg, hmse_cfg* cfg, hmse_stream* s, "
+                              "void* row, void* ws, size_t ws_bytes, stream",
+    "hmse_stream_piece_encode": "int: u8* data, u64 data_cap, u64 piece_bytes, u64 cap_bytes, hmse_cfg* cfg, hmse_stream* s, void* rows, "
+                                "void* ws, size_t ws_bytes, stream",
+    "hmse_stream_sig_cap": "u64: u64 cap_bytes, hmse_cfg* cfg",
+    "hmse_stream_sig_row_bytes": "u64: u64 cap_bytes, hmse_cfg* cfg",
+    "hmse_stream_piece_sign": "int: u8* data, u64 data_cap, u64 piece_bytes, u64 cap_bytes, hmse_cfg* cfg, hmse_stream* s, void* rows, void* sig_row, "
+                              "void* ws, size_t ws_bytes, stream",
+    "hmse_stream_piece_bases": "int: u64 cap_bytes, hmse_cfg* cfg, hmse_stream* s, void* sig_rows, hmse_gl4* g, void* ws, size_t ws_bytes, stream",
+    "hmse_stream_piece_encode_g": "int: u8* data, u64 data_cap, u64 piece_bytes, u64 cap_bytes, hmse_cfg* cfg, hmse_stream* s, u64* gstate, "
+                                  "void* ws, size_t ws_bytes, stream",
+    "hmse_manifest_pack": "int: u8* streams, u64* stream_off, u8* kind, i64* base, u64* uniq_ids, u64 n_unique, u8* digests, u32* refcount, u64* cuts, "
+                          "u64 n_chunks, u64* first_occ, u64 chunk_base, u32 shard, u64* shard_bases, u32 n_shards, u64* rec_off, u32 lba_unit, "
+                          "u64* ptr_index, u8* blob, u64 blob_bytes, void* index, void* chunk_map, void*? pointers, u64 n_pointers, u32* status, "
+                          "void* ws, size_t ws_bytes, stream",
+    "hmse_manifest_pack_ex": "int: u8* streams, u64* stream_off, u8* kind, i64* base, u64* uniq_ids, u64 n_unique, u8* digests, u32* refcount, u64* cuts, "
+                             "u64 n_chunks, u64* first_occ, u64 chunk_base, u32 shard, u64* shard_bases, u32 n_shards, u32 flags, u64* rec_off, "
+                             "u32 lba_unit, u64* ptr_index, u8* blob, u64 blob_bytes, void* index, void* chunk_map, void*? pointers, u64 n_pointers, "
+                             "u32* status, void* ws, size_t ws_bytes, stream",
+    "hmse_gc_plan": "int: u64* cuts, u64 n_chunks, u32* slot, u64 n_slots, u64* seg_off, u32 n_seg, u8* drop, u8* digests_old, u64* counts, "
+                    "i64* old_chunk, i64* first_occ, u32* refcount, u8* digests, i64* uniq_ids, i64* old_slot, i64* new_slot_of_old, u32* status, "
+                    "void* ws, size_t ws_bytes, stream",
+    "hmse_record_gather": "int: u8*? src0, u64 src0_bytes, u8*? src1, u64 src1_bytes, u64* src_off, u8* src_sel, u64* dst_off, u64 n, u8*? dst, "
+                          "u64 dst_bytes, u32* status, stream",
+    "hmse_band_tables_bound": "u64: u64 n, u32 bands, u32 band_bits, u32 n_hashes",
+    "hmse_band_tables_workspace_bytes": "size_t: u64 n",
+    "hmse_band_tables_write": "int: u32*? band_keys, u64 n, u32 bands, u32 band_bits, u32*? sig, u32 n_hashes, u8* out, u64 out_cap, u64* out_bytes, "
+                              "u32* status, void* ws, size_t ws_bytes, stream",
+    "hmse_l4_index_build": "int: u32*? keys, u64 n, u32 bands, u32*? sorted_keys, u32*? sorted_ids, u32* status, void* ws, size_t ws_bytes, stream",
+    "hmse_l4_query": "int: u32*? sig_q, u32*? keys_q, u64 n_q, u32*? sig_s, u64 n_s, u32*? sorted_keys, u32*? sorted_ids, hmse_cfg* cfg, u32 top_k, "
+                     "u32 min_score, u32 flags, i64*? out_ids, i32*? out_scores, u32*? n_hits, u64*? n_candidates, u32* status, "
+                     "void* ws, size_t ws_bytes, stream",
+    "hmse_scrub_records": "int: u8* blob, u64 blob_bytes, u64 n, u32 n_shards, u32*? rec_shard, u64*? shard_blob, u64*? shard_slot, u32*? lba_unit, "
+                          "u32*? lba, u32*? rec_len, u8*? kind, i64*? remote, u32*? sorted_lba, u32*? sorted_slot, u32 steps, u8*? meta, u8* status, "
+                          "i64* dict, u64* padding, stream",
+    "hmse_scrub_attribute": "int: u64 n, u8*? status, i64*? dict, u8*? ok, u8*? got_sha, u8*? want_sha, u32 check_digest, u32 max_depth_log2, "
+                            "u64 n_chunks, i64*? chunk_slot, u64* cuts, u8* status_out, i64* root, i64* chunk_root, u64* root_records, u64* root_chunks, "
+                            "u64* root_bytes, u64* ranges, u64* counts, void* ws, size_t ws_bytes, stream",
+    "hmse_find_scan": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u32* mult, u8* pat, u32[] pat_off, u32 n_pat, u32 flags, "
+                      "u64* hits, u64 hits_cap, u64* n_hits, u64* counts, u32* status, stream",
+    "hmse_find_seams": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, u8* pat, u32[] pat_off, u32 n_pat, "
+                       "u32 flags, u64* hits, u64 hits_cap, u64* n_hits, u64* counts, u32* status, stream",
+    "hmse_find_place": "int: u64*? hits, u64 n_hits, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, u64* chunk_out, "
+                       "u64* out, u64 out_cap, u32* status, stream",
+    "hmse_findset_scan": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u32* mult, hmse_findset* set, u32 flags, "
+                         "u64* hits, u64 hits_cap, u64* n_hits, u64*? counts, u32* status, stream",
+    "hmse_findset_seams": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, hmse_findset* set, u32 flags, "
+                          "u64* hits, u64 hits_cap, u64* n_hits, u64*? counts, u32* status, stream",
+    "hmse_findset_place": "int: u64*? hits, u64 n_hits, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, u64* chunk_out, "
+                          "u64* out, u64 out_cap, u32* status, stream",
+    "hmse_sync_match": "int: u8*? a, u64 a_bytes, u64*? a_off, u32*? a_len, u64 n, u8*? b, u64 b_bytes, u64*? b_off, u32*? b_len, u64 n_b, i64*? cand, "
+                       "u8*? same, u32* status, stream",
+    "hmse_lines_extent": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, u64*? pos, u64 n, u32 delim, "
+                         "u32 before, u32 after, u32 reach, u64*? start, u64*? end, u8*? flags, u32* status, stream",
+    "hmse_lines_gather": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, u64*? start, u64*? end, "
+                         "u64* out_off, u64 n, u8* out, u64 out_cap, u32* status, stream",
+    "hmse_regex_scan": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u32* mult, hmse_regex* rx, "
+                       "u64* hits, u64 hits_cap, u64* n_hits, u64* count, u32* status, stream",
+    "hmse_regex_seams": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, hmse_regex* rx, "
+                        "u64* hits, u64 hits_cap, u64* n_hits, u64* count, u32* status, stream",
+    "hmse_approx_scan": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u32* mult, u8* pat, u32[] pat_off, u8[] k, u32 n_pat, u32 flags, "
+                        "u64* hits, u64 hits_cap, u64* n_hits, u64* counts, u32* status, stream",
+    "hmse_approx_seams": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, u8* pat, u32[] pat_off, u8[] k, "
+                         "u32 n_pat, u32 flags, u64* hits, u64 hits_cap, u64* n_hits, u64* counts, u32* status, stream",
+    "hmse_approx_spans": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, u8* pat, u32[] pat_off, u32 n_pat, "
+                         "u32 flags, u64*? hits, u64 n, u64* start, u32* status, stream",
+    "hmse_crc32": "int: u8*? data, u64 n, u64* cuts, u64 n_chunks, u32*? crc_out, u32* status, stream",
+    "hmse_crc32_combine": "int: u32*? crc, u64*? len, u64 n, u32* out, u32* status, stream",
+    "hmse_gzip_members": "int: u8*? src0, u64 src0_bytes, u8*? src1, u64 src1_bytes, u64* src_off, u64* stream_len, u8* src_sel, u32* crc, u64* raw_off, "
+                         "u64 n_rec, u64* slot, u64 n_chunks, u64* member_off, u32 flags, u8*? dst, u64 dst_bytes, u32* status, stream",
+    "hmse_profile_enable": "void: int on",
+    "hmse_profile_read": "int: int stage, f64[] total_ms, u64[] launches, int reset",
+    "hmse_profile_counter": "int: int slot, u64[] value, int reset",
+}
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
+
+_ELEM = {"u8": C.c_uint8, "u32": C.c_uint32, "i32": C.c_int32, "u64": C.c_uint64, "i64": C.c_int64, "f64": C.c_double}
+_SCALAR = {"u32": C.c_uint32, "u64": C.c_uint64, "size_t": C.c_size_t, "int": C.c_int}
+_STRUCT = {"hmse_cfg": HmseCfg, "hmse_stream": HmseStream, "hmse_gl4": HmseGl4, "hmse_findset": HmseFindset, "hmse_regex": HmseRegex}
+_RETURN = {"int": C.c_int, "void": None, "u64": C.c_uint64, "size_t": C.c_size_t, "str": C.c_char_p}
+DEVICE, HOST, STRUCT, SCALAR, STREAM = range(5)
+
+
+class Param(NamedTuple):
+    name: str
+    kind: int          # DEVICE, HOST, STRUCT, SCALAR or STREAM
+    ctype: type
+    width: int         # DEVICE: the element size a tensor must have; 0: opaque bytes
+    null_if_empty: bool
+
+
+def _param(text: str) -> Param:
+    if text == "stream":
+        return Param("stream", STREAM, C.c_void_p, 0, False)
+    ty, name = text.split()
+    if ty in _SCALAR:
+        return Param(name, SCALAR, _SCALAR[ty], 0, False)
+    if ty.endswith("[]"):
+        return Param(name, HOST, C.POINTER(_ELEM[ty[:-2]]), 0, False)
+    base = ty.rstrip("?")[:-1]
+    if base in _STRUCT:
+        return Param(name, STRUCT, C.POINTER(_STRUCT[base]), 0, False)
+    return Param(name, DEVICE, C.c_void_p, 0 if base == "void" else C.sizeof(_ELEM[base]), ty.endswith("?"))
+
+
+def _parse(sig: str):
+    ret, _, params = sig.partition(":")
+    return _RETURN[ret], tuple(_param(p.strip()) for p in params.split(",") if p.strip())
+
+
+PARSED = {name: _parse(sig) for name, sig in SIGNATURES.items()}      # name -> (restype, parameters)
+
 _hip = None
 _corpus = None
-
-_VP, _U64, _U32, _SZ = C.c_void_p, C.c_uint64, C.c_uint32, C.c_size_t
 
 
 def hip_lib():
@@ -85,138 +238,9 @@ def hip_lib():
         # two runtimes and every launch fails with a HIP error.
         import torch  # noqa: F401
         L = C.CDLL(HIP_LIB_PATH)
-        cfgp, strp = C.POINTER(HmseCfg), C.POINTER(HmseStream)
-        L.hmse_cfg_default.argtypes = [cfgp]
-        L.hmse_cfg_validate.argtypes = [cfgp]
-        L.hmse_cfg_validate.restype = C.c_int
-        L.hmse_abi_version.restype = C.c_int
-        L.hmse_strerror.restype = C.c_char_p
-        L.hmse_strerror.argtypes = [C.c_int]
-        L.hmse_gear_table.argtypes = [_VP]
-        L.hmse_workspace_bytes.restype = _SZ
-        L.hmse_workspace_bytes.argtypes = [C.c_int, _U64, cfgp]
-        L.hmse_l2_cdc.restype = C.c_int
-        L.hmse_l2_cdc.argtypes = [_VP, _U64, _VP, _U32, cfgp, _VP, _U64, _VP, _VP, _VP, _SZ, _VP]
-        L.hmse_l3_sha256.restype = C.c_int
-        L.hmse_l3_sha256.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _SZ, _VP]
-        L.hmse_l3_dedup.restype = C.c_int
-        L.hmse_l3_dedup.argtypes = [_VP, _U64, _VP, _VP, _VP, _SZ, _VP]
-        L.hmse_l3_index_slots.restype = _U64
-        L.hmse_l3_index_slots.argtypes = [_U64]
-        L.hmse_l3_index_update.restype = C.c_int
-        L.hmse_l3_index_update.argtypes = [_VP, _U64, _U64, _VP, _VP, _VP, _U64, _VP]
-        L.hmse_l4_lsh_slots.restype = _U64
-        L.hmse_l4_lsh_slots.argtypes = [_U64]
-        L.hmse_l4_lsh_update.restype = C.c_int
-        L.hmse_l4_lsh_update.argtypes = [_VP, _U64, _U64, cfgp, _VP, _VP, _VP, _U64, _U32, _VP]
-        L.hmse_l4_minhash.restype = C.c_int
-        L.hmse_l4_minhash.argtypes = [_VP, _U64, _VP, _VP, _U64, cfgp, _VP, _VP, _SZ, _VP]
-        L.hmse_l4_lsh.restype = C.c_int
-        L.hmse_l4_lsh.argtypes = [_VP, _U64, cfgp, _VP, _VP, _VP, _SZ, _VP]
-        L.hmse_l1_deflate.restype = C.c_int
-        L.hmse_l1_deflate.argtypes = [_VP, _U64, _VP, _VP, _VP, _U64, cfgp, _VP, _U64, _VP, _VP, _VP, _VP, _SZ, _VP]
-        L.hmse_l1_deflate_ex.restype = C.c_int
-        L.hmse_l1_deflate_ex.argtypes = [_VP, _U64, _VP, _VP, _VP, _U64, cfgp, _U32, _VP, _U64, _VP, _VP, _VP, _VP, _SZ, _VP]
-        L.hmse_l1_deflate_record_bytes.restype = _U64
-        L.hmse_l1_deflate_record_bytes.argtypes = [_U32]
-        L.hmse_l1_deflate_record_bytes_dict.restype = _U64
-        L.hmse_l1_deflate_record_bytes_dict.argtypes = [_U32]
-        L.hmse_l1_inflate_mode.restype = C.c_int
-        L.hmse_l1_inflate_mode.argtypes = [C.c_int]
-        L.hmse_l1_inflate.restype = C.c_int
-        L.hmse_l1_inflate.argtypes = [_VP, _U64, _VP, _VP, _VP, _VP, _U64, _VP, _VP, _U64, _VP, _VP, _VP, _SZ, _VP]
-        L.hmse_read_assemble.restype = C.c_int
-        L.hmse_read_assemble.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _VP, _U64, _VP, _VP]
-        L.hmse_stream_batch_workspace_bytes.restype = _U64
-        L.hmse_stream_batch_workspace_bytes.argtypes = [_U64, cfgp]
-        L.hmse_stream_workspace_init.restype = C.c_int
-        L.hmse_stream_workspace_init.argtypes = [_VP, _SZ, _U64, cfgp, _VP]
-        L.hmse_stream_batch.restype = C.c_int
-        L.hmse_stream_batch.argtypes = [_VP, _U64, _U64, _VP, _U32, cfgp, strp, _VP, _SZ, _VP]
-        L.hmse_stream_row_bytes.restype = _U64
-        L.hmse_stream_row_bytes.argtypes = [_U64, cfgp]
-        L.hmse_stream_piece_hash.restype = C.c_int
-        L.hmse_stream_piece_hash.argtypes = [_VP, _U64, _U64, _U64, _VP, _U32, cfgp, strp, _VP, _VP, _SZ, _VP]
-        L.hmse_stream_piece_encode.restype = C.c_int
-        L.hmse_stream_piece_encode.argtypes = [_VP, _U64, _U64, _U64, cfgp, strp, _VP, _VP, _SZ, _VP]
-        L.hmse_stream_sig_cap.restype = _U64
-        L.hmse_stream_sig_cap.argtypes = [_U64, cfgp]
-        L.hmse_stream_sig_row_bytes.restype = _U64
-        L.hmse_stream_sig_row_bytes.argtypes = [_U64, cfgp]
-        L.hmse_stream_piece_sign.restype = C.c_int
-        L.hmse_stream_piece_sign.argtypes = [_VP, _U64, _U64, _U64, cfgp, strp, _VP, _VP, _VP, _SZ, _VP]
-        L.hmse_stream_piece_bases.restype = C.c_int
-        L.hmse_stream_piece_bases.argtypes = [_U64, cfgp, strp, _VP, C.POINTER(HmseGl4), _VP, _SZ, _VP]
-        L.hmse_stream_piece_encode_g.restype = C.c_int
-        L.hmse_stream_piece_encode_g.argtypes = [_VP, _U64, _U64, _U64, cfgp, strp, _VP, _VP, _SZ, _VP]
-        L.hmse_manifest_pack.restype = C.c_int
-        L.hmse_manifest_pack.argtypes = [_VP, _VP, _VP, _VP, _VP, _U64, _VP, _VP, _VP, _U64, _VP, _U64, _U32, _VP, _U32, _VP, _U32, _VP,
-                                         _VP, _U64, _VP, _VP, _VP, _U64, _VP, _VP, _SZ, _VP]
-        L.hmse_manifest_pack_ex.restype = C.c_int
-        L.hmse_manifest_pack_ex.argtypes = [_VP, _VP, _VP, _VP, _VP, _U64, _VP, _VP, _VP, _U64, _VP, _U64, _U32, _VP, _U32, _U32, _VP, _U32, _VP,
-                                            _VP, _U64, _VP, _VP, _VP, _U64, _VP, _VP, _SZ, _VP]
-        L.hmse_gc_plan.restype = C.c_int
-        L.hmse_gc_plan.argtypes = [_VP, _U64, _VP, _U64, _VP, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]
-        L.hmse_record_gather.restype = C.c_int
-        L.hmse_record_gather.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _VP, _U64, _VP, _U64, _VP, _VP]
-        L.hmse_band_tables_bound.restype = _U64
-        L.hmse_band_tables_bound.argtypes = [_U64, _U32, _U32, _U32]
-        L.hmse_band_tables_workspace_bytes.restype = _SZ
-        L.hmse_band_tables_workspace_bytes.argtypes = [_U64]
-        L.hmse_band_tables_write.restype = C.c_int
-        L.hmse_band_tables_write.argtypes = [_VP, _U64, _U32, _U32, _VP, _U32, _VP, _U64, _VP, _VP, _VP, _SZ, _VP]
-        L.hmse_l4_index_build.restype = C.c_int
-        L.hmse_l4_index_build.argtypes = [_VP, _U64, _U32, _VP, _VP, _VP, _VP, _SZ, _VP]
-        L.hmse_l4_query.restype = C.c_int
-        L.hmse_l4_query.argtypes = [_VP, _VP, _U64, _VP, _U64, _VP, _VP, cfgp, _U32, _U32, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]
-        L.hmse_scrub_records.restype = C.c_int
-        L.hmse_scrub_records.argtypes = [_VP, _U64, _U64, _U32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _U32, _VP, _VP, _VP, _VP, _VP]
-        L.hmse_scrub_attribute.restype = C.c_int
-        L.hmse_scrub_attribute.argtypes = [_U64, _VP, _VP, _VP, _VP, _VP, _U32, _U32, _U64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
-                                           _VP, _SZ, _VP]
-        u32p = C.POINTER(C.c_uint32)      # the patterns' bounds: a HOST array, read during the call
-        L.hmse_find_scan.restype = C.c_int
-        L.hmse_find_scan.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, u32p, _U32, _U32, _VP, _U64, _VP, _VP, _VP, _VP]
-        L.hmse_find_seams.restype = C.c_int
-        L.hmse_find_seams.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _U64, _VP, u32p, _U32, _U32, _VP, _U64, _VP, _VP, _VP, _VP]
-        L.hmse_find_place.restype = C.c_int
-        L.hmse_find_place.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _U64, _VP, _VP, _U64, _VP, _VP]
-        fsp = C.POINTER(HmseFindset)      # the set's header: a HOST struct, read during the call
-        L.hmse_findset_scan.restype = C.c_int
-        L.hmse_findset_scan.argtypes = [_VP, _U64, _VP, _U64, _VP, fsp, _U32, _VP, _U64, _VP, _VP, _VP, _VP]
-        L.hmse_findset_seams.restype = C.c_int
-        L.hmse_findset_seams.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _U64, fsp, _U32, _VP, _U64, _VP, _VP, _VP, _VP]
-        L.hmse_findset_place.restype = C.c_int
-        L.hmse_findset_place.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _U64, _VP, _VP, _U64, _VP, _VP]
-        rxp = C.POINTER(HmseRegex)        # the automaton's header: a HOST struct, read during the call
-        L.hmse_regex_scan.restype = C.c_int
-        L.hmse_regex_scan.argtypes = [_VP, _U64, _VP, _U64, _VP, rxp, _VP, _U64, _VP, _VP, _VP, _VP]
-        L.hmse_regex_seams.restype = C.c_int
-        L.hmse_regex_seams.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _U64, rxp, _VP, _U64, _VP, _VP, _VP, _VP]
-        u8p = C.POINTER(C.c_uint8)        # the patterns' error bounds: a HOST array, read during the call
-        L.hmse_approx_scan.restype = C.c_int
-        L.hmse_approx_scan.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, u32p, u8p, _U32, _U32, _VP, _U64, _VP, _VP, _VP, _VP]
-        L.hmse_approx_seams.restype = C.c_int
-        L.hmse_approx_seams.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _U64, _VP, u32p, u8p, _U32, _U32, _VP, _U64, _VP, _VP, _VP, _VP]
-        L.hmse_approx_spans.restype = C.c_int
-        L.hmse_approx_spans.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _U64, _VP, u32p, _U32, _U32, _VP, _U64, _VP, _VP, _VP]
-        L.hmse_crc32.restype = C.c_int
-        L.hmse_crc32.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _VP]
-        L.hmse_crc32_combine.restype = C.c_int
-        L.hmse_crc32_combine.argtypes = [_VP, _VP, _U64, _VP, _VP, _VP]
-        L.hmse_gzip_members.restype = C.c_int
-        L.hmse_gzip_members.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _VP, _VP, _VP, _U64, _VP, _U64, _VP, _U32, _VP, _U64, _VP, _VP]
-        L.hmse_sync_match.restype = C.c_int
-        L.hmse_sync_match.argtypes = [_VP, _U64, _VP, _VP, _U64, _VP, _U64, _VP, _VP, _U64, _VP, _VP, _VP, _VP]
-        L.hmse_lines_extent.restype = C.c_int
-        L.hmse_lines_extent.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _U64, _VP, _U64, _U32, _U32, _U32, _U32, _VP, _VP, _VP, _VP, _VP]
-        L.hmse_lines_gather.restype = C.c_int
-        L.hmse_lines_gather.argtypes = [_VP, _U64, _VP, _U64, _VP, _VP, _U64, _VP, _VP, _VP, _U64, _VP, _U64, _VP, _VP]
-        L.hmse_profile_enable.argtypes = [C.c_int]
-        L.hmse_profile_read.restype = C.c_int
-        L.hmse_profile_read.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
-        L.hmse_profile_counter.restype = C.c_int
-        L.hmse_profile_counter.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.c_int]
+        for name, (restype, params) in PARSED.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, [p.ctype for p in params]
         _hip = L
     return _hip
 
@@ -228,13 +252,6 @@ def corpus_lib():
             raise ImportError(f"{CORPUS_LIB_PATH} is missing: run __graft_entry__.build()")
         L = C.CDLL(CORPUS_LIB_PATH)
         L.hmse_corpus_generate.restype = C.c_int
-        L.hmse_corpus_generate.argtypes = [_VP, _U64, _U64, _U32, _U64, C.c_int, C.c_int]
+        L.hmse_corpus_generate.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int]
         _corpus = L
     return _corpus
-
-
-EXPORTED_SYMBOLS = (
-    "hmse_cfg_default", "hmse_cfg_validate", "hmse_abi_version", "hmse_strerror", "hmse_gear_table",
-    "hmse_workspace_bytes", "hmse_l2_cdc", "hmse_l3_sha256", "hmse_l3_dedup", "hmse_l3_index_slots", "hmse_l3_index_update",
-    "hmse_l4_lsh_slots", "hmse_l4_lsh_update", "hmse_l4_minhash",
-    "hmse_l4_lsh", "hmse_l1_deflate", "hmse_l1_deflate_ex", "hmse_l1_deflate_record_bytes", "hmse_l1_deflate_record_bytes_dict", "hmse_l1_inflate", "hmse_l1_inflate_mode", "hmse_read_assemble", "hmse_manifest_pack", "hmse_manifest_pack_ex", "hmse_stream_batch", "hmse_stream_batch_workspace_bytes", "hmse_stream_workspace_init", "hmse_stream_row_bytes", "hmse_stream_piece_hash", "hmse_stream_piece_encode", "hmse_stream_sig_cap", "hmse_stream_sig_row_bytes", "hmse_stream_piece_sign", "hmse_stream_piece_bases", "hmse_stream_piece_encode_g", "hmse_gc_plan", "hmse_record_gather", "hmse_band_tables_bound", "hmse_band_tables_workspace_bytes", "hmse_band_tables_write", "hmse_l4_index_build", "hmse_l4_query", "hmse_scrub_records", "hmse_scrub_attribute", "hmse_find_scan", "hmse_find_seams", "hmse_find_place", "hmse_findset_scan", "hmse_findset_seams", "hmse_findset_place", "hmse_sync_match", "hmse_lines_extent", "hmse_lines_gather", "hmse_regex_scan", "hmse_regex_seams", "hmse_approx_scan", "hmse_approx_seams", "hmse_approx_spans", "hmse_crc32", "hmse_crc32_combine", "hmse_gzip_members", "hmse_profile_enable", "hmse_profile_read", "hmse_profile_counter")

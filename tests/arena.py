@@ -10,8 +10,11 @@ on the CPU; tests/test_gpu_arguments_only.py on the GPU).
   empty(shape, dtype)              the same placement, 256-byte aligned (uint8: misalign= as in place), contents = the pattern
   check()                          every guard band still holds its pattern, else AssertionError naming the buffer and the first changed offset
   install(monkeypatch, ...)        hmse_amd.ops allocates its outputs, status words and workspaces here
+  record(monkeypatch, faked)       hmse_amd.ops runs without a GPU: the entry points `faked` record their arguments (RecordingLib)
 """
 from __future__ import annotations
+
+import ctypes as C
 
 import numpy as np
 import torch
@@ -129,3 +132,52 @@ class Arena:
         monkeypatch.setattr(ops, "_ws", ws)
         monkeypatch.setattr(ops, "_buf", buf)
         return self
+
+
+# ---- hmse_amd.ops without a GPU: the library's device entry points replaced by recorders ------------------------------------------------
+class RecordingLib:
+    """The real library with the entry points `faked` replaced by recorders of their arguments (they return HMSE_OK and touch nothing);
+    every other function (sizes, bounds, error strings) stays real.  calls: (name, the device pointers that are not NULL, all arguments)."""
+
+    def __init__(self, real, faked):
+        self._real, self._faked, self.calls = real, tuple(faked), []
+
+    def __getattr__(self, name):
+        fn = getattr(self._real, name)
+        if name not in self._faked:
+            return fn
+
+        def fake(*args):
+            assert len(args) == len(fn.argtypes), name
+            ptrs = [a for a, t in zip(args[:-1], fn.argtypes[:-1]) if t is C.c_void_p and a is not None]   # (the last argument is the stream)
+            assert all(isinstance(p, int) for p in ptrs), (name, ptrs)
+            ints = [a for a, t in zip(args, fn.argtypes) if t in (C.c_uint64, C.c_uint32)]
+            assert all(isinstance(v, int) and v >= 0 for v in ints), (name, ints)
+            self.calls.append((name, ptrs, args))
+            return 0
+        return fake
+
+
+class NoBareAllocation:
+    """`torch` as hmse_amd.ops sees it: an uninitialised or filled allocation past _ws / _buf is an error."""
+
+    def __init__(self, banned):
+        self._banned = tuple(banned)
+
+    def __getattr__(self, name):
+        if name in self._banned:
+            raise AssertionError(f"hmse_amd.ops calls torch.{name} directly: device buffers come from ops._ws / ops._buf")
+        return getattr(torch, name)
+
+
+def record(monkeypatch, faked, banned=()) -> RecordingLib:
+    """Let hmse_amd.ops run on CPU tensors: the entry points `faked` record their calls, the device check and the stream are stubbed, and
+    (with `banned`) ops sees a torch without those allocators.  -> the recording library."""
+    from hmse_amd import _lib, ops
+    lib = RecordingLib(_lib.hip_lib(), faked)
+    monkeypatch.setattr(_lib, "hip_lib", lambda: lib)
+    monkeypatch.setattr(ops, "_require_gpu", lambda t, name: None)
+    monkeypatch.setattr(ops, "_stream", lambda: 0)
+    if banned:
+        monkeypatch.setattr(ops, "torch", NoBareAllocation(banned))
+    return lib

@@ -28,6 +28,83 @@ def test_library_exports_every_declared_symbol():
     assert lib.hmse_abi_version() == 3
 
 
+def prototypes():
+    """include/hmse.h -> {name: (return type, [(C type without const, is a pointer, parameter name)])}."""
+    src = open(os.path.join(ROOT, "include", "hmse.h")).read()
+    src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+    out = {}
+    for m in re.finditer(r"^([A-Za-z_][\w \*]*?[\s\*])(hmse_[a-z0-9_]+)\s*\(([^;{}]*)\)\s*;", src, re.M):
+        ret, name, params = (" ".join(g.split()) for g in m.groups())
+        assert name not in out, name
+        decls = []
+        for p in ([] if params == "void" else params.split(",")):
+            ty, star, pname, array = re.fullmatch(r"\s*(?:const\s+)?(\w+)\s*(\*?)\s*(\w+)\s*(\[\d+\])?\s*", p).groups()
+            decls.append((ty, bool(star or array), pname))           # (`uint64_t table[256]` is a pointer)
+        out[name] = (ret, decls)
+    return out
+
+
+_C_ELEM = {"u8": "uint8_t", "u32": "uint32_t", "i32": "int32_t", "u64": "uint64_t", "i64": "int64_t", "f64": "double"}
+_C_SCALAR = {"u32": "uint32_t", "u64": "uint64_t", "size_t": "size_t", "int": "int"}
+_C_RETURN = {"int": "int", "void": "void", "u64": "uint64_t", "size_t": "size_t", "str": "const char*"}
+
+
+def kind_agrees(kind: str, c_type: str, is_pointer: bool) -> bool:
+    """A kind of _lib.SIGNATURES against the C declaration: pointer or not, the pointee's width and signedness, the scalar's type.  Opaque
+    bytes (`void*`) may stand for a `void*` or a `uint8_t*`."""
+    if kind == "stream":
+        return is_pointer and c_type == "void"
+    if kind in _C_SCALAR:
+        return not is_pointer and c_type == _C_SCALAR[kind]
+    if kind.endswith("[]"):
+        return is_pointer and c_type == _C_ELEM.get(kind[:-2])
+    base = kind.rstrip("?")
+    if not is_pointer or not base.endswith("*"):
+        return False
+    base = base[:-1]
+    if base == "void":
+        return c_type in ("void", "uint8_t")
+    return c_type == (base if base.startswith("hmse_") else _C_ELEM.get(base))
+
+
+def test_the_signature_table_is_the_header():
+    """Every prototype of include/hmse.h has its entry in _lib.SIGNATURES: the same parameters under the same names in the same order, each of a
+    kind that agrees with its C type, the same return type — and the table names nothing else.  What ctypes is told follows from the table."""
+    import ctypes as C
+    from hmse_amd import _lib
+    protos = prototypes()
+    assert len(protos) == 64 and set(protos) == set(_lib.SIGNATURES) and _lib.EXPORTED_SYMBOLS == tuple(_lib.SIGNATURES)
+    lib = _lib.hip_lib()
+    for name, (ret, decls) in protos.items():
+        t_ret, _, t_params = _lib.SIGNATURES[name].partition(":")
+        assert _C_RETURN[t_ret] == ret, (name, t_ret, ret)
+        entries = [p.split() for p in t_params.split(",") if p.strip()]
+        entries = [e if len(e) == 2 else [e[0], e[0]] for e in entries]                   # ("stream" is its own name)
+        assert [e[1] for e in entries] == [d[2] for d in decls], name
+        for (kind, pname), (c_type, is_pointer, _) in zip(entries, decls):
+            assert kind_agrees(kind, c_type, is_pointer), (name, pname, kind, c_type)
+        assert "stream" not in [e[0] for e in entries[:-1]], name                          # the stream comes last
+        fn, (restype, params) = getattr(lib, name), _lib.PARSED[name]
+        assert fn.restype is restype and list(fn.argtypes) == [p.ctype for p in params] and (restype is None) == (ret == "void"), name
+        for p, (kind, _), (c_type, _, _) in zip(params, entries, decls):
+            assert p.kind == (_lib.STREAM if kind == "stream" else _lib.SCALAR if kind in _C_SCALAR else _lib.HOST if kind.endswith("[]") else
+                              _lib.STRUCT if kind.startswith("hmse_") else _lib.DEVICE), (name, p)
+            if p.kind == _lib.DEVICE:
+                width = 0 if kind.startswith("void") else C.sizeof(getattr(C, "c_" + c_type[:-2]))     # uint64_t -> c_uint64
+                assert p.ctype is C.c_void_p and p.width == width and p.null_if_empty == kind.endswith("?"), (name, p)
+    assert [n for n, (r, _) in _lib.PARSED.items() if r is None] == ["hmse_cfg_default", "hmse_gear_table", "hmse_profile_enable"]
+
+
+def test_the_table_check_sees_one_changed_width():
+    """The comparison above fails for a table that is wrong in one width, one signedness, a scalar for a pointer or a host array's type."""
+    assert kind_agrees("u64*", "uint64_t", True) and kind_agrees("u64*?", "uint64_t", True) and kind_agrees("void*", "uint8_t", True)
+    assert kind_agrees("u32[]", "uint32_t", True) and kind_agrees("hmse_cfg*", "hmse_cfg", True) and kind_agrees("size_t", "size_t", False)
+    for kind, c_type, is_pointer in (("u32*", "uint64_t", True), ("u64*", "uint32_t", True), ("u64*", "int64_t", True), ("u32", "uint64_t", False),
+                                     ("u64", "size_t", False), ("u64", "uint64_t", True), ("u64*", "uint64_t", False), ("u8[]", "uint32_t", True),
+                                     ("void*", "uint32_t", True), ("hmse_cfg*", "hmse_stream", True), ("stream", "uint8_t", True), ("int", "uint32_t", False)):
+        assert not kind_agrees(kind, c_type, is_pointer), (kind, c_type)
+
+
 def test_library_exports_nothing_but_the_declared_abi():
     """exported == declared: no diagnostic hook or probe entry point ships in the product library."""
     import subprocess

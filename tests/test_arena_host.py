@@ -93,42 +93,11 @@ DEVICE_CALLS = ("hmse_l2_cdc", "hmse_l3_sha256", "hmse_l3_dedup", "hmse_l3_index
                 "hmse_stream_piece_sign", "hmse_stream_piece_bases", "hmse_stream_piece_encode_g")
 
 
-class RecordingLib:
-    """The real library with its device entry points replaced by recorders of their pointer arguments (they return HMSE_OK and touch nothing);
-    the host-side functions (sizes, bounds, error strings) stay real."""
-
-    def __init__(self, real):
-        self._real, self.calls = real, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._real, name)
-        if name not in DEVICE_CALLS:
-            return fn
-
-        def fake(*args):
-            assert len(args) == len(fn.argtypes), name
-            ptrs = [a for a, t in zip(args[:-1], fn.argtypes[:-1]) if t is C.c_void_p and a is not None]   # (the last argument is the stream)
-            assert all(isinstance(p, int) for p in ptrs), (name, ptrs)
-            self.calls.append((name, ptrs))
-            return 0
-        return fake
-
-
 @pytest.fixture()
 def recorded(monkeypatch):
-    from hmse_amd import _lib, ops
-    lib = RecordingLib(_lib.hip_lib())
-    monkeypatch.setattr(_lib, "hip_lib", lambda: lib)
-    monkeypatch.setattr(ops, "_require_gpu", lambda t, name: None)
-    monkeypatch.setattr(ops, "_stream", lambda: 0)
-
-    class NoBareAllocation:
-        """`torch` as hmse_amd.ops sees it: an uninitialised or zeroed allocation past _ws / _buf is an error."""
-        def __getattr__(self, name):
-            if name in ("empty", "zeros", "empty_like", "empty_strided"):
-                raise AssertionError(f"hmse_amd.ops calls torch.{name} directly: device buffers come from ops._ws / ops._buf")
-            return getattr(torch, name)
-    monkeypatch.setattr(ops, "torch", NoBareAllocation())
+    """The library with its device entry points replaced by recorders (tests/arena.py: RecordingLib), and `torch` as hmse_amd.ops sees it
+    without its uninitialised and zeroed allocators."""
+    lib = A.record(monkeypatch, DEVICE_CALLS, banned=("empty", "zeros", "empty_like", "empty_strided"))
     ar = A.Arena(CPU, "random", seed=5)
     ar.install(monkeypatch)
     return ar, lib
@@ -188,7 +157,7 @@ def test_every_pointer_ops_hands_to_the_library_comes_from_the_arena(recorded):
         fn()
         made = lib.calls[n_call:]
         assert made, name
-        ptrs = [p for _, ps in made for p in ps]
+        ptrs = [p for _, ps, _ in made for p in ps]
         outside = {p for p in ptrs if not ar.contains(p)}
         assert ptrs and len(outside) <= (computed[0] if computed else 0), (name, [hex(p) for p in outside])
         # at least as many requests as the wrapper has outputs, status words and workspaces of its own

@@ -104,41 +104,10 @@ def test_wrappers_refuse_host_tensors():
 
 
 # ---- the wrappers allocate through _ws / _buf only ---------------------------------------------------------------------------------------
-class RecordingLib:
-    """The real library with hmse_find_* replaced by recorders of their device-pointer arguments (they return HMSE_OK and touch nothing)."""
-
-    def __init__(self, real):
-        self._real, self.calls = real, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._real, name)
-        if name not in DEVICE_CALLS:
-            return fn
-
-        def fake(*args):
-            assert len(args) == len(fn.argtypes), name
-            ptrs = [a for a, t in zip(args[:-1], fn.argtypes[:-1]) if t is C.c_void_p and a is not None]   # (the last argument is the stream)
-            assert all(isinstance(p, int) for p in ptrs), (name, ptrs)
-            host = [a for a, t in zip(args, fn.argtypes) if t is not C.c_void_p and not isinstance(a, int)]
-            assert all(isinstance(h, C.Array) for h in host), (name, host)           # the patterns' bounds: a host array
-            self.calls.append((name, ptrs))
-            return 0
-        return fake
-
-
 def test_every_pointer_the_find_wrappers_hand_to_the_library_comes_from_the_arena(monkeypatch):
-    from hmse_amd import _lib, ops
-    lib = RecordingLib(_lib.hip_lib())
-    monkeypatch.setattr(_lib, "hip_lib", lambda: lib)
-    monkeypatch.setattr(ops, "_require_gpu", lambda t, name: None)
-    monkeypatch.setattr(ops, "_stream", lambda: 0)
-
-    class NoBareAllocation:
-        def __getattr__(self, name):
-            if name in ("empty", "zeros", "empty_like", "empty_strided", "full", "zeros_like"):
-                raise AssertionError(f"hmse_amd.ops calls torch.{name} directly: device buffers come from ops._ws / ops._buf")
-            return getattr(torch, name)
-    monkeypatch.setattr(ops, "torch", NoBareAllocation())
+    """hmse_find_* replaced by recorders of their arguments (tests/arena.py: RecordingLib)."""
+    from hmse_amd import ops
+    lib = A.record(monkeypatch, DEVICE_CALLS, banned=("empty", "zeros", "empty_like", "empty_strided", "full", "zeros_like"))
     ar = A.Arena(CPU, "random", seed=5).install(monkeypatch)
     p = ar.place
     i64 = lambda *v: p(np.array(v, np.int64))
@@ -157,7 +126,10 @@ def test_every_pointer_the_find_wrappers_hand_to_the_library_comes_from_the_aren
         fn()
         made = lib.calls[n_call:]
         assert made and all(c[0] in DEVICE_CALLS for c in made), name
-        ptrs = [q for _, ps in made for q in ps]
+        for call, _, args in made:
+            host = [a for a, t in zip(args, getattr(lib._real, call).argtypes) if t is not C.c_void_p and not isinstance(a, int)]
+            assert all(isinstance(h, C.Array) for h in host), (name, host)           # the patterns' bounds: a host array
+        ptrs = [q for _, ps, _ in made for q in ps]
         assert ptrs and all(ar.contains(q) for q in ptrs), (name, [hex(q) for q in ptrs if not ar.contains(q)])
         assert len(ar.requests) - n_req >= least, (name, len(ar.requests) - n_req)
         assert not [k for k, _ in ar.requests[n_req:] if k != "buf"]                # no workspace anywhere

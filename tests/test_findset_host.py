@@ -233,36 +233,11 @@ def test_wrappers_refuse_host_tensors_and_sets_that_do_not_match_their_header():
         ops.findset_place(torch.zeros(1, dtype=torch.int64), off, off, torch.tensor([0]), torch.tensor([0, 1]), 1)
 
 
-class RecordingLib:
-    """The real library with hmse_findset_* replaced by recorders of their arguments (they return HMSE_OK and touch nothing)."""
-    CALLS = ("hmse_findset_scan", "hmse_findset_seams", "hmse_findset_place")
-
-    def __init__(self, real):
-        self._real, self.calls = real, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._real, name)
-        if name not in self.CALLS:
-            return fn
-
-        def fake(*args):
-            assert len(args) == len(fn.argtypes), name
-            ptrs = [a for a, t in zip(args[:-1], fn.argtypes[:-1]) if t is C.c_void_p and a is not None]   # (the last argument is the stream)
-            assert all(isinstance(p, int) for p in ptrs), (name, ptrs)
-            ints = [a for a, t in zip(args, fn.argtypes) if t in (C.c_uint64, C.c_uint32)]
-            assert all(isinstance(v, int) and v >= 0 for v in ints), (name, ints)
-            self.calls.append((name, ptrs, args))
-            return 0
-        return fake
-
-
 def test_every_pointer_the_findset_wrappers_hand_to_the_library_comes_from_the_arena(monkeypatch):
+    """hmse_findset_* replaced by recorders of their arguments (tests/arena.py: RecordingLib)."""
     import arena as A
     from hmse_amd import _lib, find, ops
-    lib = RecordingLib(_lib.hip_lib())
-    monkeypatch.setattr(_lib, "hip_lib", lambda: lib)
-    monkeypatch.setattr(ops, "_require_gpu", lambda t, name: None)
-    monkeypatch.setattr(ops, "_stream", lambda: 0)
+    lib = A.record(monkeypatch, ("hmse_findset_scan", "hmse_findset_seams", "hmse_findset_place"))
     ar = A.Arena(torch.device("cpu"), "random", seed=5).install(monkeypatch)
     p = ar.place
     i64 = lambda *v: p(np.array(v, np.int64))
