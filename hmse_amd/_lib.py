@@ -14,6 +14,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # HMSE_LIB_VARIANT=<tag> (diagnostics / A-B experiments only): load csrc/libhmse_hip_<tag>.so instead — e.g. the stamps or diag build
 HIP_LIB_PATH = os.path.join(_CSRC, "libhmse_hip" + ("_" + os.environ["HMSE_LIB_VARIANT"] if os.environ.get("HMSE_LIB_VARIANT") else "") + ".so")
 CORPUS_LIB_PATH = os.path.join(_CSRC, "libhmse_corpus.so")
+GUNZIP_LIB_PATH = os.path.join(_CSRC, "libhmse_gunzip.so")     # include/hmse_gunzip.h: the gzip import, beside the C ABI of include/hmse.h
 
 
 class HmseCfg(C.Structure):
@@ -184,6 +185,14 @@ SIGNATURES = {
     "hmse_profile_counter": "int: int slot, u64[] value, int reset",
 }
 EXPORTED_SYMBOLS = tuple(SIGNATURES)
+# The entry points of include/hmse_gunzip.h (the gzip import, csrc/libhmse_gunzip.so) in the same notation; tests/test_gunzip_host.py holds this
+# table against that header.  hip_lib() hands them out beside the others, so ops._call is the one call path for both libraries.
+GUNZIP_SIGNATURES = {
+    "hmse_gzip_workspace_bytes": "size_t: u64 n",
+    "hmse_gzip_candidates": "int: u8*? data, u64 n, u64*? cand_off, u64 cap, u64* count, u32* status, void* ws, size_t ws_bytes, stream",
+    "hmse_gzip_measure": "int: u8*? data, u64 n, u64*? cand_off, u64 n_cand, u64*? stream_off, u64*? end, u64*? raw_len, u32*? crc, u32*? flags, "
+                         "u32* status, void* ws, size_t ws_bytes, stream",
+}
 
 _ELEM = {"u8": C.c_uint8, "u32": C.c_uint32, "i32": C.c_int32, "u64": C.c_uint64, "i64": C.c_int64, "f64": C.c_double}
 _SCALAR = {"u32": C.c_uint32, "u64": C.c_uint64, "size_t": C.c_size_t, "int": C.c_int}
@@ -219,7 +228,7 @@ def _parse(sig: str):
     return _RETURN[ret], tuple(_param(p.strip()) for p in params.split(",") if p.strip())
 
 
-PARSED = {name: _parse(sig) for name, sig in SIGNATURES.items()}      # name -> (restype, parameters)
+PARSED = {name: _parse(sig) for name, sig in {**SIGNATURES, **GUNZIP_SIGNATURES}.items()}      # name -> (restype, parameters)
 
 _hip = None
 _corpus = None
@@ -238,9 +247,14 @@ def hip_lib():
         # two runtimes and every launch fails with a HIP error.
         import torch  # noqa: F401
         L = C.CDLL(HIP_LIB_PATH)
+        if not os.path.exists(GUNZIP_LIB_PATH):
+            raise ImportError(f"{GUNZIP_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        L._gunzip = G = C.CDLL(GUNZIP_LIB_PATH)          # (it links against libhmse_hip.so, loaded above)
         for name, (restype, params) in PARSED.items():
-            fn = getattr(L, name)
+            fn = getattr(G if name in GUNZIP_SIGNATURES else L, name)
             fn.restype, fn.argtypes = restype, [p.ctype for p in params]
+            if name in GUNZIP_SIGNATURES:
+                setattr(L, name, fn)
         _hip = L
     return _hip
 

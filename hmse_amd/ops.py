@@ -1004,3 +1004,45 @@ def gzip_members(src0: torch.Tensor, src1: torch.Tensor | None, src_off: torch.T
         _refuse(status, ((1, -2, "hmse_gzip_members: a member lies outside its source or the destination, or its size is not header + stream + 8"),
                          (2, -2, "hmse_gzip_members: a BGZF member above 65536 bytes")))
     return out
+
+
+GZIP_VALID, GZIP_FAST, GZIP_WHY_SHIFT = 1, 2, 2
+GZIP_WHY = {1: "header", 2: "stream", 3: "length", 4: "bounds"}
+GZIP_MIN_MEMBER = 20
+
+
+def gzip_workspace_bytes(n: int) -> int:
+    return _host("hmse_gzip_workspace_bytes", int(n))
+
+
+def gzip_candidates(data: torch.Tensor, cap: int, out: torch.Tensor | None = None):
+    """hmse_gzip_candidates: every position of `data` (uint8) that could start a gzip member — 1f 8b 08, no reserved FLG bit, 20 bytes of
+    room —, ascending.  -> (int64[cap] (`out` if given), their number as a Python int — one host sync).  Only min(number, cap) entries
+    are written; the rest of the tensor is left as it was."""
+    _require_gpu(data, "data")
+    dev = data.device
+    if out is None:
+        out = _buf(cap, torch.int64, dev)
+    if out.numel() != cap or out.dtype != torch.int64:
+        raise HmseError(-1, "gzip_candidates: out is not int64[cap]")
+    meta = _buf(2, torch.int64, dev, fill=0)               # [count, status (its low word)]
+    ws = _ws(gzip_workspace_bytes(data.numel()), dev)
+    _call("hmse_gzip_candidates", data, data.numel(), out, cap, meta.data_ptr(), meta.data_ptr() + 8, ws, ws.numel())
+    return out, int(meta[0].item())
+
+
+def gzip_measure(data: torch.Tensor, cand_off: torch.Tensor):
+    """hmse_gzip_measure: one wavefront per candidate offset (int64[n]) parses the header and finds the member's end — from the BC
+    subfield of a BGZF block, else by walking the DEFLATE stream for its length.  -> (stream_off int64[n], end int64[n], raw_len int64[n],
+    crc int32[n] (u32 bits), flags int32[n]: GZIP_VALID | GZIP_FAST, or reason << GZIP_WHY_SHIFT (GZIP_WHY))."""
+    _require_gpu(data, "data")
+    dev = data.device
+    n = cand_off.numel()
+    if cand_off.dtype != torch.int64:
+        raise HmseError(-1, "gzip_measure: cand_off is not int64")
+    stream_off, end, raw_len = (_buf(n, torch.int64, dev) for _ in range(3))
+    crc, flags = (_buf(n, torch.int32, dev) for _ in range(2))
+    status = _status_word(dev)
+    ws = _ws(gzip_workspace_bytes(data.numel()), dev)
+    _call("hmse_gzip_measure", data, data.numel(), cand_off, n, stream_off, end, raw_len, crc, flags, status, ws, ws.numel())
+    return stream_off, end, raw_len, crc, flags

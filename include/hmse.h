@@ -1031,7 +1031,7 @@ int hmse_approx_spans(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* ra
  * HMSE_EINVAL before anything is cleared or launched: status NULL, unknown flag bits, a NULL pointer to a non-empty array, n_chunks
  * above 2^40 (hmse_crc32), n above 2^32 (hmse_crc32_combine), n_chunks >= 2^33 (hmse_gzip_members).  No workspace; stream-ordered,
  * allocate nothing, never sync.  Profile slots: hmse_crc32 reports in 0, hmse_gzip_members in 1.
- * Out of scope: byte ranges or single documents, containers, other codecs, one member for the whole corpus, importing gzip.
+ * Out of scope: byte ranges or single documents, containers, other codecs, one member for the whole corpus; importing gzip: hmse_gunzip.h.
  */
 #define HMSE_GZIP_BGZF 1u
 

@@ -1,4 +1,4 @@
-// hip_on_cpu.h — what the emulators (find_emu, findset_emu, lines_emu, regex_emu, approx_emu, export_emu, sync_emu) put under a HIP kernel to run it on the CPU:
+// hip_on_cpu.h — what the emulators (find_emu, findset_emu, lines_emu, regex_emu, approx_emu, export_emu, sync_emu, gunzip_emu) put under a HIP kernel to run it on the CPU:
 // one std::thread per lane, a std::barrier under __syncthreads and one per wavefront under __ballot (a loop that is not wave-uniform hangs
 // it), a plain prefix sum for block_exclusive_scan, and the launcher.  Include it after "hmse.h" and in front of hmse_amd/csrc/chunkmap.h,
 // blockops.h and the kernels cut out of a .hip file.
@@ -57,6 +57,35 @@ static inline unsigned long long __ballot(int p) {
   g_wave[w]->arrive_and_wait();
   return v;
 }
+// The wave-level reads of the one-stream-per-wavefront decoders (hmse_amd/csrc/inflate_core.h, gunzip.hip; launch_waves only): every lane
+// publishes its value, the wavefront meets, every lane reads lane j's.  uni32 / uni64 (common.h: readfirstlane) are the same read of
+// lane 0, so a value that is NOT uniform — or a loop that is not — shows here as a wrong result or a hang instead of passing unnoticed.
+static uint32_t g_lanes[16][64];
+static inline uint32_t emu_readlane(uint32_t v, uint32_t j) {
+  const uint32_t w = threadIdx.x >> 6;
+  g_lanes[w][lane_id()] = v;
+  g_wave[w]->arrive_and_wait();
+  const uint32_t r = g_lanes[w][j & 63u];
+  g_wave[w]->arrive_and_wait();
+  return r;
+}
+#define __builtin_amdgcn_readlane(v, j) ((int)emu_readlane((uint32_t)(v), (uint32_t)(j)))
+static inline uint32_t uni32(uint32_t v) { return emu_readlane(v, 0); }
+static inline uint64_t uni64(uint64_t v) { return ((uint64_t)uni32((uint32_t)(v >> 32)) << 32) | uni32((uint32_t)v); }
+static inline uint64_t lanemask_lt() { return (1ull << lane_id()) - 1ull; }
+static inline void emu_wave_barrier() { g_wave[threadIdx.x >> 6]->arrive_and_wait(); }
+#define __builtin_amdgcn_wave_barrier emu_wave_barrier
+#define __builtin_amdgcn_fence(...) __atomic_thread_fence(__ATOMIC_SEQ_CST)
+#ifndef __clang__
+static inline uint32_t emu_bitreverse32(uint32_t x) {
+  x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
+  x = ((x >> 2) & 0x33333333u) | ((x & 0x33333333u) << 2);
+  x = ((x >> 4) & 0x0F0F0F0Fu) | ((x & 0x0F0F0F0Fu) << 4);
+  return __builtin_bswap32(x);
+}
+#define __builtin_bitreverse32 emu_bitreverse32
+#endif
+static inline uint32_t atomicAdd(uint32_t* p, uint32_t v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
 // grid workgroups of NT threads, one after the other.  launch_block: for kernels that meet at __syncthreads (a thread that returns leaves
 // the barrier: arrive_and_drop).  launch_waves: for kernels whose wavefronts meet only at __ballot and return as a whole.
 template <int NT> static void launch_block(uint32_t grid, const std::function<void()>& f) {
