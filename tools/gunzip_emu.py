@@ -4,7 +4,8 @@ Cuts the kernels out of gunzip.hip (everything between its geometry constants an
 the symbol decode come with hmse_amd/csrc/inflate_core.h as they are, the block-sum scan with blockops.h), compiles them with
 tools/gunzip_emu.cpp (g++ -std=c++20: one std::thread per lane, std::barrier under __syncthreads, __ballot, readlane and readfirstlane)
 and runs the candidate passes on planted buffers and the measure kernel on known answers that this script takes from zlib
-(tests/gunzip_ref.py): small members of every block type and header, BGZF blocks, damaged ones, candidates inside other members.
+(tests/gunzip_ref.py): small members of every block type and header, BGZF blocks, damaged ones, candidates inside other members, and
+the catalogue of tests/deflate_vectors.py.
 --sanitize builds that program with -fsanitize=address,undefined (host code only).  Exit status 0 = all equal."""
 import os
 import random
@@ -15,6 +16,7 @@ import zlib
 from emu_common import ROOT, run
 
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import deflate_vectors  # noqa: E402
 import gunzip_ref as ref  # noqa: E402
 
 
@@ -61,6 +63,9 @@ def cases():
         at = rnd.randrange(len(b))
         b[at] = rnd.randrange(256) if rnd.random() < 0.5 else b[at] ^ (1 << rnd.randrange(8))
         out.append((bytes(b), sorted(set([0] + ref.candidates(bytes(b))))))
+    # hand-built streams zlib's encoder never writes (tests/deflate_vectors.py), each wrapped as a member: the dynamic-header rules,
+    # one-code and empty distance sets, 15-bit codes, the longest header, and what zlib refuses beside them
+    out.append(deflate_vectors.emu_case())
     return out
 
 

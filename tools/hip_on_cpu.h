@@ -1,4 +1,4 @@
-// hip_on_cpu.h — what the emulators (find_emu, findset_emu, lines_emu, regex_emu, approx_emu, export_emu, sync_emu, gunzip_emu) put under a HIP kernel to run it on the CPU:
+// hip_on_cpu.h — what the emulators (find_emu, findset_emu, lines_emu, regex_emu, approx_emu, export_emu, sync_emu, gunzip_emu, inflate_emu) put under a HIP kernel to run it on the CPU:
 // one std::thread per lane, a std::barrier under __syncthreads and one per wavefront under __ballot (a loop that is not wave-uniform hangs
 // it), a plain prefix sum for block_exclusive_scan, and the launcher.  Include it after "hmse.h" and in front of hmse_amd/csrc/chunkmap.h,
 // blockops.h and the kernels cut out of a .hip file.
@@ -86,6 +86,15 @@ static inline uint32_t emu_bitreverse32(uint32_t x) {
 #define __builtin_bitreverse32 emu_bitreverse32
 #endif
 static inline uint32_t atomicAdd(uint32_t* p, uint32_t v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
+// The scoped atomics and the sleep of the decoders' hand-off between streams (hmse_amd/csrc/l1_inflate.hip: a DELTA record polls its base's
+// flag): sequentially consistent here, and a poll gives the core away.  (Its s_waitcnt and register-pinning asm statements and its
+// ext_vector_type typedef are replaced where tools/inflate_emu.py cuts the kernels out.)
+#define __HIP_MEMORY_SCOPE_AGENT 0
+#define __HIP_MEMORY_SCOPE_SYSTEM 0
+#define __hip_atomic_load(p, order, scope) __atomic_load_n((p), __ATOMIC_SEQ_CST)
+#define __hip_atomic_store(p, v, order, scope) __atomic_store_n((p), (v), __ATOMIC_SEQ_CST)
+static inline void emu_sleep(int) { std::this_thread::yield(); }
+#define __builtin_amdgcn_s_sleep emu_sleep
 // grid workgroups of NT threads, one after the other.  launch_block: for kernels that meet at __syncthreads (a thread that returns leaves
 // the barrier: arrive_and_drop).  launch_waves: for kernels whose wavefronts meet only at __ballot and return as a whole.
 template <int NT> static void launch_block(uint32_t grid, const std::function<void()>& f) {
