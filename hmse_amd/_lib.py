@@ -15,6 +15,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 HIP_LIB_PATH = os.path.join(_CSRC, "libhmse_hip" + ("_" + os.environ["HMSE_LIB_VARIANT"] if os.environ.get("HMSE_LIB_VARIANT") else "") + ".so")
 CORPUS_LIB_PATH = os.path.join(_CSRC, "libhmse_corpus.so")
 GUNZIP_LIB_PATH = os.path.join(_CSRC, "libhmse_gunzip.so")     # include/hmse_gunzip.h: the gzip import, beside the C ABI of include/hmse.h
+REGEXA_LIB_PATH = os.path.join(_CSRC, "libhmse_regexa.so")     # include/hmse_regexa.h: the regex search with assertions, likewise
 
 
 class HmseCfg(C.Structure):
@@ -58,6 +59,13 @@ class HmseRegex(C.Structure):
 
     _fields_ = [("struct_size", C.c_uint32), ("n_states", C.c_uint32), ("n_classes", C.c_uint32), ("reach", C.c_uint32),
                 ("table", C.c_void_p), ("classmap", C.c_void_p)]
+
+
+class HmseRegexa(C.Structure):
+    """Mirror of `hmse_regexa` (include/hmse_regexa.h): a regular expression compiled with assertions — its header and its device arrays."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("n_states", C.c_uint32), ("n_classes", C.c_uint32), ("reach", C.c_uint32),
+                ("start", C.c_uint32 * 4), ("table", C.c_void_p), ("classmap", C.c_void_p)]
 
 
 def build(force: bool = False) -> None:
@@ -193,10 +201,19 @@ GUNZIP_SIGNATURES = {
     "hmse_gzip_measure": "int: u8*? data, u64 n, u64*? cand_off, u64 n_cand, u64*? stream_off, u64*? end, u64*? raw_len, u32*? crc, u32*? flags, "
                          "u32* status, void* ws, size_t ws_bytes, stream",
 }
+# The entry points of include/hmse_regexa.h (the regex search with assertions, csrc/libhmse_regexa.so); tests/test_regexa_host.py holds this
+# table against that header.  Parsed into a table of its own (PARSED_REGEXA); ops._call looks a name up in PARSED, then there.
+REGEXA_SIGNATURES = {
+    "hmse_regexa_scan": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u32* mult, hmse_regexa* rx, "
+                        "u64* hits, u64 hits_cap, u64* n_hits, u64* count, u32* status, stream",
+    "hmse_regexa_seams": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, hmse_regexa* rx, "
+                         "u64* hits, u64 hits_cap, u64* n_hits, u64* count, u32* status, stream",
+}
 
 _ELEM = {"u8": C.c_uint8, "u32": C.c_uint32, "i32": C.c_int32, "u64": C.c_uint64, "i64": C.c_int64, "f64": C.c_double}
 _SCALAR = {"u32": C.c_uint32, "u64": C.c_uint64, "size_t": C.c_size_t, "int": C.c_int}
-_STRUCT = {"hmse_cfg": HmseCfg, "hmse_stream": HmseStream, "hmse_gl4": HmseGl4, "hmse_findset": HmseFindset, "hmse_regex": HmseRegex}
+_STRUCT = {"hmse_cfg": HmseCfg, "hmse_stream": HmseStream, "hmse_gl4": HmseGl4, "hmse_findset": HmseFindset, "hmse_regex": HmseRegex,
+           "hmse_regexa": HmseRegexa}
 _RETURN = {"int": C.c_int, "void": None, "u64": C.c_uint64, "size_t": C.c_size_t, "str": C.c_char_p}
 DEVICE, HOST, STRUCT, SCALAR, STREAM = range(5)
 
@@ -229,6 +246,7 @@ def _parse(sig: str):
 
 
 PARSED = {name: _parse(sig) for name, sig in {**SIGNATURES, **GUNZIP_SIGNATURES}.items()}      # name -> (restype, parameters)
+PARSED_REGEXA = {name: _parse(sig) for name, sig in REGEXA_SIGNATURES.items()}
 
 _hip = None
 _corpus = None
@@ -255,6 +273,13 @@ def hip_lib():
             fn.restype, fn.argtypes = restype, [p.ctype for p in params]
             if name in GUNZIP_SIGNATURES:
                 setattr(L, name, fn)
+        if not os.path.exists(REGEXA_LIB_PATH):
+            raise ImportError(f"{REGEXA_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        L._regexa = A = C.CDLL(REGEXA_LIB_PATH)          # (it links against libhmse_hip.so as well)
+        for name, (restype, params) in PARSED_REGEXA.items():
+            fn = getattr(A, name)
+            fn.restype, fn.argtypes = restype, [p.ctype for p in params]
+            setattr(L, name, fn)
         _hip = L
     return _hip
 

@@ -1,8 +1,8 @@
 // chunkmap.h — the three tables through which every search kernel reads a store, once: raw_off (n_rec + 1 bounds of the decoded records
 // in raw), cuts (n_chunks + 1 bounds of the chunks in the corpus) and slot (the record of every chunk).  Corpus byte q of chunk k is
-// raw[raw_off[slot[k]] + q - cuts[k]].  find.hip, findset.hip, lines.hip, regex.hip and approx.hip include this after common.h; the CPU emulators
+// raw[raw_off[slot[k]] + q - cuts[k]].  find.hip, findset.hip, lines.hip, regex.hip, regexa.hip and approx.hip include this after common.h; the CPU emulators
 // (tools/*_emu.cpp) include it after tools/hip_on_cpu.h, so the device part uses only what both provide and the file includes nothing.
-// Everything here is a template or __forceinline__: five translation units include it and link into one library.
+// Everything here is a template or __forceinline__: several translation units include it (five of them link into one library).
 #pragma once
 
 // ---- bytes --------------------------------------------------------------------------------------------------------------------

@@ -31,7 +31,9 @@ Regular expressions: a regex.Regex (compiled on the host into a bounded DFA, hms
 answered by StoreFinder.count_regex / find_regex / grep_regex with the same three steps — scan of the unique records, place, seams
 (hmse_amd/csrc/regex.hip; include/hmse.h hmse_regex_*) — split by START: a start whose record still holds `reach` bytes is a scan
 start, the last reach - 1 starts of every chunk are seam starts.  The result is a RegexFound: a Found with the lengths of the matches.
-Out of scope: anchors and \\b, captures, lazy matching, matches over 256 bytes, Unicode classes, several regexes fused into one
+A Regex compiled with assertions=True (^ $ \\A \\Z \\b \\B) goes through hmse_amd/csrc/regexa.hip (include/hmse_regexa.h), whose scan
+leaves a record's first start and its last `reach` ones to the seams as well.  Out of scope: captures, lazy matching, matches over
+256 bytes, Unicode classes, look-around, assertions in a PatternSet or in the approximate search, several regexes fused into one
 automaton, multi-byte line delimiters, routing find / find_set through the DFA.
 
 Approximate search: StoreFinder.count_approx / find_approx / grep_approx answer "where does something within k edits of this string
@@ -251,8 +253,9 @@ class StoreFinder:
                       lambda *a: ops.findset_place(*a), ops.FINDSET_ID_BITS)
 
     def _q_regex(self, r: Regex) -> _Query:
-        return _Query(lambda cap: ops.regex_scan(self.raw, self.raw_off, self.mult, r.rx, hits_cap=cap),
-                      lambda cap: ops.regex_seams(self.raw, self.raw_off, self.cuts, self.slot, r.rx, hits_cap=cap),
+        scan, seams = ("regexa_scan", "regexa_seams") if r.asserting else ("regex_scan", "regex_seams")     # (an asserting Regex: regexa.hip)
+        return _Query(lambda cap: getattr(ops, scan)(self.raw, self.raw_off, self.mult, r.rx, hits_cap=cap),
+                      lambda cap: getattr(ops, seams)(self.raw, self.raw_off, self.cuts, self.slot, r.rx, hits_cap=cap),
                       lambda *a: ops.find_place(*a), 8)                          # (a regex hit word is find's: the length - 1 in the low byte)
 
     def _count(self, q: _Query):

@@ -82,7 +82,7 @@ def _call(name: str, *args) -> None:
     address (NULL when it is empty and the table says `?`); None is NULL; an int is a raw address.  An IngestConfig, a StreamArrays (whatever holds
     its struct as `.c`) or a mirror struct goes by reference; a host array as it is; a scalar as int().  A non-zero return raises HmseError (an _ex entry point
     under the name of the one it extends)."""
-    params = _lib.PARSED[name][1]
+    params = (_lib.PARSED.get(name) or _lib.PARSED_REGEXA[name])[1]
     if len(args) != len(params) - 1:
         raise TypeError(f"{name} takes {len(params) - 1} arguments and the stream, got {len(args)}")
     out = list(args)
@@ -899,6 +899,41 @@ def regex_seams(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, sl
     """hmse_regex_seams: the occurrence of the regex at every SEAM start o of every chunk (cuts[k + 1] - o < reach), walked through
     the chunk map.  -> (hits int64[n] = corpus offset << 8 | (length - 1), any order; n_hits; count int64[1] = n_hits)."""
     return _seams("regex_seams", raw, raw_off, cuts, slot, hits_cap, 1, _regex_args(rx), refuse=_BAD_TABLES_OR_AUTOMATON)
+
+
+@dataclass
+class RegexA:
+    """The device arrays and the header of a regular expression compiled with assertions (include/hmse_regexa.h `hmse_regexa`; built by
+    regex.Regex(assertions=True))."""
+    table: torch.Tensor          # int16 [n_states * n_classes]: the bits of the u16 entries
+    classmap: torch.Tensor       # uint8 [256]
+    n_states: int
+    n_classes: int               # the EDGE class (the last one) included
+    reach: int
+    start: tuple                 # the four start states, by the kind of the byte in front
+
+    def header(self) -> "_lib.HmseRegexa":
+        return _lib.HmseRegexa(C.sizeof(_lib.HmseRegexa), int(self.n_states), int(self.n_classes), int(self.reach),
+                               (C.c_uint32 * 4)(*(int(v) for v in self.start)), self.table.data_ptr(), self.classmap.data_ptr())
+
+
+def _regexa_args(rx: RegexA):
+    if len(rx.start) != 4:
+        raise HmseError(-1, "regexa: an automaton has four start states")
+    return _regex_args(rx)
+
+
+def regexa_scan(raw: torch.Tensor, raw_off: torch.Tensor, mult: torch.Tensor | None, rx: RegexA, hits_cap: int | None = None,
+                raw_bytes: int | None = None):
+    """hmse_regexa_scan: the occurrence of the asserting regex at every SCAN start p of every record (p > raw_off[r] and
+    raw_off[r + 1] - p > reach: the byte in front, the match and its look-ahead byte lie in the record).  Returns what regex_scan returns."""
+    return _scan("regexa_scan", raw, raw_off, mult, raw_bytes, hits_cap, 1, _regexa_args(rx), refuse=_BAD_TABLES_OR_AUTOMATON)
+
+
+def regexa_seams(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, rx: RegexA, hits_cap: int | None = None):
+    """hmse_regexa_seams: the occurrence of the asserting regex at every SEAM start o of every non-empty chunk k (o == cuts[k] or
+    cuts[k + 1] - o <= reach), both context bytes read through the chunk map.  Returns what regex_seams returns."""
+    return _seams("regexa_seams", raw, raw_off, cuts, slot, hits_cap, 1, _regexa_args(rx), refuse=_BAD_TABLES_OR_AUTOMATON)
 
 
 APPROX_MAX_PATTERNS, APPROX_MAX_LEN, APPROX_MAX_K = 8, 64, 16

@@ -9,8 +9,8 @@ plain Python with the standard `re` module as the oracle):
     \\d \\D \\w \\W \\s \\S (ASCII), \\ plus ASCII punctuation; `.` (any byte but 0x0A; dotall: any byte); classes [...] and [^...] with
     ranges and those escapes ([ ] ^ - \\ escaped inside); groups ( ) and (?: ) (nothing is captured); alternation (an empty alternative
     is allowed); ? * + {m} {m,} {m,n} with m <= n <= 256.  What is accepted means what it means to `re` in bytes mode; everything else
-    (anchors, \\b, back-references, octal, lazy and possessive forms, a quantifier on a quantifier or on nothing, other (? forms,
-    {,n}) is refused with a RegexError naming the byte offset.
+    (anchors and \\b unless assertions=True, back-references, octal, lazy and possessive forms, a quantifier on a quantifier or on
+    nothing, other (? forms, {,n}) is refused with a RegexError naming the byte offset.
   * ignore_case closes every literal and class under ASCII case BEFORE a class is negated (re.IGNORECASE on bytes); bytes >= 0x80
     are untouched; the data is never folded.
 Compiled form (deterministic): Glushkov position automaton -> subset construction -> minimal DFA.  State 0 is the dead state (its row
@@ -18,6 +18,17 @@ is all 0), state 1 the start, the others in BFS order from the start over the cl
 equal columns share a class, classes numbered by their smallest byte); `table` u16[n_states * n_classes] = next state, OR-ed with
 HMSE_REGEX_ACCEPT iff the next state accepts; `reach` = the longest path from the start through live states if that graph is acyclic,
 else 256.
+assertions=True (opt-in; the default accepts and refuses exactly as above): the parser additionally takes the zero-width assertions ^ $ \\A
+\\Z \\b \\B with the meaning of re.MULTILINE on bytes — between the previous byte a and the next byte b (the text is the whole buffer;
+its ends are the EDGE): ^ iff a is the edge or 0x0A, $ iff b is, \\A iff a is the edge, \\Z iff b is, \\b iff exactly one of a, b is an
+ASCII word byte, \\B otherwise.  An occurrence's assertions are evaluated against the real buf[o - 1] and buf[o + l].  Refused with the
+offset: a quantifier directly on an assertion (a group that holds one may be quantified), \\b in a class, \\z, \\G, look-around, inline
+flags; a pattern that can match nothing non-empty is refused as "matches nothing but the empty string".  Compiled form
+(include/hmse_regexa.h; tests/regexa_ref.py is the oracle): an assertion is a 16-bit mask over (kind before, kind after),
+kinds EDGE = 0, NL = 1, WORD = 2, OTHER = 3; Glushkov with masks; a state is (positions, kind of the byte just read); four start states
+`start` (by the kind in front) numbered first, then BFS; the classes refine the kinds and EDGE is one more, the last (`edge_class`), whose
+column leads to state 0; the accept flag of table[s * n_classes + c] says that a match may end just BEFORE a byte of class c; the walk
+reads reach + 1 classes.  Out of scope: look-around, Unicode word classes, CR handling, multi-byte line terminators.
 """
 from __future__ import annotations
 
@@ -54,6 +65,27 @@ def _close_case(m: int) -> int:
     return m | ((m & _UPPER) << 32) | ((m & _LOWER) >> 32)
 
 
+# ---- assertions (assertions=True): the KIND of a byte, and an assertion as a 16-bit mask over (kind of the byte before, kind of the byte after)
+EDGE, NL, WORD, OTHER = 0, 1, 2, 3
+_FULL = 0xFFFF
+
+
+def byte_kind(b: int) -> int:
+    return NL if b == 0x0A else WORD if (_WORD >> b) & 1 else OTHER
+
+
+def _pairs(holds) -> int:
+    return sum(1 << (a * 4 + b) for a in range(4) for b in range(4) if holds(a, b))
+
+
+_ASSERTION = {"^": _pairs(lambda a, b: a in (EDGE, NL)), "$": _pairs(lambda a, b: b in (EDGE, NL)),
+              "A": _pairs(lambda a, b: a == EDGE), "Z": _pairs(lambda a, b: b == EDGE),
+              "b": _pairs(lambda a, b: (a == WORD) != (b == WORD)), "B": _pairs(lambda a, b: (a == WORD) == (b == WORD))}
+
+
+_KIND_OF = np.array([byte_kind(b) for b in range(256)], np.int64)
+
+
 class RegexError(ValueError):
     """A pattern outside the syntax or above a cap; `offset` is the byte offset in the pattern (None for a cap)."""
 
@@ -64,8 +96,8 @@ class RegexError(ValueError):
 
 # ---- parser: pattern -> tree of ("set", mask) | ("cat", [..]) | ("alt", [..]) | ("rep", node, m, n or None) ------------------------------
 class _Parser:
-    def __init__(self, pat: bytes, ignore_case: bool, dotall: bool):
-        self.p, self.i, self.ic, self.dotall = pat, 0, ignore_case, dotall
+    def __init__(self, pat: bytes, ignore_case: bool, dotall: bool, assertions: bool = False):
+        self.p, self.i, self.ic, self.dotall, self.assertions = pat, 0, ignore_case, dotall, assertions
 
     def parse(self):
         node = self.alt()
@@ -94,7 +126,13 @@ class _Parser:
         if c in b"}]":
             raise RegexError(f"an unescaped {chr(c)!r}", at)
         if c in b"^$":
-            raise RegexError(f"the anchor {chr(c)!r} (line anchors are out of scope)", at)
+            if not self.assertions:
+                raise RegexError(f"the anchor {chr(c)!r} (line anchors are out of scope)", at)
+            self.i += 1
+            return self.asserted(_ASSERTION[chr(c)])
+        if self.assertions and c == 0x5C and self.p[at + 1: at + 2] in (b"A", b"Z", b"b", b"B"):
+            self.i += 2
+            return self.asserted(_ASSERTION[chr(self.p[at + 1])])
         node = self.atom()
         q = self.quantifier()
         if q is None:
@@ -104,6 +142,11 @@ class _Parser:
         if self.i < len(self.p) and self.p[self.i] in b"*{":
             raise RegexError("a quantifier on a quantifier", self.i)
         return ("rep", node, q[0], q[1])
+
+    def asserted(self, mask: int):
+        if self.i < len(self.p) and self.p[self.i] in b"?*+{":
+            raise RegexError("a quantifier on an assertion (quantify a group that holds it)", self.i)
+        return ("assert", mask)
 
     def quantifier(self):
         if self.i >= len(self.p):
@@ -231,6 +274,8 @@ def _positions(node) -> int:
     k = node[0]
     if k == "set":
         return 1
+    if k == "assert":
+        return 0
     if k == "rep":
         m, n = node[2], node[3]
         return _positions(node[1]) * max(m + 1 if n is None else n, 1)
@@ -285,30 +330,116 @@ def _concat(a, b, follow):
     return a[0] and b[0], a[1] | (b[1] if a[0] else 0), b[2] | (a[2] if b[0] else 0)
 
 
+# ---- the same with assertions: nullable is a mask, first / last map a position to a mask, follow[p] maps a successor to a mask ----------
+def _or(d, e):
+    d = dict(d)
+    for p, m in e.items():
+        d[p] = d.get(p, 0) | m
+    return d
+
+
+def _and(d, mask: int):
+    return {p: m & mask for p, m in d.items() if m & mask}
+
+
+def _link_masked(last, first, follow):
+    for p, mp in last.items():
+        f = follow[p]
+        for q, mq in first.items():
+            if mp & mq:
+                f[q] = f.get(q, 0) | (mp & mq)
+
+
+def _concat_masked(a, b, follow):
+    _link_masked(a[2], b[1], follow)
+    return a[0] & b[0], _or(a[1], _and(b[1], a[0])), _or(b[2], _and(a[2], b[0]))
+
+
+def _glushkov_masked(node, sym, follow):
+    """_glushkov with assertions: everything zero-width between two consumed bytes sees the same (kind before, kind after), so a sequence
+    ANDs masks and an alternation ORs them.  A star contributes the full mask for zero iterations; further empty iterations only shrink it."""
+    k = node[0]
+    if k == "assert":
+        return node[1], {}, {}
+    if k == "set":
+        p = len(sym)
+        sym.append(node[1])
+        follow.append({})
+        return 0, {p: _FULL}, {p: _FULL}
+    if k == "alt":
+        nu, fi, la = 0, {}, {}
+        for c in node[1]:
+            a, b, d = _glushkov_masked(c, sym, follow)
+            nu, fi, la = nu | a, _or(fi, b), _or(la, d)
+        return nu, fi, la
+    if k == "cat":
+        acc = (_FULL, {}, {})
+        for c in node[1]:
+            acc = _concat_masked(acc, _glushkov_masked(c, sym, follow), follow)
+        return acc
+    _, body, m, n = node
+    acc = (_FULL, {}, {})
+    for _ in range(m):
+        acc = _concat_masked(acc, _glushkov_masked(body, sym, follow), follow)
+    if n is None:
+        _, fi, la = _glushkov_masked(body, sym, follow)
+        _link_masked(la, fi, follow)
+        acc = _concat_masked(acc, (_FULL, fi, la), follow)
+    else:
+        for _ in range(n - m):
+            _, fi, la = _glushkov_masked(body, sym, follow)
+            acc = _concat_masked(acc, (_FULL, fi, la), follow)
+    return acc
+
+
+def _by_pair(d):
+    """{position: mask} -> for each of the 16 (before, after) pairs the bit set of the positions whose mask holds it"""
+    out = [0] * 16
+    for p, m in d.items():
+        j = 0
+        while m:
+            if m & 1:
+                out[j] |= 1 << p
+            m >>= 1
+            j += 1
+    return out
+
+
 class Regex:
     """A compiled regular expression (module docstring).  .n_states, .n_classes, .reach, .min_len; .table (uint16 numpy), .classmap
     (uint8 numpy); .match_at(buf, o) simulates the table on the host.  With a device: .rx (ops.Regex: the arrays in HBM and the
-    `hmse_regex` header) and .resident_bytes."""
+    `hmse_regex` header) and .resident_bytes.
+    assertions=True: the ASSERTING form (module docstring; include/hmse_regexa.h) — .asserting, .start (the four start states, by the kind
+    of the byte in front), .edge_class (= n_classes - 1), .rx an ops.RegexA; match_at / match_all evaluate the assertions against the real
+    bytes around the match in `buf`, whose ends are the text's edges."""
 
-    def __init__(self, pattern, ignore_case: bool = False, dotall: bool = False, device=None):
+    def __init__(self, pattern, ignore_case: bool = False, dotall: bool = False, device=None, assertions: bool = False):
         if isinstance(pattern, str) or not isinstance(pattern, (bytes, bytearray, memoryview)):
             raise RegexError(f"a pattern is bytes, got a {type(pattern).__name__} (encode it)")
         self.pattern, self.ignore_case, self.dotall = bytes(pattern), bool(ignore_case), bool(dotall)
-        tree = _Parser(self.pattern, self.ignore_case, self.dotall).parse()
+        self.asserting, self.start, self.edge_class = bool(assertions), (1, 1, 1, 1), None
+        tree = _Parser(self.pattern, self.ignore_case, self.dotall, self.asserting).parse()
         n_pos = _positions(tree)
         if n_pos > _MAX_POSITIONS:
             raise RegexError(f"{n_pos} literal / class positions after expanding the counted repeats; the compiler takes {_MAX_POSITIONS}")
         sym, follow = [], []
-        nullable, first, last = _glushkov(tree, sym, follow)
-        trans, accept, cols = self._subsets(sym, follow, nullable, first, last)
-        self._minimise(trans, accept, cols)
+        if self.asserting:
+            _, first, last = _glushkov_masked(tree, sym, follow)
+            self._minimise_asserting(*self._subsets_asserting(sym, follow, first, last))
+        else:
+            nullable, first, last = _glushkov(tree, sym, follow)
+            trans, accept, cols = self._subsets(sym, follow, nullable, first, last)
+            self._minimise(trans, accept, cols)
         self.dev, self.rx, self.resident_bytes, self._lists = None, None, 0, None
         if device is not None:
             import torch
             from . import ops
             self.dev = torch.device(device)
-            self.rx = ops.Regex(torch.from_numpy(self.table.view(np.int16).copy()).to(self.dev), torch.from_numpy(self.classmap.copy()).to(self.dev),
-                                self.n_states, self.n_classes, self.reach)
+            arrays = torch.from_numpy(self.table.view(np.int16).copy()).to(self.dev), torch.from_numpy(self.classmap.copy()).to(self.dev)
+            if self.asserting:
+                self.rx = ops.RegexA(*arrays, self.n_states, self.n_classes, self.reach, self.start)
+            else:
+                self.rx = ops.Regex(*arrays, self.n_states, self.n_classes, self.reach)
             self.resident_bytes = self.table.nbytes + self.classmap.nbytes
 
     # -- subset construction over the byte classes of the positions' sets: state 0 = dead, 1 = start --
@@ -456,10 +587,208 @@ class Regex:
                     ready.append(t)
         self.reach = min(max(depth), HMSE_REGEX_MAX_LEN) if done == m - 1 else HMSE_REGEX_MAX_LEN
 
+    # -- the asserting form: a state is (positions just read, kind of the byte just read); states 1..4 = the starts by the kind in front --
+    @staticmethod
+    def _subsets_asserting(sym, follow, first, last):
+        """-> (trans, sig, byte_col, col_kind): sig[s] bit b = state s accepts when the NEXT byte has kind b (b = EDGE included)."""
+        pos_of = [0] * 256
+        for p, m in enumerate(sym):
+            bit, b = 1 << p, 0
+            while m:
+                if m & 1:
+                    pos_of[b] |= bit
+                m >>= 1
+                b += 1
+        cols, col_kind, col_of, byte_col = [], [], {}, []            # the columns refine the kinds: 0x0A alone, word bytes, the rest
+        for b in range(256):
+            key = (pos_of[b], byte_kind(b))
+            c = col_of.setdefault(key, len(cols))
+            if c == len(cols):
+                cols.append(pos_of[b])
+                col_kind.append(key[1])
+            byte_col.append(c)
+        first_by, last_by = _by_pair(first), _by_pair(last)
+        follow_by = [_by_pair(f) for f in follow]
+        order = [None] + [(0, a, True) for a in range(4)]            # (positions, kind, is a start)
+        ids = {key: i for i, key in enumerate(order)}
+        trans, sig = [[0] * len(cols)], [0]
+        s = 1
+        while s < len(order):
+            ps, a, init = order[s]
+            nxt = [0, 0, 0, 0]                                        # by the kind of the byte read next
+            if init:
+                for b in (NL, WORD, OTHER):
+                    nxt[b] = first_by[a * 4 + b]
+                sig.append(0)                                         # (a start's flags are never looked at: the walk reports from i = 1 on)
+            else:
+                g = 0
+                for b in range(4):
+                    if ps & last_by[a * 4 + b]:
+                        g |= 1 << b
+                sig.append(g)
+                p = 0
+                while ps:
+                    if ps & 1:
+                        f = follow_by[p]
+                        for b in (NL, WORD, OTHER):
+                            nxt[b] |= f[a * 4 + b]
+                    ps >>= 1
+                    p += 1
+            row = []
+            for c, kind in zip(cols, col_kind):
+                t = nxt[kind] & c
+                if t == 0:
+                    row.append(0)
+                    continue
+                key = (t, kind, False)
+                j = ids.get(key)
+                if j is None:
+                    j = ids[key] = len(order)
+                    if j >= _MAX_SUBSETS:
+                        raise RegexError(f"the subset construction exceeds {_MAX_SUBSETS} states (the table holds {HMSE_REGEX_MAX_TABLE} entries)")
+                    order.append(key)
+                row.append(j)
+            trans.append(row)
+            s += 1
+        return trans, sig, byte_col, col_kind
+
+    def _minimise_asserting(self, trans, sig, byte_col, col_kind):
+        n, k = len(trans), len(trans[0])
+        starts = (1, 2, 3, 4)
+        back = [[] for _ in range(n)]
+        for s, row in enumerate(trans):
+            for t in set(row):
+                back[t].append(s)
+        live = [False] * n
+        stack = [s for s in range(n) if sig[s]]
+        for s in stack:
+            live[s] = True
+        while stack:
+            for q in back[stack.pop()]:
+                if not live[q]:
+                    live[q] = True
+                    stack.append(q)
+        live[0] = False
+        trans = [[t if live[t] else 0 for t in row] if live[s] else [0] * k for s, row in enumerate(trans)]
+        if not any(live[s] for s in starts):
+            raise RegexError("the pattern matches nothing but the empty string")
+        # Moore from the partition by the 4-bit accept signature; a start without a live successor keeps a (zero) row of its own: the
+        # header's start[] never names the dead state
+        block = [0 if not live[s] and s not in starts else (1 if not live[s] else 2 + sig[s]) for s in range(n)]
+        n_blocks = len(set(block))
+        while True:
+            seen = {}
+            block = [seen.setdefault((block[s], tuple(block[t] for t in trans[s])), len(seen)) for s in range(n)]
+            if len(seen) == n_blocks:
+                break
+            n_blocks = len(seen)
+        rep = {}
+        for s in range(n):
+            rep.setdefault(block[s], s)
+        # number the blocks: dead 0, the starts in the order of their kinds, the others in BFS order over the columns in ascending order
+        num, queue = {block[0]: 0}, []
+        for s in starts:
+            if block[s] not in num:
+                num[block[s]] = len(num)
+                queue.append(block[s])
+        for b in queue:
+            for t in trans[rep[b]]:
+                if block[t] not in num:
+                    num[block[t]] = len(num)
+                    queue.append(block[t])
+        m = len(num)
+        rows, sg = [[0] * k for _ in range(m)], [0] * m
+        for b, i in num.items():
+            rows[i] = [num[block[t]] for t in trans[rep[b]]]
+            sg[i] = sig[rep[b]] if i else 0
+        # classes: bytes with equal columns AND equal kinds, numbered by their smallest byte; EDGE is one more class, the last
+        full = np.array(rows, np.int64)[:, np.array(byte_col)]       # [m, 256]
+        seen, classmap, keep = {}, np.zeros(256, np.uint8), []
+        for b in range(256):
+            key = (full[:, b].tobytes(), byte_kind(b))
+            c = seen.get(key)
+            if c is None:
+                c = seen[key] = len(keep)
+                keep.append(b)
+            classmap[b] = c
+        nc = len(keep) + 1
+        if m > MAX_STATES or nc > 256 or m * nc > HMSE_REGEX_MAX_TABLE:
+            raise RegexError(f"the minimal DFA has {m} states x {nc} classes = {m * nc} table entries; the caps are {MAX_STATES} states, 256 "
+                             f"classes and HMSE_REGEX_MAX_TABLE = {HMSE_REGEX_MAX_TABLE} entries")
+        nxt = np.concatenate([full[:, keep], np.zeros((m, 1), np.int64)], axis=1)      # [m, nc]; the EDGE column leads nowhere
+        kinds = np.array([byte_kind(b) for b in keep] + [EDGE])
+        sga = np.array(sg, np.int64)
+        flag = (sga[:, None] >> kinds[None, :]) & 1                  # a match may end just before a byte of this class
+        self.n_states, self.n_classes, self.edge_class = m, nc, nc - 1
+        self.classmap = classmap
+        self.table = (nxt | np.where(flag != 0, HMSE_REGEX_ACCEPT, 0)).astype(np.uint16).reshape(-1)
+        self.accept_sig = sga.astype(np.uint8)
+        self.accepting = sga != 0
+        self.start = tuple(num[block[s]] for s in starts)
+        # shortest non-empty match; longest path through the live states (256 if they hold a cycle)
+        seen_s, frontier, self.min_len = set(self.start), sorted(set(self.start)), 0
+        for step in range(1, m + 1):
+            frontier = sorted({int(t) for s in frontier for t in nxt[s] if t})
+            if any(sg[t] for t in frontier):
+                self.min_len = step
+                break
+            frontier = [t for t in frontier if t not in seen_s]
+            seen_s.update(frontier)
+        if self.min_len == 0 or self.min_len > HMSE_REGEX_MAX_LEN:
+            raise RegexError(f"the shortest non-empty match has more than HMSE_REGEX_MAX_LEN = {HMSE_REGEX_MAX_LEN} bytes")
+        succ = [sorted({int(t) for t in nxt[s] if t}) for s in range(m)]
+        indeg = [0] * m
+        for s in range(1, m):
+            for t in succ[s]:
+                indeg[t] += 1
+        depth, ready, done = [0] * m, [s for s in range(1, m) if indeg[s] == 0], 0
+        while ready:
+            s = ready.pop()
+            done += 1
+            for t in succ[s]:
+                depth[t] = max(depth[t], depth[s] + 1)
+                indeg[t] -= 1
+                if indeg[t] == 0:
+                    ready.append(t)
+        self.reach = min(max(depth), HMSE_REGEX_MAX_LEN) if done == m - 1 else HMSE_REGEX_MAX_LEN
+
+    def _match_at_asserting(self, buf, o: int) -> int:
+        n, nc, (tab, cm) = len(buf), self.n_classes, self._lists
+        s, best = self.start[byte_kind(buf[o - 1]) if o else EDGE], 0
+        for i in range(self.reach + 1):                              # the read at i = reach is look-ahead only
+            e = tab[s * nc + (cm[buf[o + i]] if o + i < n else self.edge_class)]
+            if i and e & HMSE_REGEX_ACCEPT:
+                best = i
+            s = e & 0x7FFF
+            if s == 0:
+                break
+        return best
+
+    def _match_all_asserting(self, buf) -> np.ndarray:
+        data = np.frombuffer(bytes(buf), np.uint8)
+        n = data.size
+        cls = np.append(self.classmap[data].astype(np.int64), self.edge_class)       # cls[n]: the look-ahead beyond the text
+        before = np.append(EDGE, _KIND_OF[data[:-1]]) if n else np.zeros(0, np.int64)
+        best = np.zeros(n, np.int64)
+        idx, state = np.arange(n), np.array(self.start, np.int64)[before]
+        tab = self.table.astype(np.int64)
+        for i in range(self.reach + 1):
+            if idx.size == 0:
+                break
+            e = tab[state * self.n_classes + cls[idx + i]]
+            if i:
+                best[idx[(e & HMSE_REGEX_ACCEPT) != 0]] = i
+            state = e & 0x7FFF
+            alive = state != 0                                       # (the EDGE column leads to state 0: no walk reads beyond cls[n])
+            idx, state = idx[alive], state[alive]
+        return best
+
     def match_at(self, buf, o: int) -> int:
         """The length of the occurrence at buf[o] (the longest match of 1..min(reach, len(buf) - o) bytes), or 0."""
         if self._lists is None:                                      # (plain lists: indexing a numpy array element by element is slow)
             self._lists = self.table.tolist(), self.classmap.tolist()
+        if self.asserting:
+            return self._match_at_asserting(buf, o)
         s, best, nc, (tab, cm) = 1, 0, self.n_classes, self._lists
         for i in range(min(self.reach, len(buf) - o)):
             e = tab[s * nc + cm[buf[o + i]]]
@@ -472,6 +801,8 @@ class Regex:
 
     def match_all(self, buf) -> np.ndarray:
         """match_at for every start of buf at once -> int64[len(buf)] (numpy: one step of all live walks per trip)."""
+        if self.asserting:
+            return self._match_all_asserting(buf)
         cls = self.classmap[np.frombuffer(bytes(buf), np.uint8)].astype(np.int64)
         n = cls.size
         best = np.zeros(n, np.int64)

@@ -926,7 +926,8 @@ int hmse_lines_gather(const uint8_t* raw, uint64_t raw_bytes, const uint64_t* ra
  *           With bit1 or bit2 nothing is read through the tables or the automaton, no hit is written, n_hits and count are 0.
  * The other arguments mean what they mean for hmse_find_scan / hmse_find_seams.  No workspace; stream-ordered, allocate nothing, never
  * sync.  Profile slots: hmse_regex_scan reports in 30, hmse_regex_seams in 31 (see Diagnostics below).
- * Out of scope: anchors and \b, captures, lazy matching, matches over 256 bytes, Unicode classes, several regexes in one automaton.
+ * Out of scope here: anchors and \b (include/hmse_regexa.h has them: hmse_regexa_scan / hmse_regexa_seams, a library of its own),
+ * captures, lazy matching, matches over 256 bytes, Unicode classes, several regexes in one automaton.
  */
 #define HMSE_REGEX_MAX_LEN   256
 #define HMSE_REGEX_MAX_TABLE 16384
