@@ -29,9 +29,9 @@ delimiters of more than one byte, CR stripping, merging the overlapping context 
 
 Regular expressions: a regex.Regex (compiled on the host into a bounded DFA, hmse_amd/regex.py has the syntax and the definitions) is
 answered by StoreFinder.count_regex / find_regex / grep_regex with the same three steps — scan of the unique records, place, seams
-(hmse_amd/csrc/regex.hip; include/hmse.h hmse_regex_*) — split by START: a start whose record still holds `reach` bytes is a scan
+(hmse_amd/csrc/regex_core.h, built by regex.hip; include/hmse.h hmse_regex_*) — split by START: a start whose record still holds `reach` bytes is a scan
 start, the last reach - 1 starts of every chunk are seam starts.  The result is a RegexFound: a Found with the lengths of the matches.
-A Regex compiled with assertions=True (^ $ \\A \\Z \\b \\B) goes through hmse_amd/csrc/regexa.hip (include/hmse_regexa.h), whose scan
+A Regex compiled with assertions=True (^ $ \\A \\Z \\b \\B) goes through the same kernels' asserting form (hmse_amd/csrc/regexa.hip; include/hmse_regexa.h), whose scan
 leaves a record's first start and its last `reach` ones to the seams as well.  Out of scope: captures, lazy matching, matches over
 256 bytes, Unicode classes, look-around, assertions in a PatternSet or in the approximate search, several regexes fused into one
 automaton, multi-byte line delimiters, routing find / find_set through the DFA.

@@ -29,6 +29,9 @@ kinds EDGE = 0, NL = 1, WORD = 2, OTHER = 3; Glushkov with masks; a state is (po
 `start` (by the kind in front) numbered first, then BFS; the classes refine the kinds and EDGE is one more, the last (`edge_class`), whose
 column leads to state 0; the accept flag of table[s * n_classes + c] says that a match may end just BEFORE a byte of class c; the walk
 reads reach + 1 classes.  Out of scope: look-around, Unicode word classes, CR handling, multi-byte line terminators.
+Both forms are one pipeline with two front ends: the passes from _byte_columns to _reach below are shared; what a
+state is and when it accepts is Regex._subsets / _minimise and Regex._subsets_asserting / _minimise_asserting.  The kernels that walk
+either table are hmse_amd/csrc/regex_core.h; tests/golden/regex_compiled.json pins the compiled form.
 """
 from __future__ import annotations
 
@@ -405,6 +408,148 @@ def _by_pair(d):
     return out
 
 
+# ---- Glushkov automaton -> table: the passes both forms run.  What a state IS and when it accepts is the forms' own (Regex._subsets /
+# _minimise, Regex._subsets_asserting / _minimise_asserting) -----------------------------------------------------------------------------
+def _byte_columns(sym, by_kind: bool):
+    """-> (cols, col_kind, byte_col): the distinct sets of positions that hold a byte — by_kind: of (positions, the byte's kind) — in
+    order of their smallest byte, the kind of every column (None without by_kind) and the column of every byte"""
+    pos_of = [0] * 256                                              # positions whose set holds byte b
+    for p, m in enumerate(sym):
+        bit, b = 1 << p, 0
+        while m:
+            if m & 1:
+                pos_of[b] |= bit
+            m >>= 1
+            b += 1
+    cols, col_kind, col_of, byte_col = [], [], {}, []
+    for b in range(256):
+        key = (pos_of[b], byte_kind(b) if by_kind else None)
+        c = col_of.setdefault(key, len(cols))
+        if c == len(cols):
+            cols.append(key[0])
+            col_kind.append(key[1])
+        byte_col.append(c)
+    return cols, col_kind, byte_col
+
+
+def _state_id(ids, order, key) -> int:
+    """the number of the subset construction's state `key`, a new one at the end of `order` if it has none"""
+    j = ids.get(key)
+    if j is None:
+        j = ids[key] = len(order)
+        if j >= _MAX_SUBSETS:
+            raise RegexError(f"the subset construction exceeds {_MAX_SUBSETS} states (the table holds {HMSE_REGEX_MAX_TABLE} entries)")
+        order.append(key)
+    return j
+
+
+def _fold_dead(trans, accepts, starts):
+    """States from which no state with a true accepts[s] is reachable fold into the dead state 0 -> (live, trans).  A pattern none of
+    whose starts keeps a successor is refused."""
+    n, k = len(trans), len(trans[0])
+    back = [[] for _ in range(n)]
+    for s, row in enumerate(trans):
+        for t in set(row):
+            back[t].append(s)
+    live = [False] * n
+    stack = [s for s in range(n) if accepts[s]]
+    for s in stack:
+        live[s] = True
+    while stack:
+        for q in back[stack.pop()]:
+            if not live[q]:
+                live[q] = True
+                stack.append(q)
+    live[0] = False
+    trans = [[t if live[t] else 0 for t in row] if live[s] else [0] * k for s, row in enumerate(trans)]
+    if not any(any(trans[s]) for s in starts):
+        raise RegexError("the pattern matches nothing but the empty string")
+    return live, trans
+
+
+def _refine(block, trans):
+    """Moore: split the blocks of the partition block[s] by their rows until none splits -> block[s]"""
+    n_blocks = len(set(block))
+    while True:
+        sig = {}
+        block = [sig.setdefault((block[s], tuple(block[t] for t in trans[s])), len(sig)) for s in range(len(trans))]
+        if len(sig) == n_blocks:
+            return block
+        n_blocks = len(sig)
+
+
+def _number(block, trans, starts):
+    """Number the blocks: dead 0, the starts' in their order, the others in BFS order over the columns in ascending order
+    -> (rows, reps, num): the numbered states' rows, their first member states, the number of every block"""
+    rep = {}
+    for s in range(len(trans)):
+        rep.setdefault(block[s], s)
+    num, queue = {block[0]: 0}, []
+    for s in starts:
+        if block[s] not in num:
+            num[block[s]] = len(num)
+            queue.append(block[s])
+    for b in queue:
+        for t in trans[rep[b]]:
+            if block[t] not in num:
+                num[block[t]] = len(num)
+                queue.append(block[t])
+    reps = [rep[b] for b in num]                                    # (num is in the order of the numbers)
+    return [[num[block[t]] for t in trans[r]] for r in reps], reps, num
+
+
+def _classes(rows, byte_col, asserting: bool):
+    """Bytes with equal columns — asserting: AND equal kinds — share a class, numbered by their smallest byte; asserting: EDGE is one
+    more class, the last, whose column leads nowhere -> (classmap, keep, nxt): keep = the smallest byte of every class, nxt int64[m, nc]"""
+    full = np.array(rows, np.int64)[:, np.array(byte_col)]          # [m, 256]
+    seen, classmap, keep = {}, np.zeros(256, np.uint8), []
+    for b in range(256):
+        key = (full[:, b].tobytes(), byte_kind(b) if asserting else None)
+        c = seen.get(key)
+        if c is None:
+            c = seen[key] = len(keep)
+            keep.append(b)
+        classmap[b] = c
+    nxt = full[:, keep]
+    if asserting:
+        nxt = np.concatenate([nxt, np.zeros((len(rows), 1), np.int64)], axis=1)
+    return classmap, keep, nxt
+
+
+def _min_len(nxt, starts, accepts) -> int:
+    """the shortest non-empty match: the steps from a start to the first state t with accepts[t]"""
+    seen, frontier = set(starts), sorted(set(starts))
+    for step in range(1, len(nxt) + 1):
+        frontier = sorted({int(t) for s in frontier for t in nxt[s] if t})
+        if any(accepts[t] for t in frontier):
+            if step <= HMSE_REGEX_MAX_LEN:
+                return step
+            break
+        frontier = [t for t in frontier if t not in seen]
+        seen.update(frontier)
+    raise RegexError(f"the shortest non-empty match has more than HMSE_REGEX_MAX_LEN = {HMSE_REGEX_MAX_LEN} bytes")
+
+
+def _reach(nxt) -> int:
+    """the longest path through the live states, 256 if they hold a cycle"""
+    m = len(nxt)
+    succ = [sorted({int(t) for t in nxt[s] if t}) for s in range(m)]
+    indeg = [0] * m
+    for s in range(1, m):
+        for t in succ[s]:
+            indeg[t] += 1
+    depth, ready, done = [0] * m, [s for s in range(1, m) if indeg[s] == 0], 0
+    while ready:
+        s = ready.pop()
+        done += 1
+        for t in succ[s]:
+            depth[t] = max(depth[t], depth[s] + 1)
+            indeg[t] -= 1
+            if indeg[t] == 0:
+                ready.append(t)
+    return min(max(depth), HMSE_REGEX_MAX_LEN) if done == m - 1 else HMSE_REGEX_MAX_LEN
+
+
 class Regex:
     """A compiled regular expression (module docstring).  .n_states, .n_classes, .reach, .min_len; .table (uint16 numpy), .classmap
     (uint8 numpy); .match_at(buf, o) simulates the table on the host.  With a device: .rx (ops.Regex: the arrays in HBM and the
@@ -442,28 +587,13 @@ class Regex:
                 self.rx = ops.Regex(*arrays, self.n_states, self.n_classes, self.reach)
             self.resident_bytes = self.table.nbytes + self.classmap.nbytes
 
-    # -- subset construction over the byte classes of the positions' sets: state 0 = dead, 1 = start --
+    # -- the plain form: a state is (positions just read, at the start); state 0 = dead, 1 = start; a state accepts or not --
     @staticmethod
     def _subsets(sym, follow, nullable, first, last):
-        pos_of = [0] * 256                                          # positions whose set holds byte b
-        for p, m in enumerate(sym):
-            bit, b = 1 << p, 0
-            while m:
-                if m & 1:
-                    pos_of[b] |= bit
-                m >>= 1
-                b += 1
-        cols, col_of = [], {}                                       # distinct pos_of values in order of their smallest byte
-        byte_col = []
-        for b in range(256):
-            c = col_of.setdefault(pos_of[b], len(cols))
-            if c == len(cols):
-                cols.append(pos_of[b])
-            byte_col.append(c)
-        ids = {(0, False): 0, (0, True): 1}                          # (positions just read, at the start)
+        cols, _, byte_col = _byte_columns(sym, False)
         order = [(0, False), (0, True)]
+        ids = {key: i for i, key in enumerate(order)}
         trans = [[0] * len(cols)]
-        accept = [False, nullable]
         s = 1
         while s < len(order):
             ps, init = order[s]
@@ -473,143 +603,37 @@ class Regex:
                     nxt |= follow[p]
                 ps >>= 1
                 p += 1
-            row = []
-            for c in cols:
-                t = nxt & c
-                if t == 0:
-                    row.append(0)
-                    continue
-                j = ids.get((t, False))
-                if j is None:
-                    j = ids[(t, False)] = len(order)
-                    if j >= _MAX_SUBSETS:
-                        raise RegexError(f"the subset construction exceeds {_MAX_SUBSETS} states (the table holds {HMSE_REGEX_MAX_TABLE} entries)")
-                    order.append((t, False))
-                    accept.append((t & last) != 0)
-                row.append(j)
-            trans.append(row)
+            trans.append([_state_id(ids, order, (nxt & c, False)) if nxt & c else 0 for c in cols])
             s += 1
-        return trans, accept, byte_col
+        return trans, [nullable if init else (ps & last) != 0 for ps, init in order], byte_col
 
     def _minimise(self, trans, accept, byte_col):
-        n, k = len(trans), len(trans[0])
-        # states from which no accepting state is reachable fold into the dead state
-        back = [[] for _ in range(n)]
-        for s, row in enumerate(trans):
-            for t in set(row):
-                back[t].append(s)
-        live = [False] * n
-        stack = [s for s in range(n) if accept[s]]
-        for s in stack:
-            live[s] = True
-        while stack:
-            for q in back[stack.pop()]:
-                if not live[q]:
-                    live[q] = True
-                    stack.append(q)
-        live[0] = False
-        trans = [[t if live[t] else 0 for t in row] if live[s] else [0] * k for s, row in enumerate(trans)]
-        if not any(trans[1]):
-            raise RegexError("the pattern matches nothing but the empty string")
+        live, trans = _fold_dead(trans, accept, (1,))
         # Moore: refine {dead} {accepting} {the others} until no block splits
-        block = [0 if not live[s] else (2 if accept[s] else 1) for s in range(n)]
-        n_blocks = len(set(block))
-        while True:
-            sig = {}
-            new = [sig.setdefault((block[s], tuple(block[t] for t in trans[s])), len(sig)) for s in range(n)]
-            block = new
-            if len(sig) == n_blocks:
-                break
-            n_blocks = len(sig)
-        rep = {}
-        for s in range(n):
-            rep.setdefault(block[s], s)
-        dead = block[0]
-        # number the blocks: dead 0, start 1, the others in BFS order over the columns in ascending order
-        num, queue = {dead: 0, block[1]: 1}, [block[1]]
-        if block[1] == dead:
-            raise RegexError("the pattern matches nothing but the empty string")
-        for b in queue:
-            for t in trans[rep[b]]:
-                if block[t] not in num:
-                    num[block[t]] = len(num)
-                    queue.append(block[t])
-        m = len(num)
-        rows = [[0] * k for _ in range(m)]
-        acc = [False] * m
-        for b, i in num.items():
-            rows[i] = [num[block[t]] for t in trans[rep[b]]]
-            acc[i] = accept[rep[b]] and b != dead
-        # classes: bytes with equal columns, numbered by their smallest byte
-        full = np.array(rows, np.int64)[:, np.array(byte_col)]      # [m, 256]
-        seen, classmap, keep = {}, np.zeros(256, np.uint8), []
-        for b in range(256):
-            key = full[:, b].tobytes()
-            c = seen.get(key)
-            if c is None:
-                c = seen[key] = len(keep)
-                keep.append(b)
-            classmap[b] = c
+        block = _refine([0 if not live[s] else (2 if accept[s] else 1) for s in range(len(trans))], trans)
+        rows, reps, _ = _number(block, trans, (1,))
+        m = len(rows)
+        classmap, keep, nxt = _classes(rows, byte_col, False)
         nc = len(keep)
         if m > MAX_STATES or m * nc > HMSE_REGEX_MAX_TABLE:
             raise RegexError(f"the minimal DFA has {m} states x {nc} classes = {m * nc} table entries; the caps are {MAX_STATES} states and "
                              f"HMSE_REGEX_MAX_TABLE = {HMSE_REGEX_MAX_TABLE} entries")
-        nxt = full[:, keep]                                          # [m, nc]
-        accb = np.array(acc, bool)
+        accb = np.array([i > 0 and accept[r] for i, r in enumerate(reps)], bool)
         self.n_states, self.n_classes = m, nc
         self.classmap = classmap
-        self.table = (nxt | np.where(accb[nxt], HMSE_REGEX_ACCEPT, 0)).astype(np.uint16).reshape(-1)
+        self.table = (nxt | np.where(accb[nxt], HMSE_REGEX_ACCEPT, 0)).astype(np.uint16).reshape(-1)    # the flag: the NEXT state accepts
         self.accepting = accb
-        # shortest non-empty match; longest path through the live states (256 if they hold a cycle)
-        dist, frontier, self.min_len = {1}, [1], 0
-        for step in range(1, m + 1):
-            frontier = sorted({int(t) for s in frontier for t in nxt[s] if t})
-            if any(accb[t] for t in frontier):
-                self.min_len = step
-                break
-            frontier = [t for t in frontier if t not in dist]
-            dist.update(frontier)
-        if self.min_len == 0 or self.min_len > HMSE_REGEX_MAX_LEN:
-            raise RegexError(f"the shortest non-empty match has more than HMSE_REGEX_MAX_LEN = {HMSE_REGEX_MAX_LEN} bytes")
-        succ = [sorted({int(t) for t in nxt[s] if t}) for s in range(m)]
-        indeg = [0] * m
-        for s in range(1, m):
-            for t in succ[s]:
-                indeg[t] += 1
-        depth, ready, done = [0] * m, [s for s in range(1, m) if indeg[s] == 0], 0
-        while ready:
-            s = ready.pop()
-            done += 1
-            for t in succ[s]:
-                depth[t] = max(depth[t], depth[s] + 1)
-                indeg[t] -= 1
-                if indeg[t] == 0:
-                    ready.append(t)
-        self.reach = min(max(depth), HMSE_REGEX_MAX_LEN) if done == m - 1 else HMSE_REGEX_MAX_LEN
+        self.min_len = _min_len(nxt, (1,), accb)
+        self.reach = _reach(nxt)
 
-    # -- the asserting form: a state is (positions just read, kind of the byte just read); states 1..4 = the starts by the kind in front --
+    # -- the asserting form: a state is (positions just read, kind of the byte just read, is a start); states 1..4 = the starts by the kind
+    #    in front; a state has a 4-bit signature: bit b = it accepts when the NEXT byte has kind b (b = EDGE included) --
     @staticmethod
     def _subsets_asserting(sym, follow, first, last):
-        """-> (trans, sig, byte_col, col_kind): sig[s] bit b = state s accepts when the NEXT byte has kind b (b = EDGE included)."""
-        pos_of = [0] * 256
-        for p, m in enumerate(sym):
-            bit, b = 1 << p, 0
-            while m:
-                if m & 1:
-                    pos_of[b] |= bit
-                m >>= 1
-                b += 1
-        cols, col_kind, col_of, byte_col = [], [], {}, []            # the columns refine the kinds: 0x0A alone, word bytes, the rest
-        for b in range(256):
-            key = (pos_of[b], byte_kind(b))
-            c = col_of.setdefault(key, len(cols))
-            if c == len(cols):
-                cols.append(pos_of[b])
-                col_kind.append(key[1])
-            byte_col.append(c)
+        cols, col_kind, byte_col = _byte_columns(sym, True)          # the columns refine the kinds: 0x0A alone, word bytes, the rest
         first_by, last_by = _by_pair(first), _by_pair(last)
         follow_by = [_by_pair(f) for f in follow]
-        order = [None] + [(0, a, True) for a in range(4)]            # (positions, kind, is a start)
+        order = [None] + [(0, a, True) for a in range(4)]
         ids = {key: i for i, key in enumerate(order)}
         trans, sig = [[0] * len(cols)], [0]
         s = 1
@@ -621,11 +645,7 @@ class Regex:
                     nxt[b] = first_by[a * 4 + b]
                 sig.append(0)                                         # (a start's flags are never looked at: the walk reports from i = 1 on)
             else:
-                g = 0
-                for b in range(4):
-                    if ps & last_by[a * 4 + b]:
-                        g |= 1 << b
-                sig.append(g)
+                sig.append(sum(1 << b for b in range(4) if ps & last_by[a * 4 + b]))
                 p = 0
                 while ps:
                     if ps & 1:
@@ -634,123 +654,34 @@ class Regex:
                             nxt[b] |= f[a * 4 + b]
                     ps >>= 1
                     p += 1
-            row = []
-            for c, kind in zip(cols, col_kind):
-                t = nxt[kind] & c
-                if t == 0:
-                    row.append(0)
-                    continue
-                key = (t, kind, False)
-                j = ids.get(key)
-                if j is None:
-                    j = ids[key] = len(order)
-                    if j >= _MAX_SUBSETS:
-                        raise RegexError(f"the subset construction exceeds {_MAX_SUBSETS} states (the table holds {HMSE_REGEX_MAX_TABLE} entries)")
-                    order.append(key)
-                row.append(j)
-            trans.append(row)
+            trans.append([_state_id(ids, order, (nxt[kind] & c, kind, False)) if nxt[kind] & c else 0 for c, kind in zip(cols, col_kind)])
             s += 1
-        return trans, sig, byte_col, col_kind
+        return trans, sig, byte_col
 
-    def _minimise_asserting(self, trans, sig, byte_col, col_kind):
-        n, k = len(trans), len(trans[0])
+    def _minimise_asserting(self, trans, sig, byte_col):
         starts = (1, 2, 3, 4)
-        back = [[] for _ in range(n)]
-        for s, row in enumerate(trans):
-            for t in set(row):
-                back[t].append(s)
-        live = [False] * n
-        stack = [s for s in range(n) if sig[s]]
-        for s in stack:
-            live[s] = True
-        while stack:
-            for q in back[stack.pop()]:
-                if not live[q]:
-                    live[q] = True
-                    stack.append(q)
-        live[0] = False
-        trans = [[t if live[t] else 0 for t in row] if live[s] else [0] * k for s, row in enumerate(trans)]
-        if not any(live[s] for s in starts):
-            raise RegexError("the pattern matches nothing but the empty string")
+        live, trans = _fold_dead(trans, sig, starts)
         # Moore from the partition by the 4-bit accept signature; a start without a live successor keeps a (zero) row of its own: the
         # header's start[] never names the dead state
-        block = [0 if not live[s] and s not in starts else (1 if not live[s] else 2 + sig[s]) for s in range(n)]
-        n_blocks = len(set(block))
-        while True:
-            seen = {}
-            block = [seen.setdefault((block[s], tuple(block[t] for t in trans[s])), len(seen)) for s in range(n)]
-            if len(seen) == n_blocks:
-                break
-            n_blocks = len(seen)
-        rep = {}
-        for s in range(n):
-            rep.setdefault(block[s], s)
-        # number the blocks: dead 0, the starts in the order of their kinds, the others in BFS order over the columns in ascending order
-        num, queue = {block[0]: 0}, []
-        for s in starts:
-            if block[s] not in num:
-                num[block[s]] = len(num)
-                queue.append(block[s])
-        for b in queue:
-            for t in trans[rep[b]]:
-                if block[t] not in num:
-                    num[block[t]] = len(num)
-                    queue.append(block[t])
-        m = len(num)
-        rows, sg = [[0] * k for _ in range(m)], [0] * m
-        for b, i in num.items():
-            rows[i] = [num[block[t]] for t in trans[rep[b]]]
-            sg[i] = sig[rep[b]] if i else 0
-        # classes: bytes with equal columns AND equal kinds, numbered by their smallest byte; EDGE is one more class, the last
-        full = np.array(rows, np.int64)[:, np.array(byte_col)]       # [m, 256]
-        seen, classmap, keep = {}, np.zeros(256, np.uint8), []
-        for b in range(256):
-            key = (full[:, b].tobytes(), byte_kind(b))
-            c = seen.get(key)
-            if c is None:
-                c = seen[key] = len(keep)
-                keep.append(b)
-            classmap[b] = c
+        block = _refine([0 if not live[s] and s not in starts else (1 if not live[s] else 2 + sig[s]) for s in range(len(trans))], trans)
+        rows, reps, num = _number(block, trans, starts)
+        m = len(rows)
+        classmap, keep, nxt = _classes(rows, byte_col, True)         # EDGE is one more class, the last
         nc = len(keep) + 1
         if m > MAX_STATES or nc > 256 or m * nc > HMSE_REGEX_MAX_TABLE:
             raise RegexError(f"the minimal DFA has {m} states x {nc} classes = {m * nc} table entries; the caps are {MAX_STATES} states, 256 "
                              f"classes and HMSE_REGEX_MAX_TABLE = {HMSE_REGEX_MAX_TABLE} entries")
-        nxt = np.concatenate([full[:, keep], np.zeros((m, 1), np.int64)], axis=1)      # [m, nc]; the EDGE column leads nowhere
         kinds = np.array([byte_kind(b) for b in keep] + [EDGE])
-        sga = np.array(sg, np.int64)
-        flag = (sga[:, None] >> kinds[None, :]) & 1                  # a match may end just before a byte of this class
+        sga = np.array([sig[r] if i else 0 for i, r in enumerate(reps)], np.int64)
+        flag = (sga[:, None] >> kinds[None, :]) & 1                  # the flag: a match may end just BEFORE a byte of this class
         self.n_states, self.n_classes, self.edge_class = m, nc, nc - 1
         self.classmap = classmap
         self.table = (nxt | np.where(flag != 0, HMSE_REGEX_ACCEPT, 0)).astype(np.uint16).reshape(-1)
         self.accept_sig = sga.astype(np.uint8)
         self.accepting = sga != 0
         self.start = tuple(num[block[s]] for s in starts)
-        # shortest non-empty match; longest path through the live states (256 if they hold a cycle)
-        seen_s, frontier, self.min_len = set(self.start), sorted(set(self.start)), 0
-        for step in range(1, m + 1):
-            frontier = sorted({int(t) for s in frontier for t in nxt[s] if t})
-            if any(sg[t] for t in frontier):
-                self.min_len = step
-                break
-            frontier = [t for t in frontier if t not in seen_s]
-            seen_s.update(frontier)
-        if self.min_len == 0 or self.min_len > HMSE_REGEX_MAX_LEN:
-            raise RegexError(f"the shortest non-empty match has more than HMSE_REGEX_MAX_LEN = {HMSE_REGEX_MAX_LEN} bytes")
-        succ = [sorted({int(t) for t in nxt[s] if t}) for s in range(m)]
-        indeg = [0] * m
-        for s in range(1, m):
-            for t in succ[s]:
-                indeg[t] += 1
-        depth, ready, done = [0] * m, [s for s in range(1, m) if indeg[s] == 0], 0
-        while ready:
-            s = ready.pop()
-            done += 1
-            for t in succ[s]:
-                depth[t] = max(depth[t], depth[s] + 1)
-                indeg[t] -= 1
-                if indeg[t] == 0:
-                    ready.append(t)
-        self.reach = min(max(depth), HMSE_REGEX_MAX_LEN) if done == m - 1 else HMSE_REGEX_MAX_LEN
+        self.min_len = _min_len(nxt, self.start, self.accepting)
+        self.reach = _reach(nxt)
 
     def _match_at_asserting(self, buf, o: int) -> int:
         n, nc, (tab, cm) = len(buf), self.n_classes, self._lists

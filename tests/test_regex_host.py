@@ -346,7 +346,7 @@ def test_nonoverlapping_equals_the_plain_loop():
 
 # ---- the kernels on the CPU --------------------------------------------------------------------------------------------------------------
 def test_the_emulator_builds_and_its_cases_pass():
-    """tools/regex_emu.py: the kernels cut out of regex.hip (and place_kernel of chunkmap.h), one std::thread per lane, against a
+    """tools/regex_emu.py: the kernels of regex_core.h in their plain form (and place_kernel of chunkmap.h), one std::thread per lane, against a
     brute-force walk (no sanitizer here)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "regex_emu.py"), "--iters", "6", "--seed", "4242"], capture_output=True, text=True)
     assert r.returncode == 0 and "ALL OK" in r.stdout and "6 cases ran" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

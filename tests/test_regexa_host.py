@@ -295,7 +295,7 @@ def test_wrappers_refuse_host_tensors_and_go_through_the_one_call_path(monkeypat
 
 # ---- the kernels on the CPU ---------------------------------------------------------------------------------------------------------------
 def test_the_emulator_builds_and_its_cases_pass():
-    """tools/regexa_emu.py: the kernels cut out of regexa.hip, one std::thread per lane, against a brute-force walk with the real context
+    """tools/regexa_emu.py: the kernels of regex_core.h in their asserting form, one std::thread per lane, against a brute-force walk with the real context
     bytes; the first five cases damage the automaton in the five ways status bit 2 names (no sanitizer here)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "regexa_emu.py"), "--iters", "6"], capture_output=True, text=True)
     assert r.returncode == 0 and "ALL OK" in r.stdout and "6 cases ran" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
