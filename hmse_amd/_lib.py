@@ -16,6 +16,7 @@ HIP_LIB_PATH = os.path.join(_CSRC, "libhmse_hip" + ("_" + os.environ["HMSE_LIB_V
 CORPUS_LIB_PATH = os.path.join(_CSRC, "libhmse_corpus.so")
 GUNZIP_LIB_PATH = os.path.join(_CSRC, "libhmse_gunzip.so")     # include/hmse_gunzip.h: the gzip import, beside the C ABI of include/hmse.h
 REGEXA_LIB_PATH = os.path.join(_CSRC, "libhmse_regexa.so")     # include/hmse_regexa.h: the regex search with assertions, likewise
+TALLY_LIB_PATH = os.path.join(_CSRC, "libhmse_tally.so")       # include/hmse_tally.h: the tally of search results, likewise
 
 
 class HmseCfg(C.Structure):
@@ -209,6 +210,14 @@ REGEXA_SIGNATURES = {
     "hmse_regexa_seams": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, hmse_regexa* rx, "
                          "u64* hits, u64 hits_cap, u64* n_hits, u64* count, u32* status, stream",
 }
+# The entry points of include/hmse_tally.h (the tally of search results, csrc/libhmse_tally.so); tests/test_tally_host.py holds this table
+# against that header.  Parsed into a table of its own (PARSED_TALLY); ops._call looks a name up in PARSED, PARSED_REGEXA, then there.
+TALLY_SIGNATURES = {
+    "hmse_tally_keys": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, u64*? start, u64*? end, u64 n, "
+                       "u32 flags, u64 seed, u32 key_bits, u64*? key, u32* status, stream",
+    "hmse_tally_same": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, u64*? start, u64*? end, u64*? rep, "
+                       "u64 n, u32 flags, u8*? same, u32* status, stream",
+}
 
 _ELEM = {"u8": C.c_uint8, "u32": C.c_uint32, "i32": C.c_int32, "u64": C.c_uint64, "i64": C.c_int64, "f64": C.c_double}
 _SCALAR = {"u32": C.c_uint32, "u64": C.c_uint64, "size_t": C.c_size_t, "int": C.c_int}
@@ -247,6 +256,7 @@ def _parse(sig: str):
 
 PARSED = {name: _parse(sig) for name, sig in {**SIGNATURES, **GUNZIP_SIGNATURES}.items()}      # name -> (restype, parameters)
 PARSED_REGEXA = {name: _parse(sig) for name, sig in REGEXA_SIGNATURES.items()}
+PARSED_TALLY = {name: _parse(sig) for name, sig in TALLY_SIGNATURES.items()}
 
 _hip = None
 _corpus = None
@@ -278,6 +288,13 @@ def hip_lib():
         L._regexa = A = C.CDLL(REGEXA_LIB_PATH)          # (it links against libhmse_hip.so as well)
         for name, (restype, params) in PARSED_REGEXA.items():
             fn = getattr(A, name)
+            fn.restype, fn.argtypes = restype, [p.ctype for p in params]
+            setattr(L, name, fn)
+        if not os.path.exists(TALLY_LIB_PATH):
+            raise ImportError(f"{TALLY_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        L._tally = T = C.CDLL(TALLY_LIB_PATH)            # (it links against libhmse_hip.so as well)
+        for name, (restype, params) in PARSED_TALLY.items():
+            fn = getattr(T, name)
             fn.restype, fn.argtypes = restype, [p.ctype for p in params]
             setattr(L, name, fn)
         _hip = L

@@ -45,6 +45,15 @@ occurrence, whose `offsets` are the matches' LAST bytes (every end within k edit
 are each reported; best_ends keeps one per run).  With k = 0 they are find's offsets + m - 1.  StoreFinder.spans gives the (start, end)
 of every occurrence, as text() accepts them.  Out of scope: patterns over 64 bytes, Hamming-only and transposition distances, weighted
 costs, errors inside a regex, a dictionary of approximate patterns (PatternSet), routing find through this path.
+
+Tally: StoreFinder.tally answers "which values did the expression take, and how often each" (grep -o RX | sort | uniq -c | sort -rn) for
+the ranges of a RegexFound, a Lines or any (start, end) pair: per group the distinct texts with their counts and a representative
+occurrence, most frequent first (hmse_amd/csrc/tally.hip; include/hmse_tally.h has the definitions, tests/tally_ref.py restates them in
+plain Python).  Ranges are bucketed by a 64-bit key of their bytes (hmse_tally_keys) and a bucket's members are then compared with its
+first member byte for byte (hmse_tally_same): a key that merely agrees proves nothing, and what does not equal its bucket's first member
+waits for the next round under another seed.  tally_regex = tally(nonoverlapping(find_regex(rx))).  Out of scope: texts compared under
+anything but byte or ASCII-folded equality, weighting occurrences, lexicographic ordering of values, tallying across several stores,
+several short ranges packed into one wavefront, approximate (k-error) grouping of values.
 """
 from __future__ import annotations
 
@@ -91,6 +100,70 @@ class Lines:
     flags: torch.Tensor          # uint8 [L]  HMSE_LINES_START_CUT | HMSE_LINES_END_CUT (of any of the extent's occurrences)
     hits: torch.Tensor           # int64 [L]  occurrences of the pattern that fell into this extent
     counts: torch.Tensor         # int64 [P]  extents per pattern (with before = after = 0 and no cut: matching lines, grep -c)
+
+
+@dataclass
+class Tally:
+    ptr: torch.Tensor            # int64 [G + 1]: group j's values are [ptr[j] : ptr[j + 1]), count descending, then start, then index
+    start: torch.Tensor          # int64 [D] the representative occurrence of each value: the member with the smallest (start, index)
+    end: torch.Tensor            # int64 [D]
+    count: torch.Tensor          # int64 [D] ranges per value
+    distinct: torch.Tensor       # int64 [G] distinct values per group, before `top`
+    total: torch.Tensor          # int64 [G] ranges per group
+    value_of: torch.Tensor       # int64 [n] aligned with the input: the index of each occurrence's value, -1 where `top` cut it
+    rounds: int = 0              # key / compare rounds the grouping took (1 unless keys collided)
+
+
+def tally_ranges(start, end, group, n_groups: int, keys, same, top=None, max_rounds: int = 64) -> Tally:
+    """The grouping of StoreFinder.tally over any tensors' device (tests run it on CPU tensors with plain-Python stand-ins):
+    `keys(start, end, seed)` -> int64 keys and `same(start, end, rep)` -> 0 / 1 per range are the two ops calls.  Torch plumbing only,
+    no host loop over the occurrences.  U, the unresolved ranges, stays ordered by (start, index); a round keys U under seed = round,
+    stable-sorts it by (group, key), so that the first member of every run is the run's smallest-start member, compares every member
+    with it and resolves those that equal it.  Every round resolves at least the first member of every bucket; RuntimeError naming the
+    figures when more than max_rounds would be needed."""
+    n, dev = start.numel(), start.device
+    ar = lambda k: torch.arange(k, dtype=torch.int64, device=dev)
+    value_rep = torch.full((n,), -1, dtype=torch.int64, device=dev)                 # per range: the index of its value's representative
+    U = torch.sort(start, stable=True)[1]
+    rounds = 0
+    while U.numel():
+        if rounds >= int(max_rounds):
+            raise RuntimeError(f"tally: {U.numel()} of {n} ranges are unresolved after max_rounds = {max_rounds} rounds "
+                               f"({int((value_rep == ar(n)).sum())} distinct values so far)")
+        s, e, g = start[U].contiguous(), end[U].contiguous(), group[U]
+        k = keys(s, e, rounds)
+        o = torch.sort(k, stable=True)[1]                                        # by (group, key): two stable sorts
+        o = o[torch.sort(g[o], stable=True)[1]]
+        ks, gs = k[o], g[o]
+        new = torch.ones(o.numel(), dtype=torch.bool, device=dev)
+        new[1:] = (ks[1:] != ks[:-1]) | (gs[1:] != gs[:-1])
+        first = torch.nonzero(new).reshape(-1)
+        rep = torch.empty_like(o)
+        rep[o] = o[first[torch.cumsum(new, 0) - 1]]                              # every run's first member, broadcast
+        sm = same(s, e, rep) != 0
+        value_rep[U[sm]] = U[rep[sm]]
+        U = U[~sm]
+        rounds += 1
+    # the values: the ranges that represent themselves, ordered by (group, count descending, start, index)
+    reps = torch.nonzero(value_rep == ar(n)).reshape(-1)
+    cnt = torch.bincount(value_rep, minlength=n)[reps] if n else reps
+    o = torch.sort(start[reps], stable=True)[1]
+    o = o[torch.sort(cnt[o], stable=True, descending=True)[1]]
+    o = o[torch.sort(group[reps][o], stable=True)[1]]
+    reps, cnt = reps[o], cnt[o]
+    g = group[reps]
+    distinct = torch.bincount(g, minlength=n_groups)
+    total = torch.bincount(group, minlength=n_groups)
+    if top is not None:
+        first_of = torch.zeros(n_groups + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(distinct, 0, out=first_of[1:])
+        keep = ar(reps.numel()) - first_of[g] < int(top)                         # the rank inside the group
+        reps, cnt, g = reps[keep], cnt[keep], g[keep]
+    ptr = torch.zeros(n_groups + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(g, minlength=n_groups), 0, out=ptr[1:])
+    index_of = torch.full((n + 1,), -1, dtype=torch.int64, device=dev)
+    index_of[reps] = ar(reps.numel())
+    return Tally(ptr, start[reps], end[reps], cnt, distinct, total, index_of[value_rep], rounds)
 
 
 # Something that can be searched for — a group of at most 32 patterns, a PatternSet's long entries, one Regex: its scan and seams calls
@@ -386,14 +459,14 @@ class StoreFinder:
 
     def text(self, lines, max_bytes: int = 1 << 30):
         """The bytes of every extent back to back -> (uint8 tensor, int64 off[L + 1]: extent i is bytes[off[i] : off[i + 1]]).  `lines`:
-        a Lines, or a (start, end) pair of int64 device tensors (any ranges of the corpus; they may overlap and be empty).  One
-        hmse_lines_gather call.  ValueError naming the total if it exceeds max_bytes."""
-        if isinstance(lines, Lines):
+        a Lines, a Tally (the representative occurrence of every value) or a (start, end) pair of int64 device tensors (any ranges of
+        the corpus; they may overlap and be empty).  One hmse_lines_gather call.  ValueError naming the total if it exceeds max_bytes."""
+        if isinstance(lines, (Lines, Tally)):                                    # (a Tally: the representative occurrence of every value)
             start, end = lines.start, lines.end
         elif isinstance(lines, (tuple, list)) and len(lines) == 2 and all(isinstance(t, torch.Tensor) for t in lines):
             start, end = (t.reshape(-1) for t in lines)
         else:
-            raise ValueError(f"text: lines is a Lines or a (start, end) pair of tensors, got a {type(lines).__name__}")
+            raise ValueError(f"text: lines is a Lines or a (start, end) pair of tensors (or a Tally: its representatives), got a {type(lines).__name__}")
         if start.dtype != torch.int64 or end.dtype != torch.int64 or start.numel() != end.numel() or start.device != end.device or start.device != self.raw.device:
             raise ValueError(f"text: start and end are int64 tensors of one length on the finder's device {self.raw.device}")
         n, dev = start.numel(), self.dev
@@ -413,6 +486,54 @@ class StoreFinder:
         """lines(find(patterns, ignore_case, max_hits), delim, before, after, reach): per pattern the lines that hold it."""
         _lines_args(delim, before, after, reach)
         return self.lines(self.find(patterns, ignore_case, max_hits), delim, before, after, reach)
+
+    # ------------------------------------------------------------------ from ranges to the values they cover
+    def tally(self, what, ignore_case: bool = False, top=None, max_rounds: int = 64, _key_bits: int = 64) -> Tally:
+        """Per group the distinct texts among the ranges, with counts and a representative occurrence (module docstring;
+        include/hmse_tally.h).  `what`: a RegexFound (offsets and lengths, one group per regex), a Lines (each extent counts once, one
+        group per pattern), a (start, end) pair of int64 device tensors taken as one group, or a (start, end, ptr) triple with group
+        j's ranges at [ptr[j] : ptr[j + 1]).  top = k keeps the k most frequent values of every group.  One hmse_tally_keys and one
+        hmse_tally_same call per round (one round unless 64-bit keys collide; _key_bits is for tests); the grouping is torch sorts.
+        ValueError for a plain Found or ApproxFound (they carry no lengths: use spans() or pass a (start, end) pair), a top below 1,
+        ranges that descend or leave the corpus; RuntimeError when max_rounds rounds do not resolve every range."""
+        dev = self.dev
+        if top is not None and int(top) < 1:
+            raise ValueError(f"tally: top = {top} must be at least 1 (None keeps every value)")
+        if isinstance(what, RegexFound):
+            start, end, ptr = what.offsets, what.offsets + what.lengths, what.ptr
+        elif isinstance(what, Lines):
+            start, end, ptr = what.start, what.end, what.ptr
+        elif isinstance(what, Found):
+            raise ValueError(f"tally: what is a {type(what).__name__}, which has offsets but no lengths; tally takes a RegexFound, a Lines, the (start, end) of "
+                             "spans(), or any (start, end) pair of tensors")
+        elif isinstance(what, (tuple, list)) and len(what) in (2, 3) and all(isinstance(t, torch.Tensor) for t in what):
+            start, end = (t.reshape(-1) for t in what[:2])
+            ptr = what[2].reshape(-1) if len(what) == 3 else None
+        else:
+            raise ValueError(f"tally: what is a RegexFound, a Lines, a (start, end) pair or a (start, end, ptr) triple of tensors, got a {type(what).__name__}")
+        if any(t.dtype != torch.int64 or t.device != self.raw.device for t in (start, end) + (() if ptr is None else (ptr,))) or start.numel() != end.numel():
+            raise ValueError(f"tally: start, end and ptr are int64 tensors on the finder's device {self.raw.device}, start and end of one length")
+        n = start.numel()
+        if ptr is None:
+            ptr = torch.tensor([0, n], dtype=torch.int64, device=dev)
+        G = ptr.numel() - 1
+        per = ptr[1:] - ptr[:-1]
+        if G < 0 or (G == 0 and n) or (G > 0 and (int(ptr[0]) != 0 or int(ptr[-1]) != n or bool((per < 0).any()))):
+            raise ValueError(f"tally: ptr does not split the {n} ranges into groups (it ascends from 0 to {n})")
+        z = lambda k: torch.zeros(k, dtype=torch.int64, device=dev)
+        if n == 0 or G == 0:
+            return Tally(z(max(G, 0) + 1), z(0), z(0), z(0), z(max(G, 0)), z(max(G, 0)), z(0), 0)
+        if bool(((start < 0) | (end < start) | (end > self.n_bytes)).any()):
+            raise ValueError(f"tally: a range descends or leaves the corpus of n_bytes = {self.n_bytes}")
+        group = torch.repeat_interleave(torch.arange(G, dtype=torch.int64, device=dev), per)
+        keys = lambda s, e, seed: ops.tally_keys(self.raw, self.raw_off, self.cuts, self.slot, s, e, ignore_case, seed, _key_bits)
+        same = lambda s, e, rep: ops.tally_same(self.raw, self.raw_off, self.cuts, self.slot, s, e, rep, ignore_case)
+        return tally_ranges(start.contiguous(), end.contiguous(), group, G, keys, same, top, max_rounds)
+
+    def tally_regex(self, rx, ignore_case: bool = False, top=None, max_hits: int = 1 << 24) -> Tally:
+        """tally(nonoverlapping(find_regex(rx, max_hits)), ignore_case, top): per regex the values its leftmost-longest matches took,
+        most frequent first (grep -o RX | sort | uniq -c | sort -rn).  ignore_case folds the VALUES; how the regex matches is the Regex's own."""
+        return self.tally(nonoverlapping(self.find_regex(rx, max_hits)), ignore_case, top)
 
     # ------------------------------------------------------------------ a whole dictionary in one pass
     def _set_of(self, pset: PatternSet):
@@ -666,6 +787,11 @@ def grep_approx(store, patterns, k, device, ignore_case: bool = False, delim: by
 def find_regex(store, rx, device, max_hits: int = 1 << 24, verify: bool = True) -> RegexFound:
     """One-off form of StoreFinder(store, device, verify).find_regex(rx, max_hits)."""
     return StoreFinder(store, device, verify).find_regex(rx, max_hits)
+
+
+def tally_regex(store, rx, device, ignore_case: bool = False, top=None, max_hits: int = 1 << 24, verify: bool = True) -> Tally:
+    """One-off form of StoreFinder(store, device, verify).tally_regex(rx, ignore_case, top, max_hits)."""
+    return StoreFinder(store, device, verify).tally_regex(rx, ignore_case, top, max_hits)
 
 
 def grep_regex(store, rx, device, delim: bytes = b"\n", before: int = 0, after: int = 0, reach: int = 1 << 16, max_hits: int = 1 << 24,

@@ -82,7 +82,7 @@ def _call(name: str, *args) -> None:
     address (NULL when it is empty and the table says `?`); None is NULL; an int is a raw address.  An IngestConfig, a StreamArrays (whatever holds
     its struct as `.c`) or a mirror struct goes by reference; a host array as it is; a scalar as int().  A non-zero return raises HmseError (an _ex entry point
     under the name of the one it extends)."""
-    params = (_lib.PARSED.get(name) or _lib.PARSED_REGEXA[name])[1]
+    params = (_lib.PARSED.get(name) or _lib.PARSED_REGEXA.get(name) or _lib.PARSED_TALLY[name])[1]
     if len(args) != len(params) - 1:
         raise TypeError(f"{name} takes {len(params) - 1} arguments and the stream, got {len(args)}")
     out = list(args)
@@ -809,6 +809,46 @@ def lines_gather(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, s
                              "or out_off is not the prefix sum of the lengths"),
                      (_ANY, -2, "hmse_lines_gather device status {st:#x}: out_off[-1] exceeds the output")))
     return out[:int(n_out)]
+
+
+_BAD_TALLY = ((2, -1, "{where} device status {st:#x}: inconsistent tables, a range that descends or leaves the corpus, or a rep outside the ranges"),)
+
+
+def _tally_ranges(where: str, raw, raw_off, cuts, slot, start, end, **more) -> int:
+    _lines_tables(where, raw, raw_off, cuts, slot, start=start, end=end, **more)
+    n = start.numel()
+    if any(t.numel() != n for t in (end, *more.values())):
+        raise HmseError(-1, f"{where}: start / end{''.join(' / ' + k for k in more)} do not match")
+    return n
+
+
+def tally_keys(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, start: torch.Tensor, end: torch.Tensor,
+               ignore_case: bool = False, seed: int = 0, key_bits: int = 64) -> torch.Tensor:
+    """hmse_tally_keys: the key of the (folded) corpus bytes [start[i], end[i]) of every range (include/hmse_tally.h defines it bit for
+    bit).  The tables are lines_gather's; int64 tensors carry the u64 bits.  -> key int64[n].  The key only buckets ranges: tally_same
+    decides equality.  HmseError for inconsistent tables or a range that descends or leaves the corpus (status bit 1)."""
+    n = _tally_ranges("tally_keys", raw, raw_off, cuts, slot, start, end)
+    if not 1 <= int(key_bits) <= 64:
+        raise HmseError(-1, f"tally_keys: key_bits = {key_bits} lies outside 1..64")
+    key = _buf(n, torch.int64, cuts.device)
+    status = _status_word(cuts.device)
+    _call("hmse_tally_keys", raw, raw.numel(), raw_off, raw_off.numel() - 1, cuts, slot, slot.numel(), start, end, n,
+          FIND_IGNORE_CASE if ignore_case else 0, int(seed) & 0xFFFFFFFFFFFFFFFF, key_bits, key, status)
+    _refuse(status, _BAD_TALLY, "hmse_tally_keys")
+    return key
+
+
+def tally_same(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, start: torch.Tensor, end: torch.Tensor,
+               rep: torch.Tensor, ignore_case: bool = False) -> torch.Tensor:
+    """hmse_tally_same: same[i] = 1 iff the ranges i and rep[i] have the same length and the same (folded) bytes.  -> uint8[n].
+    HmseError for inconsistent tables, a range that descends or leaves the corpus, or a rep[i] outside [0, n) (status bit 1)."""
+    n = _tally_ranges("tally_same", raw, raw_off, cuts, slot, start, end, rep=rep)
+    same = _buf(n, torch.uint8, cuts.device)
+    status = _status_word(cuts.device)
+    _call("hmse_tally_same", raw, raw.numel(), raw_off, raw_off.numel() - 1, cuts, slot, slot.numel(), start, end, rep, n,
+          FIND_IGNORE_CASE if ignore_case else 0, same, status)
+    _refuse(status, _BAD_TALLY, "hmse_tally_same")
+    return same
 
 
 @dataclass
