@@ -1,6 +1,7 @@
 """Run by tests/test_gpu_parity.py in a child process with HMSE_ENC_FORCE_SPILL=1 (the library reads the variable once): every FULL
 record then takes the encode kernel's spill path — finished windows of the bit image go to the global scratch and move into the
-record's slot when the last token has been read — and every stream must still equal the oracle's."""
+record's slot when the last token has been read — and every stream must still equal the oracle's.  The inputs of tests/encoder_shapes.py
+(repaired trees, every code-length RLE remainder, ties between the block types) go the same way in a call of their own."""
 import os
 import sys
 
@@ -12,6 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import oracle as orc   # noqa: E402  (test infrastructure)
 from hmse_amd import IngestConfig, ops   # noqa: E402
 from conftest import words_text   # noqa: E402
+import encoder_shapes   # noqa: E402
 from test_gpu_parity import ocfg   # noqa: E402
 
 assert os.environ.get("HMSE_ENC_FORCE_SPILL") == "1"
@@ -39,4 +41,9 @@ for _ in range(2):
     assert np.array_equal(out.cpu().numpy(), want_out)
 sizes = np.diff(want_off.astype(np.int64))
 assert (sizes > 8192).sum() >= 4
+s_data, s_cuts, s_base, s_names = encoder_shapes.batch()
+want = orc.deflate_chunks(s_data, s_cuts, ocfg(orc, cfg), None, s_base)
+out, off, kind = ops.l1_deflate(torch.from_numpy(s_data).to(dev), torch.from_numpy(s_cuts.astype(np.int64)).to(dev), cfg, None, torch.from_numpy(s_base).to(dev))
+assert np.array_equal(off.cpu().numpy().astype(np.uint64), want[1]) and np.array_equal(kind.cpu().numpy(), want[2])
+assert np.array_equal(out.cpu().numpy(), want[0])
 print(f"spill path OK: {len(parts)} records, {int((sizes > 4096).sum())} of them longer than one window")

@@ -276,7 +276,9 @@ def test_deflate_c_oracle_equals_python_restatement(orc):
         for t in (20, 40, 48, 52, 56, 64, 90):
             c = body.copy(); c[L - t:] = c[:t]
             cases.append(c.tobytes())
-    # skewed frequencies: Fibonacci-like counts force depths beyond the 15-bit (and 7-bit code-length) limits -> Kraft repair
+    # skewed frequencies: Fibonacci-like counts, shuffled.  This input does NOT reach the Kraft repair: it parses to 3 744 tokens, 1 480
+    # of them matches, and its unclamped depths are 11 (literal/length), 10 (distance) and 6 (code-length) — a deep, unclamped tree is
+    # all it adds.  Depths beyond 15 and 7 and the repair of each tree: tests/encoder_shapes.py, tests/test_encoder_shapes_host.py
     fib, skew = [1, 1], bytearray()
     while len(fib) < 22:
         fib.append(fib[-1] + fib[-2])
