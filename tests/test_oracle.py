@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import words_text
+from grid_caps import mutate  # noqa: F401  (the helper module holds it; tests/test_gpu_read.py and test_gpu_arguments_only.py take it from here)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FIX = json.load(open(os.path.join(HERE, "golden", "fixtures.json")))
@@ -442,18 +443,6 @@ def _zlib_streams():
                     yield t, zd, c.compress(t[:len(t) // 2]) + c.flush(zlib.Z_FULL_FLUSH) + c.compress(t[len(t) // 2:]) + c.flush()
 
 
-def mutate(stream: bytes, rnd) -> bytes:
-    m = bytearray(stream)
-    k = rnd.random()
-    if k < 0.5 and m:
-        m[rnd.randrange(min(len(m), 40))] ^= 1 << rnd.randrange(8)   # headers and code-length sets live up front
-    elif k < 0.7 and m:
-        m[rnd.randrange(len(m))] ^= 1 << rnd.randrange(8)
-    elif k < 0.85:
-        m = m[:rnd.randrange(len(m) + 1)]
-    else:
-        m += b"\0"
-    return bytes(m)
 
 
 def test_inflate_equals_zlib_on_valid_streams(orc):
