@@ -17,6 +17,7 @@ CORPUS_LIB_PATH = os.path.join(_CSRC, "libhmse_corpus.so")
 GUNZIP_LIB_PATH = os.path.join(_CSRC, "libhmse_gunzip.so")     # include/hmse_gunzip.h: the gzip import, beside the C ABI of include/hmse.h
 REGEXA_LIB_PATH = os.path.join(_CSRC, "libhmse_regexa.so")     # include/hmse_regexa.h: the regex search with assertions, likewise
 TALLY_LIB_PATH = os.path.join(_CSRC, "libhmse_tally.so")       # include/hmse_tally.h: the tally of search results, likewise
+SUBST_LIB_PATH = os.path.join(_CSRC, "libhmse_subst.so")       # include/hmse_subst.h: the substitution of ranges, likewise
 
 
 class HmseCfg(C.Structure):
@@ -218,6 +219,12 @@ TALLY_SIGNATURES = {
     "hmse_tally_same": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, u64*? start, u64*? end, u64*? rep, "
                        "u64 n, u32 flags, u8*? same, u32* status, stream",
 }
+# The entry point of include/hmse_subst.h (the substitution of ranges, csrc/libhmse_subst.so); tests/test_subst_host.py holds this table
+# against that header.  Parsed into a table of its own (PARSED_SUBST); ops._call looks a name up there last.
+SUBST_SIGNATURES = {
+    "hmse_subst_apply": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, u64*? start, u64*? end, u64*? sel, "
+                        "u64 n, u8*? rep, u64 rep_bytes, u64*? rep_off, u64 n_rep, u32 flags, u64* out_off, u8*? out, u64 out_cap, u32* status, stream",
+}
 
 _ELEM = {"u8": C.c_uint8, "u32": C.c_uint32, "i32": C.c_int32, "u64": C.c_uint64, "i64": C.c_int64, "f64": C.c_double}
 _SCALAR = {"u32": C.c_uint32, "u64": C.c_uint64, "size_t": C.c_size_t, "int": C.c_int}
@@ -257,6 +264,7 @@ def _parse(sig: str):
 PARSED = {name: _parse(sig) for name, sig in {**SIGNATURES, **GUNZIP_SIGNATURES}.items()}      # name -> (restype, parameters)
 PARSED_REGEXA = {name: _parse(sig) for name, sig in REGEXA_SIGNATURES.items()}
 PARSED_TALLY = {name: _parse(sig) for name, sig in TALLY_SIGNATURES.items()}
+PARSED_SUBST = {name: _parse(sig) for name, sig in SUBST_SIGNATURES.items()}
 
 _hip = None
 _corpus = None
@@ -295,6 +303,13 @@ def hip_lib():
         L._tally = T = C.CDLL(TALLY_LIB_PATH)            # (it links against libhmse_hip.so as well)
         for name, (restype, params) in PARSED_TALLY.items():
             fn = getattr(T, name)
+            fn.restype, fn.argtypes = restype, [p.ctype for p in params]
+            setattr(L, name, fn)
+        if not os.path.exists(SUBST_LIB_PATH):
+            raise ImportError(f"{SUBST_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        L._subst = S = C.CDLL(SUBST_LIB_PATH)            # (it links against libhmse_hip.so as well)
+        for name, (restype, params) in PARSED_SUBST.items():
+            fn = getattr(S, name)
             fn.restype, fn.argtypes = restype, [p.ctype for p in params]
             setattr(L, name, fn)
         _hip = L

@@ -54,6 +54,14 @@ first member byte for byte (hmse_tally_same): a key that merely agrees proves no
 waits for the next round under another seed.  tally_regex = tally(nonoverlapping(find_regex(rx))).  Out of scope: texts compared under
 anything but byte or ASCII-folded equality, weighting occurrences, lexicographic ordering of values, tallying across several stores,
 several short ranges packed into one wavefront, approximate (k-error) grouping of values.
+
+Substitute: StoreFinder.substitute writes the corpus with the ranges of a RegexFound, a Lines or any (start, end) pair replaced
+(sed 's/RX/repl/g'), StoreFinder.redact overwrites them with one byte so that lengths and offsets stay; the result, a Substituted, holds
+the edited corpus in HBM as ingest.ingest_shard takes it (hmse_amd/csrc/subst.hip; include/hmse_subst.h has the definitions,
+tests/subst_ref.py restates them in plain Python).  The groups' ranges are merged by a stable sort on start and checked here; the one
+hmse_subst_apply call proves them again, and the out_off it is given, before it writes a byte.  substitute_regex =
+substitute(nonoverlapping(find_regex(rx))).  Out of scope: captures and back-references, `&` (the whole match inside a replacement),
+case-preserving replacement, editing the store's records in place without re-ingest, several stores, fill patterns longer than one byte.
 """
 from __future__ import annotations
 
@@ -112,6 +120,31 @@ class Tally:
     total: torch.Tensor          # int64 [G] ranges per group
     value_of: torch.Tensor       # int64 [n] aligned with the input: the index of each occurrence's value, -1 where `top` cut it
     rounds: int = 0              # key / compare rounds the grouping took (1 unless keys collided)
+
+
+@dataclass
+class Substituted:
+    data: torch.Tensor           # uint8 [n_bytes_out] in HBM: the edited corpus; ingest.ingest_shard(data, cfg) takes it as it is
+    start: torch.Tensor          # int64 [n_edits] the merged edits, ascending: corpus[start[i] : end[i]) was replaced
+    end: torch.Tensor            # int64 [n_edits]
+    sel: torch.Tensor            # int64 [n_edits] the replacement (the group) of every edit
+    out_off: torch.Tensor        # int64 [n_edits + 1]: edit i's replacement begins at data[out_off[i]]; out_off[-1] = n_bytes_out
+    n_edits: int
+    n_bytes_in: int
+    n_bytes_out: int
+
+    def translate(self, offsets: torch.Tensor) -> torch.Tensor:
+        """Corpus offsets (int64, 0..n_bytes_in, on the edits' device) -> offsets into `data`: a kept byte goes where it was written, an
+        offset inside a replaced range to the start of its replacement, n_bytes_in to n_bytes_out.  searchsorted plumbing, no kernel."""
+        if offsets.dtype != torch.int64 or offsets.device != self.start.device:
+            raise ValueError(f"translate: offsets are int64 on the edits' device {self.start.device}, got {offsets.dtype} on {offsets.device}")
+        q = offsets.reshape(-1)
+        if q.numel() and (int(q.min()) < 0 or int(q.max()) > self.n_bytes_in):
+            raise ValueError(f"translate: an offset lies outside 0..n_bytes_in = {self.n_bytes_in}")
+        tail = torch.tensor([self.n_bytes_in], dtype=torch.int64, device=q.device)
+        shift = self.out_off - torch.cat([self.start, tail])                     # of the kept bytes in front of edit c (behind the last: c = n)
+        c = torch.searchsorted(self.end, q, right=True)                          # the edits that end at or in front of q lie in front of it
+        return torch.minimum(q + shift[c], self.out_off[c]).reshape(offsets.shape)
 
 
 def tally_ranges(start, end, group, n_groups: int, keys, same, top=None, max_rounds: int = 64) -> Tally:
@@ -535,6 +568,101 @@ class StoreFinder:
         most frequent first (grep -o RX | sort | uniq -c | sort -rn).  ignore_case folds the VALUES; how the regex matches is the Regex's own."""
         return self.tally(nonoverlapping(self.find_regex(rx, max_hits)), ignore_case, top)
 
+    # ------------------------------------------------------------------ from ranges to the corpus without them
+    def _edits(self, where: str, what, repl, fill: bool):
+        """-> (start, end, sel, rep, rep_off) of substitute / redact: the groups' ranges merged by a stable sort on start, each edit's
+        replacement the one of its group.  Every refusal comes in front of every launch."""
+        dev = self.dev
+        if isinstance(what, RegexFound):
+            start, end, ptr = what.offsets, what.offsets + what.lengths, what.ptr
+        elif isinstance(what, Lines):
+            start, end, ptr = what.start, what.end, what.ptr
+        elif isinstance(what, Found):
+            raise ValueError(f"{where}: what is a {type(what).__name__}, which has offsets but no lengths; {where} takes a RegexFound, a Lines, the (start, end) of "
+                             "spans(), or any (start, end) pair of tensors")
+        elif isinstance(what, (tuple, list)) and len(what) in (2, 3) and all(isinstance(t, torch.Tensor) for t in what):
+            start, end = (t.reshape(-1) for t in what[:2])
+            ptr = what[2].reshape(-1) if len(what) == 3 else None
+        else:
+            raise ValueError(f"{where}: what is a RegexFound, a Lines, a (start, end) pair or a (start, end, ptr) triple of tensors, got a {type(what).__name__}")
+        if any(t.dtype != torch.int64 or t.device != self.raw.device for t in (start, end) + (() if ptr is None else (ptr,))) or start.numel() != end.numel():
+            raise ValueError(f"{where}: start, end and ptr are int64 tensors on the finder's device {self.raw.device}, start and end of one length")
+        n = start.numel()
+        if ptr is None:
+            ptr = torch.tensor([0, n], dtype=torch.int64, device=dev)
+        G = ptr.numel() - 1
+        per = ptr[1:] - ptr[:-1]
+        if G < 0 or (G == 0 and n) or (G > 0 and (int(ptr[0]) != 0 or int(ptr[-1]) != n or bool((per < 0).any()))):
+            raise ValueError(f"{where}: ptr does not split the {n} ranges into groups (it ascends from 0 to {n})")
+        name = "fill" if fill else "repl"
+        if isinstance(repl, (bytes, bytearray)):
+            reps, one = [bytes(repl)], True
+        elif isinstance(repl, (tuple, list)) and all(isinstance(r, (bytes, bytearray)) for r in repl):
+            reps, one = [bytes(r) for r in repl], False
+            if len(reps) != G:
+                raise ValueError(f"{where}: {name} has {len(reps)} entries, what has {G} groups (one bytes for all, or one per group)")
+        else:
+            raise ValueError(f"{where}: {name} is bytes, or a sequence with one bytes per group, got a {type(repl).__name__}")
+        if fill and any(len(r) != 1 for r in reps):
+            raise ValueError(f"{where}: fill is one byte (or one byte per group), got lengths {[len(r) for r in reps]}")
+        if n and bool(((start < 0) | (end < start) | (end > self.n_bytes)).any()):
+            raise ValueError(f"{where}: a range descends or leaves the corpus of n_bytes = {self.n_bytes}")
+        if one or G == 0:
+            sel = torch.zeros(n, dtype=torch.int64, device=dev)
+        else:
+            sel = torch.repeat_interleave(torch.arange(G, dtype=torch.int64, device=dev), per)
+        order = torch.sort(start, stable=True)[1]
+        start, end, sel = start[order].contiguous(), end[order].contiguous(), sel[order].contiguous()
+        if n > 1 and bool((start[1:] < end[:-1]).any()):
+            raise ValueError(f"{where}: ranges overlap (within a group or between groups); edits may touch, they may not overlap")
+        lens = [len(r) for r in reps]
+        rep = torch.from_numpy(np.frombuffer(b"".join(reps), dtype=np.uint8).copy()).to(dev)
+        rep_off = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)).to(dev)
+        return start, end, sel, rep, rep_off
+
+    def _substitute(self, where: str, what, repl, fill: bool, max_bytes: int) -> Substituted:
+        start, end, sel, rep, rep_off = self._edits(where, what, repl, fill)
+        n, dev = start.numel(), self.dev
+        out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        if fill or n == 0:
+            out_off[:n] = start
+            out_off[n] = self.n_bytes
+        else:                                                                    # out_off[i] = start[i] + sum_{j < i} (|R_j| - (end[j] - start[j]))
+            grow = (rep_off[1:] - rep_off[:-1])[sel] - (end - start)
+            torch.cumsum(grow, 0, out=out_off[1:])
+            out_off[:n] += start
+            out_off[n] += self.n_bytes
+        total = int(out_off[-1]) if n else self.n_bytes
+        if total > int(max_bytes):
+            raise ValueError(f"{where}: the output holds {total} bytes, which exceeds max_bytes = {max_bytes}")
+        data = ops.subst_apply(self.raw, self.raw_off, self.cuts, self.slot, start, end, sel, rep, rep_off, out_off, total, fill)
+        return Substituted(data, start, end, sel, out_off, n, self.n_bytes, total)
+
+    def substitute(self, what, repl, max_bytes: int = 1 << 34) -> Substituted:
+        """The corpus with every range of `what` replaced (sed 's/RX/repl/g' once the ranges are a regex's; include/hmse_subst.h has the
+        definitions).  `what`: a RegexFound (one group per regex), a Lines, a (start, end) pair of int64 device tensors taken as one
+        group, or a (start, end, ptr) triple with group j's ranges at [ptr[j] : ptr[j + 1]).  `repl`: bytes, one for all, or a sequence
+        with one bytes per group; empty deletes.  The groups' ranges are merged by a stable sort on start: empty ranges insert, several
+        at one position in the order given.  One hmse_subst_apply call writes the output in HBM; ingest.ingest_shard takes
+        `.data` as it is.  No edits gives the corpus itself.  ValueError in front of every launch for a plain Found or ApproxFound
+        (they carry no lengths: use spans()), ranges that overlap (within or between groups; they may touch), descend or leave the
+        corpus, a repl that does not match the groups, an output above max_bytes."""
+        return self._substitute("substitute", what, repl, False, max_bytes)
+
+    def redact(self, what, fill: bytes = b"*", max_bytes: int = 1 << 34) -> Substituted:
+        """substitute in fill mode: every byte of every range becomes the fill byte (one byte, or one per group), so lengths and offsets
+        are preserved: n_bytes_out == n_bytes_in."""
+        return self._substitute("redact", what, fill, True, max_bytes)
+
+    def substitute_regex(self, rx, repl, max_hits: int = 1 << 24, max_bytes: int = 1 << 34) -> Substituted:
+        """substitute(nonoverlapping(find_regex(rx, max_hits)), repl): per regex its leftmost-longest matches replaced, like
+        sed -E 's/RX/repl/g'.  Matches of different regexes that overlap raise ValueError."""
+        return self.substitute(nonoverlapping(self.find_regex(rx, max_hits)), repl, max_bytes)
+
+    def redact_regex(self, rx, fill: bytes = b"*", max_hits: int = 1 << 24, max_bytes: int = 1 << 34) -> Substituted:
+        """redact(nonoverlapping(find_regex(rx, max_hits)), fill): every byte of every match becomes the fill byte."""
+        return self.redact(nonoverlapping(self.find_regex(rx, max_hits)), fill, max_bytes)
+
     # ------------------------------------------------------------------ a whole dictionary in one pass
     def _set_of(self, pset: PatternSet):
         if not isinstance(pset, PatternSet):
@@ -792,6 +920,16 @@ def find_regex(store, rx, device, max_hits: int = 1 << 24, verify: bool = True) 
 def tally_regex(store, rx, device, ignore_case: bool = False, top=None, max_hits: int = 1 << 24, verify: bool = True) -> Tally:
     """One-off form of StoreFinder(store, device, verify).tally_regex(rx, ignore_case, top, max_hits)."""
     return StoreFinder(store, device, verify).tally_regex(rx, ignore_case, top, max_hits)
+
+
+def substitute_regex(store, rx, repl, device, max_hits: int = 1 << 24, max_bytes: int = 1 << 34, verify: bool = True) -> Substituted:
+    """One-off form of StoreFinder(store, device, verify).substitute_regex(rx, repl, max_hits, max_bytes)."""
+    return StoreFinder(store, device, verify).substitute_regex(rx, repl, max_hits, max_bytes)
+
+
+def redact_regex(store, rx, device, fill: bytes = b"*", max_hits: int = 1 << 24, max_bytes: int = 1 << 34, verify: bool = True) -> Substituted:
+    """One-off form of StoreFinder(store, device, verify).redact_regex(rx, fill, max_hits, max_bytes)."""
+    return StoreFinder(store, device, verify).redact_regex(rx, fill, max_hits, max_bytes)
 
 
 def grep_regex(store, rx, device, delim: bytes = b"\n", before: int = 0, after: int = 0, reach: int = 1 << 16, max_hits: int = 1 << 24,

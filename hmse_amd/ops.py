@@ -82,7 +82,7 @@ def _call(name: str, *args) -> None:
     address (NULL when it is empty and the table says `?`); None is NULL; an int is a raw address.  An IngestConfig, a StreamArrays (whatever holds
     its struct as `.c`) or a mirror struct goes by reference; a host array as it is; a scalar as int().  A non-zero return raises HmseError (an _ex entry point
     under the name of the one it extends)."""
-    params = (_lib.PARSED.get(name) or _lib.PARSED_REGEXA.get(name) or _lib.PARSED_TALLY[name])[1]
+    params = (_lib.PARSED.get(name) or _lib.PARSED_REGEXA.get(name) or _lib.PARSED_TALLY.get(name) or _lib.PARSED_SUBST[name])[1]
     if len(args) != len(params) - 1:
         raise TypeError(f"{name} takes {len(params) - 1} arguments and the stream, got {len(args)}")
     out = list(args)
@@ -849,6 +849,36 @@ def tally_same(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slo
           FIND_IGNORE_CASE if ignore_case else 0, same, status)
     _refuse(status, _BAD_TALLY, "hmse_tally_same")
     return same
+
+
+SUBST_LITERAL, SUBST_FILL = 0, 1
+
+
+def subst_apply(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, start: torch.Tensor, end: torch.Tensor,
+                sel: torch.Tensor, rep: torch.Tensor, rep_off: torch.Tensor, out_off: torch.Tensor, n_out: int, fill: bool = False) -> torch.Tensor:
+    """hmse_subst_apply: the corpus with the ranges [start[i], end[i]) replaced (include/hmse_subst.h has the definitions).  The edits are in
+    order and do not overlap; `sel` int64[n] names each edit's replacement among the packed `rep` uint8 / `rep_off` int64[n_rep + 1]; with
+    `fill` every replacement is one byte, repeated over its range.  `out_off` int64[n + 1]: where each replacement begins in the output,
+    and the output's length; n_out = out_off[-1].  The tables are lines_gather's.  -> uint8[n_out].  HmseError for an out_off[-1] above
+    n_out (status bit 0) and for inconsistent tables, edits that break the edit rule, a sel outside the replacements, a bad rep_off, a
+    fill replacement that is not one byte or an out_off that is not the definition's (bit 1); not one byte was written then."""
+    _lines_tables("subst_apply", raw, raw_off, cuts, slot, start=start, end=end, sel=sel, rep_off=rep_off, out_off=out_off)
+    if rep.dtype != torch.uint8:
+        raise HmseError(-1, "subst_apply: rep must be torch.uint8")
+    n = start.numel()
+    if end.numel() != n or sel.numel() != n or out_off.numel() != n + 1 or rep_off.numel() < 1:
+        raise HmseError(-1, "subst_apply: start / end / sel / out_off / rep_off do not match")
+    n_rep = rep_off.numel() - 1
+    if n and not n_rep:
+        raise HmseError(-1, "subst_apply: there are edits and no replacement")
+    out = _buf(max(int(n_out), 1), torch.uint8, cuts.device)
+    status = _status_word(cuts.device)
+    _call("hmse_subst_apply", raw, raw.numel(), raw_off, raw_off.numel() - 1, cuts, slot, slot.numel(), start, end, sel, n, rep, rep.numel(),
+          rep_off if n_rep else None, n_rep, SUBST_FILL if fill else SUBST_LITERAL, out_off, out if n_out else None, n_out, status)
+    _refuse(status, ((2, -1, "hmse_subst_apply device status {st:#x}: inconsistent tables, edits that overlap, descend or leave the corpus, a sel "
+                             "outside the replacements, a bad rep_off, a fill replacement that is not one byte, or an out_off that is not the definition's"),
+                     (_ANY, -2, "hmse_subst_apply device status {st:#x}: out_off[-1] exceeds the output")))
+    return out[:int(n_out)]
 
 
 @dataclass
