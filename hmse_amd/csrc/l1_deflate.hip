@@ -137,6 +137,8 @@ struct Small {
   uint32_t red[NT / 64 + 1];
   uint32_t qhead;
   uint32_t ocnt[4];   // sorted ranks per chain-length class (the matcher's hand-out order)
+  uint32_t otot[4];   // the same totals, known from the bucket sizes before the sort (classes whose sort writes the hand-out list)
+  unsigned long long opk[1];   // those classes' append cursors while the sort runs: four 16-bit fields, one 64-bit LDS atomic reserves in all four
   struct { uint32_t ji, job, L, Dl; uint64_t c, cstart, rec_at, dstart; } nx;   // the NEXT job's metadata, fetched while this one runs
   struct { uint64_t rec_at; } cur;   // the RUNNING job's record offset (nx is overwritten while it runs)
   uint32_t pexit[NT / 64], pexit2[NT / 64], pconv[NT / 64];
@@ -463,6 +465,15 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
   uint16_t* const jump = LDSM ? (uint16_t*)(smem + LY::A_OFF) : sc->jumpA;
   uint8_t* const K = LDSM ? (uint8_t*)(smem + LY::K_OFF) : sc->K;
   auto n_jobs_now = [&]() -> uint32_t { return *kargs()->n_jobs; };   // (fixed while the kernel runs)
+  // Plain jobs of classes S and S2 (match lengths in LDS): the ordered sort writes the matcher's hand-out list itself, see phases 1-4 and 4c.
+  // (A/B build: HMSE_NO_SORT_ORD keeps the two passes of phase 4c for them.)
+#if defined(HMSE_NO_ORD) || defined(HMSE_NO_SORT_ORD)
+  constexpr bool SORT_ORD = false;
+#else
+  constexpr bool SORT_ORD = LDSM && !MLG && !DICT;
+#endif
+  static_assert(!SORT_ORD || LY::ML_SZ >= NBK * 2, "the bucket starts wait in the match-length area during the sort");
+  [[maybe_unused]] uint32_t* const starts = (uint32_t*)(smem + LY::ML_OFF);   // packed like cur[]
 #ifdef HMSE_DFL_STAMPS
   unsigned long long stamp_acc[24] = {0}, stamp_last = clock64();
 #endif
@@ -588,10 +599,11 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     for (uint32_t i = t; i < NBK / 2; i += NT) cur[i] = 0;
     for (uint32_t i = t; i < 288; i += NT) sm.lf[i] = 0;
     if (t < 32) sm.df[t] = 0;
-    if (t == 0) sm.qhead = 0;
-    if (t < 4) sm.ocnt[t] = 0;
+    if (t == 0) { sm.qhead = 0; if constexpr (SORT_ORD) sm.opk[0] = 0; }
+    if (t < 4) { sm.ocnt[t] = 0; if constexpr (SORT_ORD) sm.otot[t] = 0; }
     // (16 bytes per store: both arrays start on a 16-byte boundary and hold LCAP = a multiple of 16 bytes)
-    for (uint32_t i = t * 16; i < L; i += NT * 16) *(uint4*)(mlen0 + i) = make_uint4(0, 0, 0, 0);
+    // (SORT_ORD: the area holds the bucket starts during the sort and is cleared behind it)
+    if constexpr (!SORT_ORD) for (uint32_t i = t * 16; i < L; i += NT * 16) *(uint4*)(mlen0 + i) = make_uint4(0, 0, 0, 0);
     __syncthreads();
 
     STAMP(0);
@@ -617,6 +629,23 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         wv[i] = idx < NBK / 2 ? cur[idx] : 0u;
         sum += (wv[i] & 0xFFFFu) + (wv[i] >> 16);
       }
+      if constexpr (SORT_ORD) {
+        // The hand-out list's class totals, which place the four classes one behind the other before the first entry is written,
+        // follow from the bucket sizes alone: a bucket of n members has the in-bucket indices 0 .. n - 1, a rank's candidate count is
+        // km = min(index, D) with D = min(depth, 63), so max(n - th, 0) of its ranks have km >= th where D >= th, none otherwise.
+        // Two 16-bit sums per register (a wavefront's buckets hold fewer than 2^14 positions); one LDS atomic per wavefront and class.
+        uint32_t ca = 0, cb = 0;   // >= 24 | >= 12 << 16;  >= 4 | >= 1 << 16
+#pragma unroll
+        for (int i = 0; i < 2 * PERW; i++) {
+          const uint32_t n = (i & 1) ? wv[i / 2] >> 16 : wv[i / 2] & 0xFFFFu;
+          ca += __builtin_elementwise_sub_sat(n, 24u) | (__builtin_elementwise_sub_sat(n, 12u) << 16);
+          cb += __builtin_elementwise_sub_sat(n, 4u) | (__builtin_elementwise_sub_sat(n, 1u) << 16);
+        }
+        const uint32_t sa = wave_sum(ca), sb = wave_sum(cb);
+        const uint32_t D = __builtin_elementwise_min(kargs()->depth, 63u);
+        const uint32_t g24 = D >= 24u ? sa & 0xFFFFu : 0u, g12 = D >= 12u ? sa >> 16 : 0u, g4 = D >= 4u ? sb & 0xFFFFu : 0u, g1 = D >= 1u ? sb >> 16 : 0u;
+        if (lane < 4u) atomicAdd(&sm.otot[lane], lane == 0u ? g24 : lane == 1u ? g12 - g24 : lane == 2u ? g4 - g12 : g1 - g4);
+      }
       uint32_t total;
       uint32_t ex = block_exclusive_scan_w<NT>(sum, t, sm.red, &total);
 #pragma unroll
@@ -624,7 +653,10 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         const uint32_t idx = t * PERW + i;
         const uint32_t lo16 = ex; ex += wv[i] & 0xFFFFu;
         const uint32_t hi16 = ex; ex += wv[i] >> 16;
-        if (idx < NBK / 2) cur[idx] = lo16 | (hi16 << 16);
+        if (idx < NBK / 2) {
+          cur[idx] = lo16 | (hi16 << 16);
+          if constexpr (SORT_ORD) starts[idx] = lo16 | (hi16 << 16);   // (the scatter turns cur[] into the buckets' ends)
+        }
       }
     }
     __syncthreads();
@@ -643,9 +675,30 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
       // (Measured, round 3: two or four positions per thread and step — half / a quarter of the barriers — are SLOWER, +4.5 % / +14 %
       // on the match kernels: the quadratic rank runs over the step's duplicates, and a step of 2048 positions has four times the pairs.)
       // (filter byte of a position: low nibble of its byte 4 | four more bits of its hash product, see the matcher's `rejects`)
+      //
+      // SORT_ORD (plain jobs of S and S2): the rewrite step also writes the matcher's hand-out list (phase 4c says what the list is).
+      // The thread that places position q at rank before + r holds the rank, the hash product and — with the bucket's start, which
+      // the scan left in starts[] — the in-bucket index, so the entry costs four ballots, the lane's place among its class in the
+      // wavefront and one store.  The class totals are known since the scan (sm.otot): class c's list begins where the classes before
+      // it end, and a wavefront reserves its slots in all four with ONE 64-bit LDS atomic per step (sm.opk: a 16-bit cursor per class),
+      // issued in front of the step's second barrier and consumed behind it.  Same set of entries as phase 4c's two passes; the order
+      // inside a class depended on the order of the wavefronts' atomics there too, and does not enter the results.
+      static_assert(!SORT_ORD || TCAP < 65536, "16-bit list cursors");
+      [[maybe_unused]] const uint16_t* const start_of = (const uint16_t*)starts;   // (the packed words, read half by half)
       uint32_t q = t, h = 0, before = 0, hx = 0;
+      [[maybe_unused]] uint32_t bidx = 0;   // in-bucket index of slot `before` (0 in a lane without a position)
       bool act = q < nh;
-      if (act) { hx = sort_key(W, q); h = hx >> (32 - HB); before = cur_get(cur, h); }
+      if (act) {
+        hx = sort_key(W, q); h = hx >> (32 - HB); before = cur_get(cur, h);
+        if constexpr (SORT_ORD) bidx = before - start_of[h];
+      }
+      [[maybe_unused]] uint32_t* ord = nullptr;
+      [[maybe_unused]] uint32_t dcap = 0, ob1 = 0, ob2 = 0, ob3 = 0;   // min(depth, 63); where the lists of classes 1..3 begin
+      if constexpr (SORT_ORD) {
+        ord = (uint32_t*)(scratch2_wg() + 98304u);
+        dcap = __builtin_elementwise_min(kargs()->depth, 63u);   // (6 bits in the entry; a deeper configuration recomputes the count at the pull)
+        ob1 = uni32(sm.otot[0]); ob2 = ob1 + uni32(sm.otot[1]); ob3 = ob2 + uni32(sm.otot[2]);
+      }
       __syncthreads();
       for (uint32_t q0 = 0; q0 < nh; q0 += NT) {
         if (act) S[cur_inc(cur, h)] = (uint16_t)q;
@@ -655,15 +708,60 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
           const uint32_t after = cur_get(cur, h);
           for (uint32_t jj = before; jj < after; jj++) r += S[jj] < q;   // (measured: four slots per round trip is slower, +3 % — the usual trip count is one)
         }
+        // this step's candidate count; the four classes' lane masks (cumulative: one compare each); the cursors the atomic returned (lane 0)
+        [[maybe_unused]] uint32_t km = 0, obl = 0, obh = 0;
+        [[maybe_unused]] uint64_t oc0 = 0, oc1 = 0, oc2 = 0, oc3 = 0;
+        if constexpr (SORT_ORD) {
+          km = bidx + r;   // (a lane without a position: 0 + 0; first-of-bucket ranks, km == 0, are not listed)
+          km = km < dcap ? km : dcap;
+          oc0 = __ballot(km >= 24u); oc1 = __ballot(km >= 12u); oc2 = __ballot(km >= 4u); oc3 = __ballot(km >= 1u);
+          if (oc3 != 0 && lane == 0u) {
+            // (the address through an opaque zero in a vector register: with a wave-uniform address the compiler rewrites the atomic
+            // for a whole wavefront of callers — lane counts, a 64-bit multiply and a wait for the result right here)
+            uint32_t z = 0;
+            asm volatile("" : "+v"(z));
+            const unsigned long long got = atomicAdd(&sm.opk[z], (unsigned long long)__builtin_popcountll(oc0) | ((unsigned long long)__builtin_popcountll(oc1 & ~oc0) << 16) |
+                                                                     ((unsigned long long)__builtin_popcountll(oc2 & ~oc1) << 32) | ((unsigned long long)__builtin_popcountll(oc3 & ~oc2) << 48));
+            obl = (uint32_t)got; obh = (uint32_t)(got >> 32);
+          }
+        }
         const uint32_t qn = q0 + NT + t;
         const bool actn = qn < nh;
         uint32_t hn = 0, beforen = 0, hxn = 0;
-        if (actn) { hxn = sort_key(W, qn); hn = hxn >> (32 - HB); beforen = cur_get(cur, hn); }
+        [[maybe_unused]] uint32_t bidxn = 0;
+        if (actn) {
+          hxn = sort_key(W, qn); hn = hxn >> (32 - HB); beforen = cur_get(cur, hn);
+          if constexpr (SORT_ORD) bidxn = beforen - start_of[hn];
+        }
         __syncthreads();
         if (act) { S[before + r] = (uint16_t)q; if constexpr (!NOK) K[before + r] = (uint8_t)((hx & 0x0Fu) | ((hx >> 12) & 0xF0u)); }
+        if constexpr (SORT_ORD) {
+          if (oc3 != 0) {   // (wave-uniform: the cross-lane reads run under the full EXEC)
+            const uint32_t gl = (uint32_t)__builtin_amdgcn_readlane((int)obl, 0), gh = (uint32_t)__builtin_amdgcn_readlane((int)obh, 0);
+            // The entry's slot = where its class's list begins + the wavefront's reservation + the lane's place among the wavefront's ranks
+            // of the class.  Class by class, three vector instructions each with masks and bases in scalar registers, shortest class
+            // first under the CUMULATIVE lane masks the ballots left (no further compare): the lanes of a longer class overwrite what
+            // they computed with a shorter one's mask.  (The empty asm keeps the steps apart: merged into selects of a lane's 64-bit
+            // mask and base they took 21 instructions.)
+            uint32_t pos = 0;
+            if (km >= 1u) { pos = ob3 + (gh >> 16) + mbcnt64(oc3 & ~oc2); asm volatile("" : "+v"(pos)); }
+            if (km >= 4u) { pos = ob2 + (gh & 0xFFFFu) + mbcnt64(oc2 & ~oc1); asm volatile("" : "+v"(pos)); }
+            if (km >= 12u) { pos = ob1 + (gl >> 16) + mbcnt64(oc1 & ~oc0); asm volatile("" : "+v"(pos)); }
+            if (km >= 24u) { pos = (gl & 0xFFFFu) + mbcnt64(oc0); asm volatile("" : "+v"(pos)); }
+            // rank | candidate count << 15 | bits 16..19 of the hash product << 21
+            if (km != 0u) *(uint32_t*)((uint8_t*)ord + (pos << 2)) = (before + r) | (km << 15) | ((hx << 5) & 0x01E00000u);
+          }
+          bidx = bidxn;
+        }
         q = qn; act = actn; h = hn; before = beforen; hx = hxn;
       }
+      // (SORT_ORD: nobody reads starts[] behind the last step's second barrier — the area becomes the match lengths, cleared here)
+      if constexpr (SORT_ORD) for (uint32_t i = t * 16; i < L; i += NT * 16) *(uint4*)(mlen0 + i) = make_uint4(0, 0, 0, 0);
       __syncthreads();  // cursor h now = end of bucket h
+#ifdef HMSE_DIAG
+      // check build: every class's appended entries against the total the scan computed (status bit 5: a list with a hole or a stray entry)
+      if constexpr (SORT_ORD) if (t < 4u && (uint32_t)((sm.opk[0] >> (16u * t)) & 0xFFFFull) != sm.otot[t]) atomicOr(kargs()->status, 32u);
+#endif
     }
     STAMP(2);
     PF_STAGE(2);
@@ -828,11 +926,16 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     // when the queue is nearly empty and every wavefront ends in a long, thinly occupied tail (a third of all lane-slots in the
     // scheduling model of tools/lz_sched.py, 19 % measured).  So the ranks are handed out longest-first: four classes by candidate
     // count (>= 24, 12..23, 4..11, 1..3), each a dense list of ranks; first-of-bucket ranks (no candidate: a third of all ranks) are
-    // not handed out at all.  The lists live in the workgroup's global scratch (no LDS left in class S): two u16[32768] buffers, two
-    // classes each, one growing up and one growing down.  Model: wave-trips per job 45.3 -> 34.1, pulls 20.3 -> 13.2 on wiki-synth;
-    // results unchanged (the order of the walks does not enter them).
+    // not handed out at all.  The four lists lie one behind the other, longest class first, in ONE u32 array in the workgroup's global
+    // scratch (no LDS left in class S); an entry is rank | candidate count << 15 | filter bits << 21.  Model: wave-trips per job
+    // 45.3 -> 34.1, pulls 20.3 -> 13.2 on wiki-synth; results unchanged (the order of the walks does not enter them).
     // Dictionary jobs: only chunk positions WITHOUT a diagonal hint are listed (rule 2c: the others were written by the pre-pass above);
     // a job has ~2.6 of them per lane, so its matcher phase is as long as its longest walks make it — started first here.
+    // WHO BUILDS THE LIST.  Plain jobs of classes S and S2 (SORT_ORD): the ordered sort above, from its rewrite step — nothing is left to
+    // do here.  Everything else runs the two passes below over the finished sort: dictionary jobs (whether a chunk position is listed
+    // depends on the anchors, which need the finished sort) and the plain jobs of SG, SG2 and SG3 (no idle 8 KiB of LDS for the bucket
+    // starts while they sort).  The two passes cost 4.9 % of a plain class-S job's clocks and 4.2 % of S2 + SG where they
+    // ran (tools/deflate_stamps.py).
 #if defined(HMSE_NO_ORD)
     constexpr bool ORD = false;   // (A/B build: round 3's hand-out in rank order)
 #elif defined(HMSE_NO_DICT_ORD)
@@ -841,7 +944,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     constexpr bool ORD = LDSM;
 #endif
     auto ord_of = [&]() -> uint32_t* { return (uint32_t*)(scratch2_wg() + 98304u); };
-    if constexpr (ORD) {
+    if constexpr (ORD && !SORT_ORD) {
       const uint32_t depth = kargs()->depth;
       uint32_t* const ord = ord_of();
       // Two passes over this wavefront's ranks (64 per step, a step every NT ranks; ITER steps at most): the first classifies — all
@@ -962,7 +1065,8 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
       uint64_t wq_mask = 0; uint32_t wq_base = 0; bool wq_done = false;
       const uint32_t nh_s = uni32(nh);
       // plain jobs: ranks per class -> ends of the four list segments in hand-out order
-      const uint32_t n_ord = ORD ? uni32(sm.ocnt[0]) + uni32(sm.ocnt[1]) + uni32(sm.ocnt[2]) + uni32(sm.ocnt[3]) : nh_s;
+      const uint32_t* const ocnt_m = SORT_ORD ? sm.otot : sm.ocnt;   // (a list the sort wrote: the totals it was laid out by)
+      const uint32_t n_ord = ORD ? uni32(ocnt_m[0]) + uni32(ocnt_m[1]) + uni32(ocnt_m[2]) + uni32(ocnt_m[3]) : nh_s;
       uint8_t* const wtab = sm.wtab + (wave << 6);
       // state of a freshly pulled position (rank ii holds chunk position pp)
       auto begin_walk = [&](uint32_t ii, uint32_t pp) {

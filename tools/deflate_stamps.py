@@ -31,7 +31,9 @@ lib.hmse_debug_deflate_stamps(buf.ctypes.data, 0)
 ebuf = np.zeros(8, dtype=np.uint64)
 lib.hmse_debug_encode_stamps.argtypes = [C.c_void_p, C.c_int]
 lib.hmse_debug_encode_stamps(ebuf.ctypes.data, 0)
-names = ["0 load+clear", "1 hist+scan", "2 scatter+rank", "3 match: state machine", "4 parse: stitch", "5 tokens + histograms", "6 match: anchors + hinted positions", "7 -", "8 hand-out order lists", "9 record out", "10 job fetch", "11 parse: next-pointers", "12 parse: speculative walks"]
+# (plain jobs of S and S2 build the hand-out list inside the sort — their slot 8 is empty and slot 2 holds both: compare the SUM of 2 and 8
+# with a build that keeps the two passes, -DHMSE_NO_SORT_ORD)
+names = ["0 load+clear", "1 hist+scan", "2 scatter+rank (+ list: plain S, S2)", "3 match: state machine", "4 parse: stitch", "5 tokens + histograms", "6 match: anchors + hinted positions", "7 -", "8 hand-out order lists (two passes)", "9 record out", "10 job fetch", "11 parse: next-pointers", "12 parse: speculative walks"]
 lens = (cuts[1:] - cuts[:-1])[uniq]
 hb = base >= 0
 Tfull = lens
@@ -49,11 +51,11 @@ for c, cn in enumerate([f"plain S (T <= {_c[0]})", f"plain S2, SG (T <= {_c[2]})
     row = buf[c * 24:(c + 1) * 24].astype(np.float64)
     occ = row[16:22].copy(); row = row[:16]
     trips, positions, jobs = row[13], row[14], row[15]
-    walked, usable = row[7], row[8]
-    row[7:9] = 0
+    walked = row[7]
+    row[7] = 0     # (a count, not clocks; slot 8 IS clocks — phase 4c's — and stays in the total)
     row[13:] = 0
     if walked:
-        print(cn, "positions walked by lane 0: %d, %.1f %% with a usable partial hint" % (walked, 100 * usable / walked))
+        print(cn, "positions walked by lane 0: %d" % walked)
     tot = row.sum()
     if tot == 0:
         continue
@@ -64,6 +66,8 @@ for c, cn in enumerate([f"plain S (T <= {_c[0]})", f"plain S2, SG (T <= {_c[2]})
               % (100 * occ[0] / trips, occ[1] / max(occ[0], 1), 100 * occ[2] / trips, occ[3] / max(occ[2], 1), 100 * occ[4] / trips, occ[5] / max(occ[4], 1)))
     for i, nm in enumerate(names):
         print("   %-18s %6.2f %%" % (nm, 100 * row[i] / tot))
+    if c >= 3:
+        print("   (dictionary jobs: the anchors and the hinted positions, phase 4b, run in front of the lists and are stamped with them in slot 8)")
 
 et = ebuf[:6].astype(np.float64)
 if et.sum():
