@@ -385,7 +385,7 @@ __device__ void rle_tree_wave(const uint8_t* l, uint32_t n, SM* sm, uint32_t tok
 
 #ifdef HMSE_DFL_STAMPS
 // diagnostic build only: per-phase shader-clock totals of thread 0, summed over jobs and workgroups
-__device__ unsigned long long g_dfl_stamps[6][24];   // [size group + 3 * dictionary jobs][phase]
+__device__ unsigned long long g_dfl_stamps[6][24];   // [size group + 3 * dictionary jobs][phase]  (16..21: lane occupancy of the matcher; 22, 23: dictionary jobs' anchors / hinted-position pre-pass)
 __device__ unsigned long long g_enc_stamps[8];   // encode kernel: clocks of thread 0 per phase (0 load, 1 trees, 2 rle+cl+decide, 3 codes, 4 emit, 5 copy-out), [7] records
 #define STAMP(i) do { if (threadIdx.x == 0) { const unsigned long long now__ = clock64(); stamp_acc[i] += now__ - stamp_last; stamp_last = now__; } } while (0)
 #else
@@ -472,6 +472,15 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
 #else
   constexpr bool SORT_ORD = LDSM && !MLG && !DICT;
 #endif
+  // Dictionary jobs of the LDS classes: the ordered sort leaves every chunk position's rank behind, and the hand-out list is built by ONE
+  // pass over the chunk positions that also writes the hinted positions' results, see phase 4c.
+  // (A/B build: HMSE_NO_DICT_POSLIST keeps the hinted-position pre-pass and the two passes over the sorted ranks for them.)
+#if defined(HMSE_NO_ORD) || defined(HMSE_NO_DICT_ORD) || defined(HMSE_NO_DICT_POSLIST)
+  constexpr bool POS_ORD = false;
+#else
+  constexpr bool POS_ORD = LDSM && DICT;
+#endif
+  static_assert(!POS_ORD || TCAP < 65536, "a rank waits in a match-distance slot");
   static_assert(!SORT_ORD || LY::ML_SZ >= NBK * 2, "the bucket starts wait in the match-length area during the sort");
   [[maybe_unused]] uint32_t* const starts = (uint32_t*)(smem + LY::ML_OFF);   // packed like cur[]
 #ifdef HMSE_DFL_STAMPS
@@ -601,6 +610,9 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     if (t < 32) sm.df[t] = 0;
     if (t == 0) { sm.qhead = 0; if constexpr (SORT_ORD) sm.opk[0] = 0; }
     if (t < 4) { sm.ocnt[t] = 0; if constexpr (SORT_ORD) sm.otot[t] = 0; }
+#ifdef HMSE_DIAG
+    if constexpr (POS_ORD) if (t < 4) sm.otot[t] = 0;   // check build: the class counts of the passes over the sorted ranks
+#endif
     // (16 bytes per store: both arrays start on a 16-byte boundary and hold LCAP = a multiple of 16 bytes)
     // (SORT_ORD: the area holds the bucket starts during the sort and is cleared behind it)
     if constexpr (!SORT_ORD) for (uint32_t i = t * 16; i < L; i += NT * 16) *(uint4*)(mlen0 + i) = make_uint4(0, 0, 0, 0);
@@ -699,6 +711,14 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         dcap = __builtin_elementwise_min(kargs()->depth, 63u);   // (6 bits in the entry; a deeper configuration recomputes the count at the pull)
         ob1 = uni32(sm.otot[0]); ob2 = ob1 + uni32(sm.otot[1]); ob3 = ob2 + uni32(sm.otot[2]);
       }
+      // POS_ORD (dictionary jobs of the LDS classes): the rewrite step leaves the rank of chunk position q in mdist[q - Dl], where phase
+      // 4c's pass over the chunk positions finds it.  The match-distance array is idle until then: the hinted positions' results and the
+      // matcher write it, each together with a non-zero match length, and its only readers — the parse's verdict in jump[] and the token
+      // phase — look at a distance only where the length is non-zero; a rank that nobody overwrites is never read as a distance.
+      // Consecutive threads store consecutive halfwords (LDS in class S, the workgroup's global scratch elsewhere); the barrier that
+      // ends the sort orders the stores before phase 4c's reads, as the matcher's barrier does for the parse.
+      [[maybe_unused]] uint16_t* rank_at = nullptr;
+      if constexpr (POS_ORD) rank_at = mdist_of();
       __syncthreads();
       for (uint32_t q0 = 0; q0 < nh; q0 += NT) {
         if (act) S[cur_inc(cur, h)] = (uint16_t)q;
@@ -735,6 +755,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         }
         __syncthreads();
         if (act) { S[before + r] = (uint16_t)q; if constexpr (!NOK) K[before + r] = (uint8_t)((hx & 0x0Fu) | ((hx >> 12) & 0xF0u)); }
+        if constexpr (POS_ORD) if (act && q >= Dl) *(uint16_t*)((uint8_t*)rank_at + ((q - Dl) << 1)) = (uint16_t)(before + r);   // (a 32-bit byte offset: no 64-bit address per lane)
         if constexpr (SORT_ORD) {
           if (oc3 != 0) {   // (wave-uniform: the cross-lane reads run under the full EXEC)
             const uint32_t gl = (uint32_t)__builtin_amdgcn_readlane((int)obl, 0), gh = (uint32_t)__builtin_amdgcn_readlane((int)obh, 0);
@@ -853,6 +874,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         anch[a0] = word; anchb[a0] = (uint8_t)back;   // every lane, same values
       }
       __syncthreads();
+      STAMP(22);
     }
     // ---- phase 5: longest match for every chunk position ----------------------------------------
     // Bucket sizes and match lengths are heavily skewed (a few hot 4-grams hold most candidates), so a
@@ -864,8 +886,8 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     // position is unchanged (nearest first), so results equal the oracle's serial walk.
     //
     // Dictionary jobs (rule 2c of the oracle): a position with a diagonal hint (>= 16 bytes of an anchor's run left) TAKES it — no
-    // walk.  Those are ~85 % of a near-duplicate's positions; a position-parallel pre-pass writes their results with coalesced stores,
-    // and the state machine below only ever sees the others: every wavefront scans the sorted ranks 64 at a time, keeps the
+    // walk.  Those are ~85 % of a near-duplicate's positions; a position-parallel pass writes their results with coalesced stores (a
+    // pre-pass of its own in class B, the first pass of phase 4c in the LDS classes), and the state machine below only ever sees the others: every wavefront scans the sorted ranks 64 at a time, keeps the
     // ranks that need a walk (chunk positions without a hint) as a 64-bit window mask, and hands them to its idle
     // lanes in order — no lane ever pulls a dictionary rank or a hinted position.
     // diagonal hint of chunk position p: best (known length, candidate) over this block's anchor and the previous one's
@@ -884,6 +906,16 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         if (m > bm) { bm = m; bq = p - d; }
       }
       return bm;
+    };
+    // (one step of hint_of with the anchor word in hand: what the anchor w of the block that starts at pa knows about p, kept if it beats
+    // bm — phase 4c's pass over the chunk positions fetches the words of several positions together)
+    [[maybe_unused]] auto hint_word = [&](uint32_t p, uint32_t maxlen, uint32_t w, uint32_t pa, uint32_t& bm, uint32_t& bq) {
+      const uint32_t d = w & 0xFFFFu, run = w >> 16;
+      if (w == 0 || p < pa || d > p || p - d >= Dl) return;
+      uint32_t m = 0;
+      if (run >= 512u) m = maxlen;
+      else if (pa + run > p) m = (pa + run - p) < maxlen ? (pa + run - p) : maxlen;
+      if (m > bm) { bm = m; bq = p - d; }
     };
     // What the anchors of the NEXT two blocks know about chunk position p (an unhinted one: the walk asks): p lies in the backward
     // stretch of anchor a' = (pa', d', run', back') iff pa' - p <= back', and then its common prefix with the candidate p - d' is
@@ -906,7 +938,8 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
       }
       return kf;
     };
-    if constexpr (DICT) {
+    // (POS_ORD: phase 4c's pass over the chunk positions writes the hinted positions' results)
+    if constexpr (DICT && !POS_ORD) {
       uint8_t* const mlen = mlen_of(); uint16_t* const mdist = mdist_of();
       for (uint32_t x = t; x < L; x += NT) {
         const uint32_t p = Dl + x;
@@ -919,6 +952,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
       // (the state machine never touches a hinted position's slots, and the parse starts behind a barrier; the barrier here is for the
       // hand-out pass below, which reads the verdicts back where the match lengths live in LDS)
       if constexpr (!MLG && LDSM) __syncthreads();
+      STAMP(23);
     }
     // ---- phase 4c (LDS classes): the matcher's hand-out order ---------------------------------------------------------
     // A walk lasts about as many trips as its position has candidates (in-bucket index, capped at the depth), candidates per position
@@ -932,10 +966,11 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     // Dictionary jobs: only chunk positions WITHOUT a diagonal hint are listed (rule 2c: the others were written by the pre-pass above);
     // a job has ~2.6 of them per lane, so its matcher phase is as long as its longest walks make it — started first here.
     // WHO BUILDS THE LIST.  Plain jobs of classes S and S2 (SORT_ORD): the ordered sort above, from its rewrite step — nothing is left to
-    // do here.  Everything else runs the two passes below over the finished sort: dictionary jobs (whether a chunk position is listed
-    // depends on the anchors, which need the finished sort) and the plain jobs of SG, SG2 and SG3 (no idle 8 KiB of LDS for the bucket
-    // starts while they sort).  The two passes cost 4.9 % of a plain class-S job's clocks and 4.2 % of S2 + SG where they
-    // ran (tools/deflate_stamps.py).
+    // do here.  The plain jobs of SG, SG2 and SG3 (no idle 8 KiB of LDS for the bucket starts while they sort) run the two passes below
+    // over the finished sort's ranks; they cost 4.9 % of a plain class-S job's clocks and 4.2 % of S2 + SG where they ran
+    // (tools/deflate_stamps.py).  Dictionary jobs (whether a chunk position is listed depends on the anchors, which
+    // need the finished sort) run two passes as well, but over their CHUNK POSITIONS (POS_ORD): half of a
+    // near-duplicate's ranks are dictionary positions, which are never listed, and the sort left each chunk position's rank behind.
 #if defined(HMSE_NO_ORD)
     constexpr bool ORD = false;   // (A/B build: round 3's hand-out in rank order)
 #elif defined(HMSE_NO_DICT_ORD)
@@ -956,13 +991,14 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
       // for the whole wavefront in nearly every trip: rank | candidate count << 15 | the four hash-product bits of the filter byte << 21.
       constexpr int ITER = (TCAP + NT - 1) / NT;
       const uint32_t wv = uni32(wave);   // (scalar control: the cross-lane reads below never run under a narrowed EXEC)
-      uint32_t pk[(ITER + 2) / 3];
+      constexpr int NPK = (ITER + 2) / 3;
+      uint32_t pk[NPK];
 #pragma unroll
-      for (int w = 0; w < (ITER + 2) / 3; w++) pk[w] = 0;
+      for (int w = 0; w < NPK; w++) pk[w] = 0;
       uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;
       // (branch-free and staged — all S reads, then all window reads, then all cursor reads: three LDS round trips per wavefront
       // instead of three per step; as nested ifs the compiler serialised the steps, 27 dependent round trips in class S)
-      {
+      if constexpr (!POS_ORD) {
         const uint32_t last = nh ? nh - 1u : 0u;
         constexpr int G = DICT ? 2 : ITER > 12 ? 4 : 8;   // steps staged together (registers: the larger classes run under a 64-VGPR cap)
         [[maybe_unused]] const uint8_t* const mlen_h = mlen_of();
@@ -1000,6 +1036,57 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
             n2 += (uint32_t)__builtin_popcountll(__ballot(km >= 4u)); n3 += (uint32_t)__builtin_popcountll(__ballot(km >= 1u));
           }
         }
+      } else {
+        // POS_ORD (dictionary jobs): the first pass runs over this thread's CHUNK POSITIONS x = t, t + NT, ... instead of the wavefront's
+        // ranks — no step is spent on a dictionary rank (half of a near-duplicate's window), and a step's reads no longer hang on each
+        // other: the two anchor words, the position's rank (the sort left it in mdist[x]) and the window dwords are fetched for several
+        // steps together, the bucket start of the position's own hash product behind them.  It is also the hinted-position pass: the hint
+        // is worked out once, a hinted position's result is written here (its distance replaces the rank, which nobody needs), and an
+        // unhinted one is classified as in the pass over the ranks.  The same thread wrote x's slot in neither array before, so nothing
+        // but the sort's barrier orders this pass; the last three positions of the window have no rank and are never listed (`hashed`).
+        // Same set of entries per class as the passes over the ranks; the order inside a class does not enter the results.
+        constexpr int G = 2;
+        uint8_t* const mlen = mlen_of(); uint16_t* const mdist = mdist_of();
+        const uint32_t xl = L ? L - 1u : 0u;
+#pragma unroll
+        for (int g = 0; g < ITER; g += G) if ((uint32_t)g * NT < L) {
+          uint32_t rk[G], d0[G], d1[G], w0[G], w1[G], lv[G];
+#pragma unroll
+          for (int u = 0; u < G; u++) if (g + u < ITER) {
+            const uint32_t x = (uint32_t)(g + u) * NT + t, xc = x < xl ? x : xl, a0 = xc >> 6;
+            const uint32_t* const wp = (const uint32_t*)(W + ((Dl + xc) & ~3u));
+            w0[u] = anch[a0]; w1[u] = anch[a0 ? a0 - 1u : 0u];
+            rk[u] = *(const uint16_t*)((const uint8_t*)mdist + (xc << 1));   // (32-bit byte offsets, as in the sort)
+            d0[u] = wp[0]; d1[u] = wp[1];
+          }
+#pragma unroll
+          for (int u = 0; u < G; u++) if (g + u < ITER) {
+            const uint32_t x = (uint32_t)(g + u) * NT + t, xc = x < xl ? x : xl, p = Dl + xc, a0 = xc >> 6;
+            const uint32_t hx = alignb(d1[u], d0[u], p) * 0x9E3779B1u;   // (the hash product: bucket = its top HB bits)
+            lv[u] = cur_get(cur, ((hx >> (32 - HB)) - 1u) & (uint32_t)(NBK - 1));   // (= end of the bucket before; unused for bucket 0)
+            // (the hint while the cursor read is under way)
+            const bool hashed = x + 4u <= L;   // a sorted position: it has a rank, and a match of 4 bytes fits behind it
+            uint32_t bm = 0, bq = 0;
+            const uint32_t maxlen = (T - p) < MAXM ? (T - p) : MAXM;
+            hint_word(p, maxlen, w0[u], Dl + (a0 << 6), bm, bq);
+            if (a0 != 0u) hint_word(p, maxlen, w1[u], Dl + ((a0 - 1u) << 6), bm, bq);
+            const bool hinted = bm >= 16u;
+            if (hashed && hinted) { mlen[x] = (uint8_t)(bm - 3); *(uint16_t*)((uint8_t*)mdist + (x << 1)) = (uint16_t)(p - bq); }
+            d0[u] = (hx & ~1u) | ((hashed && !hinted) ? 1u : 0u);   // bit 0 (unused below): the position goes on the list if it has a candidate
+          }
+#pragma unroll
+          for (int u = 0; u < G; u++) if (g + u < ITER) {
+            const int it = g + u;
+            uint32_t km = rk[u] - ((d0[u] >> (32 - HB)) ? lv[u] : 0u);
+            km = km < depth ? km : depth;
+            km = km < 63u ? km : 63u;   // (6 bits in the entry; a deeper configuration recomputes the count at the pull)
+            km = (d0[u] & 1u) ? km : 0u;
+            pk[it / 3] |= (km | ((d0[u] >> 10) & 0x3C0u)) << (10 * (it % 3));   // km (6 bits) | bits 16..19 of the hash product << 6
+            n0 += (uint32_t)__builtin_popcountll(__ballot(km >= 24u)); n1 += (uint32_t)__builtin_popcountll(__ballot(km >= 12u));
+            n2 += (uint32_t)__builtin_popcountll(__ballot(km >= 4u)); n3 += (uint32_t)__builtin_popcountll(__ballot(km >= 1u));
+          }
+          __builtin_amdgcn_sched_barrier(0);   // (keeps the next group's reads behind this one: registers)
+        }
       }
       n3 -= n2; n2 -= n1; n1 -= n0;
       uint32_t bv = 0;
@@ -1011,23 +1098,87 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         const uint32_t c0 = uni32(sm.ocnt[0]), c1 = uni32(sm.ocnt[1]), c2 = uni32(sm.ocnt[2]);
         b1 += c0; b2 += c0 + c1; b3 += c0 + c1 + c2;
       }
-#pragma unroll
-      for (int it = 0; it < ITER; it++) {
-        const uint32_t r0 = (wv << 6) + (uint32_t)it * NT;
-        if (r0 < nh) {
-          const uint32_t kv = (pk[it / 3] >> (10 * (it % 3))) & 0x3FFu, km = kv & 63u;
-          const uint64_t c0 = __ballot(km >= 24u), c1 = __ballot(km >= 12u), c2 = __ballot(km >= 4u), c3 = __ballot(km >= 1u);   // cumulative: one compare each
-          const uint64_t m0 = c0, m1 = c1 & ~c0, m2 = c2 & ~c1, m3 = c3 & ~c2;
-          if (km != 0u) {
-            const uint64_t mm = km >= 24u ? m0 : km >= 12u ? m1 : km >= 4u ? m2 : m3;
-            const uint32_t pos = (km >= 24u ? b0 : km >= 12u ? b1 : km >= 4u ? b2 : b3) + mbcnt64(mm);
-            ord[pos] = (r0 + lane) | (kv << 15);
+#ifdef HMSE_DIAG
+      // check build: the sorted ranks classified as the passes over the ranks do (a chunk position without a hint, by its in-bucket index),
+      // for the class counts alone; compared below with the sizes of the list built from the chunk positions
+      if constexpr (POS_ORD) {
+        uint32_t k0 = 0, k1 = 0, k2 = 0, k3 = 0;
+        for (uint32_t r0 = wv << 6; r0 < nh; r0 += NT) {   // (wave-uniform bounds: the ballots run under the full EXEC)
+          const uint32_t r = r0 + lane;
+          uint32_t km = 0;
+          if (r < nh) {
+            const uint32_t pp = S[r];
+            if (pp >= Dl) {
+              uint32_t bq;
+              const uint32_t h = hash4(ld32a(W, pp));
+              km = r - (h ? cur_get(cur, h - 1u) : 0u);
+              km = km < depth ? km : depth;
+              km = km < 63u ? km : 63u;
+              if (hint_of(pp, (T - pp) < MAXM ? (T - pp) : MAXM, bq) >= 16u) km = 0;
+            }
           }
-          b0 += (uint32_t)__builtin_popcountll(m0); b1 += (uint32_t)__builtin_popcountll(m1);
-          b2 += (uint32_t)__builtin_popcountll(m2); b3 += (uint32_t)__builtin_popcountll(m3);
+          k0 += (uint32_t)__builtin_popcountll(__ballot(km >= 24u)); k1 += (uint32_t)__builtin_popcountll(__ballot(km >= 12u));
+          k2 += (uint32_t)__builtin_popcountll(__ballot(km >= 4u)); k3 += (uint32_t)__builtin_popcountll(__ballot(km >= 1u));
+        }
+        k3 -= k2; k2 -= k1; k1 -= k0;
+        if (lane < 4u) atomicAdd(&sm.otot[lane], lane == 0u ? k0 : lane == 1u ? k1 : lane == 2u ? k2 : k3);
+      }
+#endif
+      if constexpr (POS_ORD) {
+        // the second pass, over the same positions: an entry's rank is read back from mdist[x] (this thread stored or kept it; several
+        // steps' reads together — the array is global memory in all classes but S), the rest sits packed in registers as below
+        constexpr int G = 8;
+        const uint16_t* const mdist = mdist_of();
+        const uint32_t xl = L ? L - 1u : 0u;
+        // (the thread index behind a compiler barrier: computed from the first pass's index, every step's clamped position and byte offset
+        // stayed in a register of its own from there to here, and the kernel spilled)
+        uint32_t t2 = t;
+        asm volatile("" : "+v"(t2));
+#pragma unroll
+        for (int g = 0; g < ITER; g += G) if ((uint32_t)g * NT < L) {
+          uint32_t rk[G / 2] = {};   // (two ranks per register)
+#pragma unroll
+          for (int u = 0; u < G; u++) if (g + u < ITER) { const uint32_t x = (uint32_t)(g + u) * NT + t2; rk[u / 2] |= (uint32_t)*(const uint16_t*)((const uint8_t*)mdist + ((x < xl ? x : xl) << 1)) << (16 * (u & 1)); }
+#pragma unroll
+          for (int u = 0; u < G; u++) if (g + u < ITER) {
+            const int it = g + u;
+            if ((wv << 6) + (uint32_t)it * NT < L) {
+              const uint32_t kv = (pk[it / 3] >> (10 * (it % 3))) & 0x3FFu, km = kv & 63u;
+              const uint64_t c0 = __ballot(km >= 24u), c1 = __ballot(km >= 12u), c2 = __ballot(km >= 4u), c3 = __ballot(km >= 1u);   // cumulative: one compare each
+              const uint64_t m0 = c0, m1 = c1 & ~c0, m2 = c2 & ~c1, m3 = c3 & ~c2;
+              if (km != 0u) {
+                const uint64_t mm = km >= 24u ? m0 : km >= 12u ? m1 : km >= 4u ? m2 : m3;
+                const uint32_t pos = (km >= 24u ? b0 : km >= 12u ? b1 : km >= 4u ? b2 : b3) + mbcnt64(mm);
+                ord[pos] = ((rk[u / 2] >> (16 * (u & 1))) & 0xFFFFu) | (kv << 15);
+              }
+              b0 += (uint32_t)__builtin_popcountll(m0); b1 += (uint32_t)__builtin_popcountll(m1);
+              b2 += (uint32_t)__builtin_popcountll(m2); b3 += (uint32_t)__builtin_popcountll(m3);
+            }
+          }
+        }
+      } else {
+#pragma unroll
+        for (int it = 0; it < ITER; it++) {
+          const uint32_t r0 = (wv << 6) + (uint32_t)it * NT;
+          if (r0 < nh) {
+            const uint32_t kv = (pk[it / 3] >> (10 * (it % 3))) & 0x3FFu, km = kv & 63u;
+            const uint64_t c0 = __ballot(km >= 24u), c1 = __ballot(km >= 12u), c2 = __ballot(km >= 4u), c3 = __ballot(km >= 1u);   // cumulative: one compare each
+            const uint64_t m0 = c0, m1 = c1 & ~c0, m2 = c2 & ~c1, m3 = c3 & ~c2;
+            if (km != 0u) {
+              const uint64_t mm = km >= 24u ? m0 : km >= 12u ? m1 : km >= 4u ? m2 : m3;
+              const uint32_t pos = (km >= 24u ? b0 : km >= 12u ? b1 : km >= 4u ? b2 : b3) + mbcnt64(mm);
+              ord[pos] = (r0 + lane) | (kv << 15);
+            }
+            b0 += (uint32_t)__builtin_popcountll(m0); b1 += (uint32_t)__builtin_popcountll(m1);
+            b2 += (uint32_t)__builtin_popcountll(m2); b3 += (uint32_t)__builtin_popcountll(m3);
+          }
         }
       }
       __syncthreads();
+#ifdef HMSE_DIAG
+      // check build: the list the pass over the chunk positions laid out against the counts of the pass over the ranks (status bit 5)
+      if constexpr (POS_ORD) if (t < 4u && sm.otot[t] != sm.ocnt[t]) atomicOr(kargs()->status, 32u);
+#endif
       STAMP(8);
     }
     STAMP(6);

@@ -33,7 +33,11 @@ lib.hmse_debug_encode_stamps.argtypes = [C.c_void_p, C.c_int]
 lib.hmse_debug_encode_stamps(ebuf.ctypes.data, 0)
 # (plain jobs of S and S2 build the hand-out list inside the sort — their slot 8 is empty and slot 2 holds both: compare the SUM of 2 and 8
 # with a build that keeps the two passes, -DHMSE_NO_SORT_ORD)
-names = ["0 load+clear", "1 hist+scan", "2 scatter+rank (+ list: plain S, S2)", "3 match: state machine", "4 parse: stitch", "5 tokens + histograms", "6 match: anchors + hinted positions", "7 -", "8 hand-out order lists (two passes)", "9 record out", "10 job fetch", "11 parse: next-pointers", "12 parse: speculative walks"]
+# (dictionary jobs: phase 4b, the hinted-position pre-pass and the lists are stamped apart — 22, 23, 8.  The product build of the LDS classes
+# has no pre-pass: its one pass over the chunk positions writes the hinted positions' results and classifies the others, all in slot 8;
+# a build with -DHMSE_NO_DICT_POSLIST keeps the pre-pass and the two passes over the sorted ranks)
+names = ["0 load+clear", "1 hist+scan", "2 scatter+rank (+ list: plain S, S2)", "3 match: state machine", "4 parse: stitch", "5 tokens + histograms", "6 -", "7 -", "8 hand-out order lists", "9 record out", "10 job fetch", "11 parse: next-pointers", "12 parse: speculative walks"]
+dict_names = {22: "22 dictionary: anchors (phase 4b)", 23: "23 dictionary: hinted-position pre-pass"}
 lens = (cuts[1:] - cuts[:-1])[uniq]
 hb = base >= 0
 Tfull = lens
@@ -49,14 +53,14 @@ for ci_, nm in enumerate(("S", "S2", "SG", "SG2", "SG3", "B")):
 print("deflate op ms", e0.elapsed_time(e1), "jobs", uniq.numel(), "+", int((base >= 0).sum()))
 for c, cn in enumerate([f"plain S (T <= {_c[0]})", f"plain S2, SG (T <= {_c[2]})", "plain SG2, SG3, B", "DICT S", "DICT S2, SG", "DICT SG2, SG3, B"]):
     row = buf[c * 24:(c + 1) * 24].astype(np.float64)
-    occ = row[16:22].copy(); row = row[:16]
+    occ = row[16:22].copy(); extra = {i: row[i] for i in dict_names}; row = row[:16]
     trips, positions, jobs = row[13], row[14], row[15]
     walked = row[7]
     row[7] = 0     # (a count, not clocks; slot 8 IS clocks — phase 4c's — and stays in the total)
     row[13:] = 0
     if walked:
         print(cn, "positions walked by lane 0: %d" % walked)
-    tot = row.sum()
+    tot = row.sum() + sum(extra.values())
     if tot == 0:
         continue
     print(cn, "jobs %d  chunk positions %.1f M  trips of wavefront 0 through the matcher: %.1f per job = %.2f per 64 positions" % (jobs, positions / 1e6, trips / max(jobs, 1), 64 * trips / max(positions, 1)))
@@ -67,7 +71,9 @@ for c, cn in enumerate([f"plain S (T <= {_c[0]})", f"plain S2, SG (T <= {_c[2]})
     for i, nm in enumerate(names):
         print("   %-18s %6.2f %%" % (nm, 100 * row[i] / tot))
     if c >= 3:
-        print("   (dictionary jobs: the anchors and the hinted positions, phase 4b, run in front of the lists and are stamped with them in slot 8)")
+        for i, nm in dict_names.items():
+            print("   %-18s %6.2f %%" % (nm, 100 * extra[i] / tot))
+        print("   anchors + pre-pass + lists: %.2f %% = %.1f Mclk" % (100 * (row[8] + sum(extra.values())) / tot, (row[8] + sum(extra.values())) / 1e6))
 
 et = ebuf[:6].astype(np.float64)
 if et.sum():
