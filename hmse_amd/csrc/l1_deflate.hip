@@ -162,6 +162,12 @@ constexpr int NT_M = 1024, TCAP_SG3 = 32768;
 #define HMSE_NT_B 1024
 #endif
 constexpr int NT_B = HMSE_NT_B, TCAP_B = 65536, LCAP_B = 32768;
+// Dictionary jobs, phase 4b: lanes per anchor when the bucket's members are compared (a power of two, 8 .. 64; 64 = one wavefront per anchor, the form to compare against)
+#ifndef HMSE_ANCH_GW
+#define HMSE_ANCH_GW 16
+#endif
+constexpr uint32_t ANCH_GW = HMSE_ANCH_GW;
+static_assert(ANCH_GW >= 8u && ANCH_GW <= 64u && (ANCH_GW & (ANCH_GW - 1u)) == 0u, "a wavefront holds a whole number of groups");
 
 // LDS carve.  LDSM: every per-position array lives in LDS (size classes T <= TCAP);
 // !LDSM (rare big jobs): S / jump / match arrays live in a per-workgroup global scratch.
@@ -385,7 +391,8 @@ __device__ void rle_tree_wave(const uint8_t* l, uint32_t n, SM* sm, uint32_t tok
 
 #ifdef HMSE_DFL_STAMPS
 // diagnostic build only: per-phase shader-clock totals of thread 0, summed over jobs and workgroups
-__device__ unsigned long long g_dfl_stamps[6][24];   // [size group + 3 * dictionary jobs][phase]  (16..21: lane occupancy of the matcher; 22, 23: dictionary jobs' anchors / hinted-position pre-pass)
+constexpr int N_STAMPS = 26;
+__device__ unsigned long long g_dfl_stamps[6][N_STAMPS];   // [size group + 3 * dictionary jobs][phase]  (16..21: lane occupancy of the matcher; 22, 24, 25: dictionary jobs' anchors — bucket search, member choice, runs —, 23: their hinted-position pre-pass)
 __device__ unsigned long long g_enc_stamps[8];   // encode kernel: clocks of thread 0 per phase (0 load, 1 trees, 2 rle+cl+decide, 3 codes, 4 emit, 5 copy-out), [7] records
 #define STAMP(i) do { if (threadIdx.x == 0) { const unsigned long long now__ = clock64(); stamp_acc[i] += now__ - stamp_last; stamp_last = now__; } } while (0)
 #else
@@ -484,7 +491,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
   static_assert(!SORT_ORD || LY::ML_SZ >= NBK * 2, "the bucket starts wait in the match-length area during the sort");
   [[maybe_unused]] uint32_t* const starts = (uint32_t*)(smem + LY::ML_OFF);   // packed like cur[]
 #ifdef HMSE_DFL_STAMPS
-  unsigned long long stamp_acc[24] = {0}, stamp_last = clock64();
+  unsigned long long stamp_acc[N_STAMPS] = {0}, stamp_last = clock64();
 #endif
 
   // the whole chain at once (thread 0; the first job of a workgroup, and behind a job that was refused)
@@ -805,9 +812,17 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     uint32_t* const anch = mark;   // u32[ceil(L / 64) + 2]: d | run << 16, 0 = none (DICT only); two zero words behind the last anchor
     uint8_t* const anchb = (uint8_t*)(mark + (LCAP / 64 + 2));   // u8[ceil(L / 64) + 2]: back, 0 = none (the mark words hold one BIT per position: room for both)
     static_assert(LCAP % 64 == 0 && (LCAP / 64 + 2) * 4 + LCAP / 64 + 2 <= LY::MARK_SZ, "anchors and their backward extents share the mark area");
+    // Phase 4b in THREE STAGES (-DHMSE_NO_ANCH_STAGES keeps one wavefront per anchor from the bucket search to the runs):
+    //   A  one LANE per anchor finds the bucket's boundary between dictionary and chunk members (the search is one number per anchor);
+    //   B  one lane per (anchor, candidate): ANCH_GW lanes per anchor, 64 / ANCH_GW anchors per wavefront, the nearest candidates in the first
+    //      round — 32 bytes compared for EQUALITY (rule 2b asks whether all 32 agree, not how many do), one ballot, the lowest set bit of the
+    //      group's part is the nearest agreeing member; a group is done once one agrees, a wavefront once its groups are;
+    //   C  one wavefront per anchor that has a member: the 512-byte run and the 128-byte backward extent along its diagonal.
+    // anch[a] carries the anchor from stage to stage: boundary | candidates << 16 behind A, the distance d (0 = none) behind B, the word behind C.
     if constexpr (DICT) {
       const uint32_t n_anch = (L + 63u) >> 6;
       if (t < 2u) { anch[n_anch + t] = 0; anchb[n_anch + t] = 0; }
+#if defined(HMSE_NO_ANCH_STAGES)
       for (uint32_t a0 = wave; a0 < n_anch; a0 += NT / 64) {
         const uint32_t pa = Dl + (a0 << 6);
         uint32_t word = 0, back = 0;
@@ -875,6 +890,162 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
       }
       __syncthreads();
       STAMP(22);
+#else
+      // the run and the backward extent of the anchor at pa (block a0) along the diagonal d; the whole wavefront
+      auto anchor_runs = [&](uint32_t pa, uint32_t a0, uint32_t d, uint32_t& word, uint32_t& back) {
+        // 512 bytes along the diagonal, 8 per lane
+        const uint32_t off = 8u * lane;
+        uint32_t n = 8;
+        if (pa + off < T) {
+          uint64_t xa[1], xb[1];
+          ldNa<1>(W, pa + off - d, xa); ldNa<1>(W, pa + off, xb);
+          const uint64_t x = xa[0] ^ xb[0];
+          if (x) n = (uint32_t)__builtin_ctzll(x) >> 3;
+        } else n = 0;
+        const uint64_t mm = __ballot(n < 8u);
+        uint32_t run = 512;
+        if (mm) { const uint32_t fl = (uint32_t)__builtin_ctzll(mm); run = 8u * fl + (uint32_t)__builtin_amdgcn_readlane((int)n, (int)fl); }
+        if (run > T - pa) run = T - pa;
+        word = d | (run << 16);
+        // 128 bytes behind the anchor, 8 per lane of the first 16 (lane j: [pa - 8j - 8, pa - 8j), counted from its top byte down);
+        // a lane whose candidate side would begin in front of the window's first byte does not compare: the stretch then ends
+        // up to 7 bytes early, which is still a true statement
+        const uint32_t qa0 = pa - d;
+        uint32_t nb = 8;
+        if (lane < 16u) {
+          nb = 0;
+          if (qa0 >= off + 8u) {
+            uint64_t ya[1], yb[1];
+            ldNa<1>(W, qa0 - off - 8u, ya); ldNa<1>(W, pa - off - 8u, yb);
+            const uint64_t y = ya[0] ^ yb[0];
+            nb = y ? (uint32_t)__builtin_clzll(y) >> 3 : 8u;
+          }
+        }
+        const uint64_t mb = __ballot(nb < 8u);
+        back = 128;
+        if (mb) {   // (the first mismatching lane's count, 0..7, read out of three ballots: scalar work, no cross-lane read)
+          const uint32_t fl = (uint32_t)__builtin_ctzll(mb);
+          const uint64_t n0 = __ballot((nb & 1u) != 0), n1 = __ballot((nb & 2u) != 0), n2 = __ballot((nb & 4u) != 0);
+          back = 8u * fl + (uint32_t)((n0 >> fl) & 1ull) + 2u * (uint32_t)((n1 >> fl) & 1ull) + 4u * (uint32_t)((n2 >> fl) & 1ull);
+        }
+        if (back > (a0 << 6)) back = a0 << 6;   // chunk positions only
+      };
+      // one wavefront, one anchor, from the bucket to the runs (the form without stages; the check build holds the stages against it)
+      [[maybe_unused]] auto anchor_wave = [&](uint32_t a0, uint32_t& word, uint32_t& back) {
+        const uint32_t pa = Dl + (a0 << 6);
+        word = 0; back = 0;
+        if (pa + 4 <= T) {
+          const uint32_t h = hash4(ld32a(W, pa));
+          const uint32_t lo = h ? cur_get(cur, h - 1) : 0u, hi = cur_get(cur, h);
+          uint32_t l = lo, r = hi;   // bucket members ascend: dictionary positions first; [lo, l) after the search
+          while (l < r) { const uint32_t m = (l + r) >> 1; if ((uint32_t)S[m] < Dl) l = m + 1; else r = m; }
+          const uint32_t first = l > lo + 64u ? l - 64u : lo;   // the (up to) 64 nearest dictionary members
+          const uint32_t idx = first + lane;
+          uint32_t ml = 0, q = 0;
+          if (idx < l) {
+            q = S[idx];
+            if (TCAP <= (int)WMAX || pa - q <= WMAX) {
+              uint64_t qa[4], pb[4];
+              ldNa<4>(W, q, qa); ldNa<4>(W, pa, pb);
+              ml = 32;
+#pragma unroll
+              for (int u = 3; u >= 0; u--) { const uint64_t x = qa[u] ^ pb[u]; if (x) ml = 8u * u + ((uint32_t)__builtin_ctzll(x) >> 3); }
+            }
+          }
+          uint32_t key = (ml << 8) | lane;   // longest, then nearest (highest lane)
+          key = wave_max(key);
+          if ((key >> 8) >= 32u) {
+            const uint32_t d = pa - (uint32_t)__builtin_amdgcn_readlane((int)q, (int)(key & 63u));
+            anchor_runs(pa, a0, d, word, back);
+          }
+        }
+      };
+      {
+        const uint32_t wv = uni32(wave);   // (scalar loop control in stages B and C: their ballots and cross-lane reads never run under a narrowed EXEC)
+        // ---- stage A: the bucket's dictionary members [lo, l), one lane per anchor; anch[a] = l | min(l - lo, 64) << 16, 0 = nothing to compare
+        static_assert(LCAP / 64 < NT, "one lane per anchor in one trip");
+        if (const uint32_t a = t; a < n_anch) {
+          const uint32_t pa = Dl + (a << 6);
+          uint32_t v = 0;
+          if (pa + 4 <= T) {
+            const uint32_t h = hash4(ld32a(W, pa));
+            const uint32_t lo = h ? cur_get(cur, h - 1) : 0u, hi = cur_get(cur, h);
+            uint32_t l = lo, r = hi;   // bucket members ascend: dictionary positions first; [lo, l) after the search
+            while (l < r) { const uint32_t m = (l + r) >> 1; if ((uint32_t)S[m] < Dl) l = m + 1; else r = m; }
+            const uint32_t cnt = l - lo < 64u ? l - lo : 64u;   // the (up to) 64 nearest dictionary members
+            v = cnt ? l | (cnt << 16) : 0u;                      // (l <= T - 3 < 65536)
+          }
+          anch[a] = v;
+        }
+        __syncthreads();
+        STAMP(22);
+        // ---- stage B: nearest member whose 32 bytes equal the anchor's; anch[a] = its distance, 0 = none
+        // Group g of a wavefront (lanes 16 g .. 16 g + 15) takes anchor ab + g; lane j of the group takes the bucket slot l - 1 - k, k = j, j + 16,
+        // ..: round 0 holds the 16 nearest members, and a group that found an agreeing member leaves (the nearest of a LATER round is
+        // farther than any of this one).  Every lane of the group reads anch[a] before the group's first lane clears it and the winner
+        // writes d — one wavefront's LDS accesses execute in program order, and no other wavefront touches this anchor's word until the
+        // barrier behind the stage.
+        {
+          constexpr uint32_t GW = ANCH_GW, GPW = 64u / GW;
+          const uint32_t g = lane / GW, j = lane % GW;
+          for (uint32_t ab = wv * GPW; ab < n_anch; ab += (uint32_t)(NT / 64) * GPW) {
+            const bool mine = ab + g < n_anch;
+            const uint32_t a = mine ? ab + g : ab;   // (a group without an anchor looks at the wavefront's first and keeps no candidate)
+            const uint32_t v = mine ? anch[a] : 0u;
+            const uint32_t l = v & 0xFFFFu, cnt = v >> 16;
+            if (mine && j == 0u) anch[a] = 0;
+            if (__ballot(cnt != 0u) == 0ull) continue;
+            const uint32_t pa = Dl + (a << 6);
+            uint64_t pb[4];
+            ldNa<4>(W, pa, pb);
+            bool open = true;
+            for (uint32_t k = j; __ballot(open && k < cnt) != 0ull; k += GW) {
+              bool eq = false;
+              uint32_t q = 0;
+              if (open && k < cnt) {
+                q = S[l - 1u - k];
+                if (TCAP <= (int)WMAX || pa - q <= WMAX) {
+                  uint64_t qa[4];
+                  ldNa<4>(W, q, qa);
+                  eq = (((qa[0] ^ pb[0]) | (qa[1] ^ pb[1])) | ((qa[2] ^ pb[2]) | (qa[3] ^ pb[3]))) == 0ull;
+                }
+              }
+              const uint64_t m = __ballot(eq);
+              if constexpr (GW < 64u) {
+                const uint32_t gb = (uint32_t)(m >> (lane & ~(GW - 1u))) & (uint32_t)((1ull << GW) - 1ull);   // the group's lanes that agree
+                if (gb != 0u) {
+                  if (eq && j == (uint32_t)__builtin_ctz(gb)) anch[a] = pa - q;   // lowest k = nearest
+                  open = false;
+                }
+              } else if (m != 0ull) {   // (one anchor per wavefront: the comparison build)
+                if (eq && j == (uint32_t)__builtin_ctzll(m)) anch[a] = pa - q;
+                open = false;
+              }
+            }
+          }
+        }
+        __syncthreads();
+        STAMP(24);
+        // ---- stage C: the runs along the chosen diagonal, one wavefront per anchor
+        for (uint32_t a0 = wv; a0 < n_anch; a0 += NT / 64) {
+          const uint32_t d = uni32(anch[a0]);   // (written by one lane before the barrier: wave-uniform)
+          uint32_t word = 0, back = 0;
+          if (d != 0u) anchor_runs(Dl + (a0 << 6), a0, d, word, back);
+          anch[a0] = word; anchb[a0] = (uint8_t)back;   // every lane, same values
+        }
+        __syncthreads();
+        STAMP(25);
+#ifdef HMSE_DIAG
+        // check build: every anchor again by the form without stages — the bucket search, the exact common prefixes and the longest-then-nearest
+        // key included — against what the stages left (status bit 6: an anchor word or a backward extent differs)
+        for (uint32_t a0 = wv; a0 < n_anch; a0 += NT / 64) {
+          uint32_t word, back;
+          anchor_wave(a0, word, back);
+          if (lane == 0u && (anch[a0] != word || anchb[a0] != (uint8_t)back)) atomicOr(kargs()->status, 64u);
+        }
+#endif
+      }
+#endif
     }
     // ---- phase 5: longest match for every chunk position ----------------------------------------
     // Bucket sizes and match lengths are heavily skewed (a few hot 4-grams hold most candidates), so a
@@ -1671,7 +1842,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
   }
 #undef PF_STAGE
 #ifdef HMSE_DFL_STAMPS
-  if (threadIdx.x == 0) for (int i = 0; i < 24; i++) atomicAdd(&g_dfl_stamps[(TCAP <= TCAP_S ? 0 : TCAP <= TCAP_SG ? 1 : 2) + (DICT ? 3 : 0)][i], stamp_acc[i]);
+  if (threadIdx.x == 0) for (int i = 0; i < N_STAMPS; i++) atomicAdd(&g_dfl_stamps[(TCAP <= TCAP_S ? 0 : TCAP <= TCAP_SG ? 1 : 2) + (DICT ? 3 : 0)][i], stamp_acc[i]);
 #endif
 }
 
@@ -2274,7 +2445,7 @@ extern "C" int hmse_debug_encode_stamps(unsigned long long* out8, int reset) {
 }
 extern "C" int hmse_debug_deflate_stamps(unsigned long long* out96, int reset) {
   if (hipMemcpyFromSymbol(out96, HIP_SYMBOL(dfl::g_dfl_stamps), sizeof(dfl::g_dfl_stamps)) != hipSuccess) return HMSE_EHIP;
-  if (reset) { unsigned long long z[144] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(dfl::g_dfl_stamps), z, sizeof z) != hipSuccess) return HMSE_EHIP; }
+  if (reset) { unsigned long long z[6 * dfl::N_STAMPS] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(dfl::g_dfl_stamps), z, sizeof z) != hipSuccess) return HMSE_EHIP; }
   return HMSE_OK;
 }
 #endif

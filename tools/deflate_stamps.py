@@ -23,7 +23,8 @@ sig = ops.l4_minhash(d, cuts, cfg, uniq)
 _, base = ops.l4_lsh(sig, cfg)
 ops.l1_deflate(d, cuts, cfg, uniq, base)
 torch.cuda.synchronize()
-buf = np.zeros(144, dtype=np.uint64)
+NS = 26   # stamp slots per group (N_STAMPS of l1_deflate.hip)
+buf = np.zeros(6 * NS, dtype=np.uint64)
 lib.hmse_debug_deflate_stamps(buf.ctypes.data, 1)
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record(); ops.l1_deflate(d, cuts, cfg, uniq, base); e1.record(); torch.cuda.synchronize()
@@ -35,9 +36,11 @@ lib.hmse_debug_encode_stamps(ebuf.ctypes.data, 0)
 # with a build that keeps the two passes, -DHMSE_NO_SORT_ORD)
 # (dictionary jobs: phase 4b, the hinted-position pre-pass and the lists are stamped apart — 22, 23, 8.  The product build of the LDS classes
 # has no pre-pass: its one pass over the chunk positions writes the hinted positions' results and classifies the others, all in slot 8;
-# a build with -DHMSE_NO_DICT_POSLIST keeps the pre-pass and the two passes over the sorted ranks)
+# a build with -DHMSE_NO_DICT_POSLIST keeps the pre-pass and the two passes over the sorted ranks.  Phase 4b is stamped in its three stages —
+# 22 bucket search, 24 choice of the member, 25 runs; a build with -DHMSE_NO_ANCH_STAGES has the whole phase in 22)
 names = ["0 load+clear", "1 hist+scan", "2 scatter+rank (+ list: plain S, S2)", "3 match: state machine", "4 parse: stitch", "5 tokens + histograms", "6 -", "7 -", "8 hand-out order lists", "9 record out", "10 job fetch", "11 parse: next-pointers", "12 parse: speculative walks"]
-dict_names = {22: "22 dictionary: anchors (phase 4b)", 23: "23 dictionary: hinted-position pre-pass"}
+dict_names = {22: "22 dictionary: anchors, bucket search (phase 4b, stage A)", 24: "24 dictionary: anchors, member choice (stage B)", 25: "25 dictionary: anchors, runs (stage C)",
+              23: "23 dictionary: hinted-position pre-pass"}
 lens = (cuts[1:] - cuts[:-1])[uniq]
 hb = base >= 0
 Tfull = lens
@@ -52,7 +55,7 @@ for ci_, nm in enumerate(("S", "S2", "SG", "SG2", "SG3", "B")):
     print("class %-6s jobs %6d  window bytes %6.1f MB  chunk bytes %6.1f MB" % (nm, m_.sum(), allT[m_].sum() / 1e6, allL[m_].sum() / 1e6))
 print("deflate op ms", e0.elapsed_time(e1), "jobs", uniq.numel(), "+", int((base >= 0).sum()))
 for c, cn in enumerate([f"plain S (T <= {_c[0]})", f"plain S2, SG (T <= {_c[2]})", "plain SG2, SG3, B", "DICT S", "DICT S2, SG", "DICT SG2, SG3, B"]):
-    row = buf[c * 24:(c + 1) * 24].astype(np.float64)
+    row = buf[c * NS:(c + 1) * NS].astype(np.float64)
     occ = row[16:22].copy(); extra = {i: row[i] for i in dict_names}; row = row[:16]
     trips, positions, jobs = row[13], row[14], row[15]
     walked = row[7]
@@ -73,6 +76,8 @@ for c, cn in enumerate([f"plain S (T <= {_c[0]})", f"plain S2, SG (T <= {_c[2]})
     if c >= 3:
         for i, nm in dict_names.items():
             print("   %-18s %6.2f %%" % (nm, 100 * extra[i] / tot))
+        anchors = extra[22] + extra[24] + extra[25]
+        print("   anchors (22 + 24 + 25): %.2f %% = %.1f Mclk" % (100 * anchors / tot, anchors / 1e6))
         print("   anchors + pre-pass + lists: %.2f %% = %.1f Mclk" % (100 * (row[8] + sum(extra.values())) / tot, (row[8] + sum(extra.values())) / 1e6))
 
 et = ebuf[:6].astype(np.float64)
