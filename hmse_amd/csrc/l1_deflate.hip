@@ -158,16 +158,11 @@ constexpr int align16(int v) { return (v + 15) & ~15; }
 #endif
 constexpr int NT_S = 1024, TCAP_S = HMSE_TCAP_S, TCAP_S2 = HMSE_TCAP_S2, TCAP_SG = HMSE_TCAP_SG, TCAP_SG2 = HMSE_TCAP_SG2;
 constexpr int NT_M = 1024, TCAP_SG3 = 32768;
-#ifndef HMSE_NT_B
-#define HMSE_NT_B 1024
-#endif
-constexpr int NT_B = HMSE_NT_B, TCAP_B = 65536, LCAP_B = 32768;
-// Dictionary jobs, phase 4b: lanes per anchor when the bucket's members are compared (a power of two, 8 .. 64; 64 = one wavefront per anchor, the form to compare against)
-#ifndef HMSE_ANCH_GW
-#define HMSE_ANCH_GW 16
-#endif
-constexpr uint32_t ANCH_GW = HMSE_ANCH_GW;
-static_assert(ANCH_GW >= 8u && ANCH_GW <= 64u && (ANCH_GW & (ANCH_GW - 1u)) == 0u, "a wavefront holds a whole number of groups");
+constexpr int NT_B = 1024, TCAP_B = 65536, LCAP_B = 32768;   // (measured, DESIGN.md §11.9: class B on 1024 threads instead of 512 took the dictionary jobs from 75.4 to 74.4 ms)
+// Dictionary jobs, phase 4b, stage B: lanes per anchor when the bucket's members are compared.  (Measured, DESIGN.md §11.36: 16 beat 8, 32 and
+// one wavefront per anchor.)
+constexpr uint32_t ANCH_GW = 16;
+static_assert(ANCH_GW <= 32u && (ANCH_GW & (ANCH_GW - 1u)) == 0u, "a wavefront holds whole groups, and a group's part of a ballot fits 32 bits");
 
 // LDS carve.  LDSM: every per-position array lives in LDS (size classes T <= TCAP);
 // !LDSM (rare big jobs): S / jump / match arrays live in a per-workgroup global scratch.
@@ -392,7 +387,7 @@ __device__ void rle_tree_wave(const uint8_t* l, uint32_t n, SM* sm, uint32_t tok
 #ifdef HMSE_DFL_STAMPS
 // diagnostic build only: per-phase shader-clock totals of thread 0, summed over jobs and workgroups
 constexpr int N_STAMPS = 26;
-__device__ unsigned long long g_dfl_stamps[6][N_STAMPS];   // [size group + 3 * dictionary jobs][phase]  (16..21: lane occupancy of the matcher; 22, 24, 25: dictionary jobs' anchors — bucket search, member choice, runs —, 23: their hinted-position pre-pass)
+__device__ unsigned long long g_dfl_stamps[6][N_STAMPS];   // [size group + 3 * dictionary jobs][phase]  (16..21: lane occupancy of the matcher; 22, 24, 25: dictionary jobs' anchors — bucket search, member choice, runs —, 23: class B's hinted-position pre-pass)
 __device__ unsigned long long g_enc_stamps[8];   // encode kernel: clocks of thread 0 per phase (0 load, 1 trees, 2 rle+cl+decide, 3 codes, 4 emit, 5 copy-out), [7] records
 #define STAMP(i) do { if (threadIdx.x == 0) { const unsigned long long now__ = clock64(); stamp_acc[i] += now__ - stamp_last; stamp_last = now__; } } while (0)
 #else
@@ -472,23 +467,20 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
   uint16_t* const jump = LDSM ? (uint16_t*)(smem + LY::A_OFF) : sc->jumpA;
   uint8_t* const K = LDSM ? (uint8_t*)(smem + LY::K_OFF) : sc->K;
   auto n_jobs_now = [&]() -> uint32_t { return *kargs()->n_jobs; };   // (fixed while the kernel runs)
-  // Plain jobs of classes S and S2 (match lengths in LDS): the ordered sort writes the matcher's hand-out list itself, see phases 1-4 and 4c.
-  // (A/B build: HMSE_NO_SORT_ORD keeps the two passes of phase 4c for them.)
-#if defined(HMSE_NO_ORD) || defined(HMSE_NO_SORT_ORD)
-  constexpr bool SORT_ORD = false;
-#else
-  constexpr bool SORT_ORD = LDSM && !MLG && !DICT;
-#endif
-  // Dictionary jobs of the LDS classes: the ordered sort leaves every chunk position's rank behind, and the hand-out list is built by ONE
-  // pass over the chunk positions that also writes the hinted positions' results, see phase 4c.
-  // (A/B build: HMSE_NO_DICT_POSLIST keeps the hinted-position pre-pass and the two passes over the sorted ranks for them.)
-#if defined(HMSE_NO_ORD) || defined(HMSE_NO_DICT_ORD) || defined(HMSE_NO_DICT_POSLIST)
-  constexpr bool POS_ORD = false;
-#else
-  constexpr bool POS_ORD = LDSM && DICT;
-#endif
-  static_assert(!POS_ORD || TCAP < 65536, "a rank waits in a match-distance slot");
-  static_assert(!SORT_ORD || LY::ML_SZ >= NBK * 2, "the bucket starts wait in the match-length area during the sort");
+  // WHO BUILDS THE MATCHER'S HAND-OUT LIST (phase 4c says what the list is), and who writes the results of a dictionary job's hinted positions:
+  //   class               plain jobs                            dictionary jobs                           hinted positions written by
+  //   S, S2               BySort: the ordered sort's rewrite    ByChunkPos: two passes over the chunk     the first of those two passes
+  //                       step (phases 3-4)                     positions (phase 4c)
+  //   SG, SG2, SG3        ByRanks: two passes over the sorted   ByChunkPos                                the first of those two passes
+  //   (match lengths      ranks (phase 4c): no idle LDS for
+  //   out of LDS)         the bucket starts during the sort
+  //   B (nothing per      None: ranks are pulled in sorted      None: every wavefront scans the sorted    a pre-pass of its own in front of
+  //   position in LDS)    order                                 ranks for work (the window queue, wq_*)   the state machine
+  // (DESIGN.md §11.34-11.36 has the measurements behind each.)
+  enum class HandOut { BySort, ByChunkPos, ByRanks, None };
+  constexpr HandOut LIST = !LDSM ? HandOut::None : DICT ? HandOut::ByChunkPos : MLG ? HandOut::ByRanks : HandOut::BySort;
+  static_assert(LIST != HandOut::ByChunkPos || TCAP < 65536, "a rank waits in a match-distance slot");
+  static_assert(LIST != HandOut::BySort || LY::ML_SZ >= NBK * 2, "the bucket starts wait in the match-length area during the sort");
   [[maybe_unused]] uint32_t* const starts = (uint32_t*)(smem + LY::ML_OFF);   // packed like cur[]
 #ifdef HMSE_DFL_STAMPS
   unsigned long long stamp_acc[N_STAMPS] = {0}, stamp_last = clock64();
@@ -615,14 +607,14 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     for (uint32_t i = t; i < NBK / 2; i += NT) cur[i] = 0;
     for (uint32_t i = t; i < 288; i += NT) sm.lf[i] = 0;
     if (t < 32) sm.df[t] = 0;
-    if (t == 0) { sm.qhead = 0; if constexpr (SORT_ORD) sm.opk[0] = 0; }
-    if (t < 4) { sm.ocnt[t] = 0; if constexpr (SORT_ORD) sm.otot[t] = 0; }
+    if (t == 0) { sm.qhead = 0; if constexpr (LIST == HandOut::BySort) sm.opk[0] = 0; }
+    if (t < 4) { sm.ocnt[t] = 0; if constexpr (LIST == HandOut::BySort) sm.otot[t] = 0; }
 #ifdef HMSE_DIAG
-    if constexpr (POS_ORD) if (t < 4) sm.otot[t] = 0;   // check build: the class counts of the passes over the sorted ranks
+    if constexpr (LIST == HandOut::ByChunkPos) if (t < 4) sm.otot[t] = 0;   // check build: the class counts of the passes over the sorted ranks
 #endif
     // (16 bytes per store: both arrays start on a 16-byte boundary and hold LCAP = a multiple of 16 bytes)
-    // (SORT_ORD: the area holds the bucket starts during the sort and is cleared behind it)
-    if constexpr (!SORT_ORD) for (uint32_t i = t * 16; i < L; i += NT * 16) *(uint4*)(mlen0 + i) = make_uint4(0, 0, 0, 0);
+    // (BySort: the area holds the bucket starts during the sort and is cleared behind it)
+    if constexpr (LIST != HandOut::BySort) for (uint32_t i = t * 16; i < L; i += NT * 16) *(uint4*)(mlen0 + i) = make_uint4(0, 0, 0, 0);
     __syncthreads();
 
     STAMP(0);
@@ -648,7 +640,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         wv[i] = idx < NBK / 2 ? cur[idx] : 0u;
         sum += (wv[i] & 0xFFFFu) + (wv[i] >> 16);
       }
-      if constexpr (SORT_ORD) {
+      if constexpr (LIST == HandOut::BySort) {
         // The hand-out list's class totals, which place the four classes one behind the other before the first entry is written,
         // follow from the bucket sizes alone: a bucket of n members has the in-bucket indices 0 .. n - 1, a rank's candidate count is
         // km = min(index, D) with D = min(depth, 63), so max(n - th, 0) of its ranks have km >= th where D >= th, none otherwise.
@@ -674,7 +666,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         const uint32_t hi16 = ex; ex += wv[i] >> 16;
         if (idx < NBK / 2) {
           cur[idx] = lo16 | (hi16 << 16);
-          if constexpr (SORT_ORD) starts[idx] = lo16 | (hi16 << 16);   // (the scatter turns cur[] into the buckets' ends)
+          if constexpr (LIST == HandOut::BySort) starts[idx] = lo16 | (hi16 << 16);   // (the scatter turns cur[] into the buckets' ends)
         }
       }
     }
@@ -695,37 +687,37 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
       // on the match kernels: the quadratic rank runs over the step's duplicates, and a step of 2048 positions has four times the pairs.)
       // (filter byte of a position: low nibble of its byte 4 | four more bits of its hash product, see the matcher's `rejects`)
       //
-      // SORT_ORD (plain jobs of S and S2): the rewrite step also writes the matcher's hand-out list (phase 4c says what the list is).
+      // BySort (plain jobs of S and S2): the rewrite step also writes the matcher's hand-out list (phase 4c says what the list is).
       // The thread that places position q at rank before + r holds the rank, the hash product and — with the bucket's start, which
       // the scan left in starts[] — the in-bucket index, so the entry costs four ballots, the lane's place among its class in the
       // wavefront and one store.  The class totals are known since the scan (sm.otot): class c's list begins where the classes before
       // it end, and a wavefront reserves its slots in all four with ONE 64-bit LDS atomic per step (sm.opk: a 16-bit cursor per class),
       // issued in front of the step's second barrier and consumed behind it.  Same set of entries as phase 4c's two passes; the order
       // inside a class depended on the order of the wavefronts' atomics there too, and does not enter the results.
-      static_assert(!SORT_ORD || TCAP < 65536, "16-bit list cursors");
+      static_assert(LIST != HandOut::BySort || TCAP < 65536, "16-bit list cursors");
       [[maybe_unused]] const uint16_t* const start_of = (const uint16_t*)starts;   // (the packed words, read half by half)
       uint32_t q = t, h = 0, before = 0, hx = 0;
       [[maybe_unused]] uint32_t bidx = 0;   // in-bucket index of slot `before` (0 in a lane without a position)
       bool act = q < nh;
       if (act) {
         hx = sort_key(W, q); h = hx >> (32 - HB); before = cur_get(cur, h);
-        if constexpr (SORT_ORD) bidx = before - start_of[h];
+        if constexpr (LIST == HandOut::BySort) bidx = before - start_of[h];
       }
       [[maybe_unused]] uint32_t* ord = nullptr;
       [[maybe_unused]] uint32_t dcap = 0, ob1 = 0, ob2 = 0, ob3 = 0;   // min(depth, 63); where the lists of classes 1..3 begin
-      if constexpr (SORT_ORD) {
+      if constexpr (LIST == HandOut::BySort) {
         ord = (uint32_t*)(scratch2_wg() + 98304u);
         dcap = __builtin_elementwise_min(kargs()->depth, 63u);   // (6 bits in the entry; a deeper configuration recomputes the count at the pull)
         ob1 = uni32(sm.otot[0]); ob2 = ob1 + uni32(sm.otot[1]); ob3 = ob2 + uni32(sm.otot[2]);
       }
-      // POS_ORD (dictionary jobs of the LDS classes): the rewrite step leaves the rank of chunk position q in mdist[q - Dl], where phase
+      // ByChunkPos (dictionary jobs of the LDS classes): the rewrite step leaves the rank of chunk position q in mdist[q - Dl], where phase
       // 4c's pass over the chunk positions finds it.  The match-distance array is idle until then: the hinted positions' results and the
       // matcher write it, each together with a non-zero match length, and its only readers — the parse's verdict in jump[] and the token
       // phase — look at a distance only where the length is non-zero; a rank that nobody overwrites is never read as a distance.
       // Consecutive threads store consecutive halfwords (LDS in class S, the workgroup's global scratch elsewhere); the barrier that
       // ends the sort orders the stores before phase 4c's reads, as the matcher's barrier does for the parse.
       [[maybe_unused]] uint16_t* rank_at = nullptr;
-      if constexpr (POS_ORD) rank_at = mdist_of();
+      if constexpr (LIST == HandOut::ByChunkPos) rank_at = mdist_of();
       __syncthreads();
       for (uint32_t q0 = 0; q0 < nh; q0 += NT) {
         if (act) S[cur_inc(cur, h)] = (uint16_t)q;
@@ -738,7 +730,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         // this step's candidate count; the four classes' lane masks (cumulative: one compare each); the cursors the atomic returned (lane 0)
         [[maybe_unused]] uint32_t km = 0, obl = 0, obh = 0;
         [[maybe_unused]] uint64_t oc0 = 0, oc1 = 0, oc2 = 0, oc3 = 0;
-        if constexpr (SORT_ORD) {
+        if constexpr (LIST == HandOut::BySort) {
           km = bidx + r;   // (a lane without a position: 0 + 0; first-of-bucket ranks, km == 0, are not listed)
           km = km < dcap ? km : dcap;
           oc0 = __ballot(km >= 24u); oc1 = __ballot(km >= 12u); oc2 = __ballot(km >= 4u); oc3 = __ballot(km >= 1u);
@@ -758,12 +750,12 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         [[maybe_unused]] uint32_t bidxn = 0;
         if (actn) {
           hxn = sort_key(W, qn); hn = hxn >> (32 - HB); beforen = cur_get(cur, hn);
-          if constexpr (SORT_ORD) bidxn = beforen - start_of[hn];
+          if constexpr (LIST == HandOut::BySort) bidxn = beforen - start_of[hn];
         }
         __syncthreads();
         if (act) { S[before + r] = (uint16_t)q; if constexpr (!NOK) K[before + r] = (uint8_t)((hx & 0x0Fu) | ((hx >> 12) & 0xF0u)); }
-        if constexpr (POS_ORD) if (act && q >= Dl) *(uint16_t*)((uint8_t*)rank_at + ((q - Dl) << 1)) = (uint16_t)(before + r);   // (a 32-bit byte offset: no 64-bit address per lane)
-        if constexpr (SORT_ORD) {
+        if constexpr (LIST == HandOut::ByChunkPos) if (act && q >= Dl) *(uint16_t*)((uint8_t*)rank_at + ((q - Dl) << 1)) = (uint16_t)(before + r);   // (a 32-bit byte offset: no 64-bit address per lane)
+        if constexpr (LIST == HandOut::BySort) {
           if (oc3 != 0) {   // (wave-uniform: the cross-lane reads run under the full EXEC)
             const uint32_t gl = (uint32_t)__builtin_amdgcn_readlane((int)obl, 0), gh = (uint32_t)__builtin_amdgcn_readlane((int)obh, 0);
             // The entry's slot = where its class's list begins + the wavefront's reservation + the lane's place among the wavefront's ranks
@@ -783,12 +775,12 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         }
         q = qn; act = actn; h = hn; before = beforen; hx = hxn;
       }
-      // (SORT_ORD: nobody reads starts[] behind the last step's second barrier — the area becomes the match lengths, cleared here)
-      if constexpr (SORT_ORD) for (uint32_t i = t * 16; i < L; i += NT * 16) *(uint4*)(mlen0 + i) = make_uint4(0, 0, 0, 0);
+      // (BySort: nobody reads starts[] behind the last step's second barrier — the area becomes the match lengths, cleared here)
+      if constexpr (LIST == HandOut::BySort) for (uint32_t i = t * 16; i < L; i += NT * 16) *(uint4*)(mlen0 + i) = make_uint4(0, 0, 0, 0);
       __syncthreads();  // cursor h now = end of bucket h
 #ifdef HMSE_DIAG
       // check build: every class's appended entries against the total the scan computed (status bit 5: a list with a hole or a stray entry)
-      if constexpr (SORT_ORD) if (t < 4u && (uint32_t)((sm.opk[0] >> (16u * t)) & 0xFFFFull) != sm.otot[t]) atomicOr(kargs()->status, 32u);
+      if constexpr (LIST == HandOut::BySort) if (t < 4u && (uint32_t)((sm.opk[0] >> (16u * t)) & 0xFFFFull) != sm.otot[t]) atomicOr(kargs()->status, 32u);
 #endif
     }
     STAMP(2);
@@ -812,7 +804,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     uint32_t* const anch = mark;   // u32[ceil(L / 64) + 2]: d | run << 16, 0 = none (DICT only); two zero words behind the last anchor
     uint8_t* const anchb = (uint8_t*)(mark + (LCAP / 64 + 2));   // u8[ceil(L / 64) + 2]: back, 0 = none (the mark words hold one BIT per position: room for both)
     static_assert(LCAP % 64 == 0 && (LCAP / 64 + 2) * 4 + LCAP / 64 + 2 <= LY::MARK_SZ, "anchors and their backward extents share the mark area");
-    // Phase 4b in THREE STAGES (-DHMSE_NO_ANCH_STAGES keeps one wavefront per anchor from the bucket search to the runs):
+    // Phase 4b in THREE STAGES:
     //   A  one LANE per anchor finds the bucket's boundary between dictionary and chunk members (the search is one number per anchor);
     //   B  one lane per (anchor, candidate): ANCH_GW lanes per anchor, 64 / ANCH_GW anchors per wavefront, the nearest candidates in the first
     //      round — 32 bytes compared for EQUALITY (rule 2b asks whether all 32 agree, not how many do), one ballot, the lowest set bit of the
@@ -822,75 +814,6 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     if constexpr (DICT) {
       const uint32_t n_anch = (L + 63u) >> 6;
       if (t < 2u) { anch[n_anch + t] = 0; anchb[n_anch + t] = 0; }
-#if defined(HMSE_NO_ANCH_STAGES)
-      for (uint32_t a0 = wave; a0 < n_anch; a0 += NT / 64) {
-        const uint32_t pa = Dl + (a0 << 6);
-        uint32_t word = 0, back = 0;
-        if (pa + 4 <= T) {
-          const uint32_t h = hash4(ld32a(W, pa));
-          const uint32_t lo = h ? cur_get(cur, h - 1) : 0u, hi = cur_get(cur, h);
-          uint32_t l = lo, r = hi;   // bucket members ascend: dictionary positions first; [lo, l) after the search
-          while (l < r) { const uint32_t m = (l + r) >> 1; if ((uint32_t)S[m] < Dl) l = m + 1; else r = m; }
-          const uint32_t first = l > lo + 64u ? l - 64u : lo;   // the (up to) 64 nearest dictionary members
-          const uint32_t idx = first + lane;
-          uint32_t ml = 0, q = 0;
-          if (idx < l) {
-            q = S[idx];
-            if (TCAP <= (int)WMAX || pa - q <= WMAX) {
-              uint64_t qa[4], pb[4];
-              ldNa<4>(W, q, qa); ldNa<4>(W, pa, pb);
-              ml = 32;
-#pragma unroll
-              for (int u = 3; u >= 0; u--) { const uint64_t x = qa[u] ^ pb[u]; if (x) ml = 8u * u + ((uint32_t)__builtin_ctzll(x) >> 3); }
-            }
-          }
-          uint32_t key = (ml << 8) | lane;   // longest, then nearest (highest lane)
-          key = wave_max(key);
-          if ((key >> 8) >= 32u) {
-            const uint32_t d = pa - (uint32_t)__builtin_amdgcn_readlane((int)q, (int)(key & 63u));
-            // 512 bytes along the diagonal, 8 per lane
-            const uint32_t off = 8u * lane;
-            uint32_t n = 8;
-            if (pa + off < T) {
-              uint64_t xa[1], xb[1];
-              ldNa<1>(W, pa + off - d, xa); ldNa<1>(W, pa + off, xb);
-              const uint64_t x = xa[0] ^ xb[0];
-              if (x) n = (uint32_t)__builtin_ctzll(x) >> 3;
-            } else n = 0;
-            const uint64_t mm = __ballot(n < 8u);
-            uint32_t run = 512;
-            if (mm) { const uint32_t fl = (uint32_t)__builtin_ctzll(mm); run = 8u * fl + (uint32_t)__builtin_amdgcn_readlane((int)n, (int)fl); }
-            if (run > T - pa) run = T - pa;
-            word = d | (run << 16);
-            // 128 bytes behind the anchor, 8 per lane of the first 16 (lane j: [pa - 8j - 8, pa - 8j), counted from its top byte down);
-            // a lane whose candidate side would begin in front of the window's first byte does not compare: the stretch then ends
-            // up to 7 bytes early, which is still a true statement
-            const uint32_t qa0 = pa - d;
-            uint32_t nb = 8;
-            if (lane < 16u) {
-              nb = 0;
-              if (qa0 >= off + 8u) {
-                uint64_t ya[1], yb[1];
-                ldNa<1>(W, qa0 - off - 8u, ya); ldNa<1>(W, pa - off - 8u, yb);
-                const uint64_t y = ya[0] ^ yb[0];
-                nb = y ? (uint32_t)__builtin_clzll(y) >> 3 : 8u;
-              }
-            }
-            const uint64_t mb = __ballot(nb < 8u);
-            back = 128;
-            if (mb) {   // (the first mismatching lane's count, 0..7, read out of three ballots: scalar work, no cross-lane read)
-              const uint32_t fl = (uint32_t)__builtin_ctzll(mb);
-              const uint64_t n0 = __ballot((nb & 1u) != 0), n1 = __ballot((nb & 2u) != 0), n2 = __ballot((nb & 4u) != 0);
-              back = 8u * fl + (uint32_t)((n0 >> fl) & 1ull) + 2u * (uint32_t)((n1 >> fl) & 1ull) + 4u * (uint32_t)((n2 >> fl) & 1ull);
-            }
-            if (back > (a0 << 6)) back = a0 << 6;   // chunk positions only
-          }
-        }
-        anch[a0] = word; anchb[a0] = (uint8_t)back;   // every lane, same values
-      }
-      __syncthreads();
-      STAMP(22);
-#else
       // the run and the backward extent of the anchor at pa (block a0) along the diagonal d; the whole wavefront
       auto anchor_runs = [&](uint32_t pa, uint32_t a0, uint32_t d, uint32_t& word, uint32_t& back) {
         // 512 bytes along the diagonal, 8 per lane
@@ -929,36 +852,6 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
           back = 8u * fl + (uint32_t)((n0 >> fl) & 1ull) + 2u * (uint32_t)((n1 >> fl) & 1ull) + 4u * (uint32_t)((n2 >> fl) & 1ull);
         }
         if (back > (a0 << 6)) back = a0 << 6;   // chunk positions only
-      };
-      // one wavefront, one anchor, from the bucket to the runs (the form without stages; the check build holds the stages against it)
-      [[maybe_unused]] auto anchor_wave = [&](uint32_t a0, uint32_t& word, uint32_t& back) {
-        const uint32_t pa = Dl + (a0 << 6);
-        word = 0; back = 0;
-        if (pa + 4 <= T) {
-          const uint32_t h = hash4(ld32a(W, pa));
-          const uint32_t lo = h ? cur_get(cur, h - 1) : 0u, hi = cur_get(cur, h);
-          uint32_t l = lo, r = hi;   // bucket members ascend: dictionary positions first; [lo, l) after the search
-          while (l < r) { const uint32_t m = (l + r) >> 1; if ((uint32_t)S[m] < Dl) l = m + 1; else r = m; }
-          const uint32_t first = l > lo + 64u ? l - 64u : lo;   // the (up to) 64 nearest dictionary members
-          const uint32_t idx = first + lane;
-          uint32_t ml = 0, q = 0;
-          if (idx < l) {
-            q = S[idx];
-            if (TCAP <= (int)WMAX || pa - q <= WMAX) {
-              uint64_t qa[4], pb[4];
-              ldNa<4>(W, q, qa); ldNa<4>(W, pa, pb);
-              ml = 32;
-#pragma unroll
-              for (int u = 3; u >= 0; u--) { const uint64_t x = qa[u] ^ pb[u]; if (x) ml = 8u * u + ((uint32_t)__builtin_ctzll(x) >> 3); }
-            }
-          }
-          uint32_t key = (ml << 8) | lane;   // longest, then nearest (highest lane)
-          key = wave_max(key);
-          if ((key >> 8) >= 32u) {
-            const uint32_t d = pa - (uint32_t)__builtin_amdgcn_readlane((int)q, (int)(key & 63u));
-            anchor_runs(pa, a0, d, word, back);
-          }
-        }
       };
       {
         const uint32_t wv = uni32(wave);   // (scalar loop control in stages B and C: their ballots and cross-lane reads never run under a narrowed EXEC)
@@ -1011,14 +904,9 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
                 }
               }
               const uint64_t m = __ballot(eq);
-              if constexpr (GW < 64u) {
-                const uint32_t gb = (uint32_t)(m >> (lane & ~(GW - 1u))) & (uint32_t)((1ull << GW) - 1ull);   // the group's lanes that agree
-                if (gb != 0u) {
-                  if (eq && j == (uint32_t)__builtin_ctz(gb)) anch[a] = pa - q;   // lowest k = nearest
-                  open = false;
-                }
-              } else if (m != 0ull) {   // (one anchor per wavefront: the comparison build)
-                if (eq && j == (uint32_t)__builtin_ctzll(m)) anch[a] = pa - q;
+              const uint32_t gb = (uint32_t)(m >> (lane & ~(GW - 1u))) & (uint32_t)((1ull << GW) - 1ull);   // the group's lanes that agree
+              if (gb != 0u) {
+                if (eq && j == (uint32_t)__builtin_ctz(gb)) anch[a] = pa - q;   // lowest k = nearest
                 open = false;
               }
             }
@@ -1036,6 +924,36 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         __syncthreads();
         STAMP(25);
 #ifdef HMSE_DIAG
+        // one wavefront, one anchor, from the bucket to the runs (the form without stages; the check build holds the stages against it)
+        auto anchor_wave = [&](uint32_t a0, uint32_t& word, uint32_t& back) {
+          const uint32_t pa = Dl + (a0 << 6);
+          word = 0; back = 0;
+          if (pa + 4 <= T) {
+            const uint32_t h = hash4(ld32a(W, pa));
+            const uint32_t lo = h ? cur_get(cur, h - 1) : 0u, hi = cur_get(cur, h);
+            uint32_t l = lo, r = hi;   // bucket members ascend: dictionary positions first; [lo, l) after the search
+            while (l < r) { const uint32_t m = (l + r) >> 1; if ((uint32_t)S[m] < Dl) l = m + 1; else r = m; }
+            const uint32_t first = l > lo + 64u ? l - 64u : lo;   // the (up to) 64 nearest dictionary members
+            const uint32_t idx = first + lane;
+            uint32_t ml = 0, q = 0;
+            if (idx < l) {
+              q = S[idx];
+              if (TCAP <= (int)WMAX || pa - q <= WMAX) {
+                uint64_t qa[4], pb[4];
+                ldNa<4>(W, q, qa); ldNa<4>(W, pa, pb);
+                ml = 32;
+#pragma unroll
+                for (int u = 3; u >= 0; u--) { const uint64_t x = qa[u] ^ pb[u]; if (x) ml = 8u * u + ((uint32_t)__builtin_ctzll(x) >> 3); }
+              }
+            }
+            uint32_t key = (ml << 8) | lane;   // longest, then nearest (highest lane)
+            key = wave_max(key);
+            if ((key >> 8) >= 32u) {
+              const uint32_t d = pa - (uint32_t)__builtin_amdgcn_readlane((int)q, (int)(key & 63u));
+              anchor_runs(pa, a0, d, word, back);
+            }
+          }
+        };
         // check build: every anchor again by the form without stages — the bucket search, the exact common prefixes and the longest-then-nearest
         // key included — against what the stages left (status bit 6: an anchor word or a backward extent differs)
         for (uint32_t a0 = wv; a0 < n_anch; a0 += NT / 64) {
@@ -1045,7 +963,6 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         }
 #endif
       }
-#endif
     }
     // ---- phase 5: longest match for every chunk position ----------------------------------------
     // Bucket sizes and match lengths are heavily skewed (a few hot 4-grams hold most candidates), so a
@@ -1057,10 +974,9 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     // position is unchanged (nearest first), so results equal the oracle's serial walk.
     //
     // Dictionary jobs (rule 2c of the oracle): a position with a diagonal hint (>= 16 bytes of an anchor's run left) TAKES it — no
-    // walk.  Those are ~85 % of a near-duplicate's positions; a position-parallel pass writes their results with coalesced stores (a
-    // pre-pass of its own in class B, the first pass of phase 4c in the LDS classes), and the state machine below only ever sees the others: every wavefront scans the sorted ranks 64 at a time, keeps the
-    // ranks that need a walk (chunk positions without a hint) as a 64-bit window mask, and hands them to its idle
-    // lanes in order — no lane ever pulls a dictionary rank or a hinted position.
+    // walk.  Those are ~85 % of a near-duplicate's positions; a position-parallel pass writes their results with coalesced stores (the
+    // first pass of phase 4c in the LDS classes, a pre-pass of its own in class B), and the state machine below only ever sees the
+    // others: no lane ever pulls a dictionary rank or a hinted position.
     // diagonal hint of chunk position p: best (known length, candidate) over this block's anchor and the previous one's
     auto hint_of = [&](uint32_t p, uint32_t maxlen, uint32_t& bq) -> uint32_t {
       const uint32_t a0 = (p - Dl) >> 6;
@@ -1109,8 +1025,8 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
       }
       return kf;
     };
-    // (POS_ORD: phase 4c's pass over the chunk positions writes the hinted positions' results)
-    if constexpr (DICT && !POS_ORD) {
+    // ---- class B's dictionary jobs: the hinted-position pre-pass (the LDS classes write these results in phase 4c's first pass) ----
+    if constexpr (DICT && LIST == HandOut::None) {
       uint8_t* const mlen = mlen_of(); uint16_t* const mdist = mdist_of();
       for (uint32_t x = t; x < L; x += NT) {
         const uint32_t p = Dl + x;
@@ -1120,9 +1036,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         const uint32_t bm = hint_of(p, maxlen, bq);
         if (bm >= 16u) { mlen[x] = (uint8_t)(bm - 3); mdist[x] = (uint16_t)(p - bq); }
       }
-      // (the state machine never touches a hinted position's slots, and the parse starts behind a barrier; the barrier here is for the
-      // hand-out pass below, which reads the verdicts back where the match lengths live in LDS)
-      if constexpr (!MLG && LDSM) __syncthreads();
+      // (no barrier: the state machine never touches a hinted position's slots, and the parse starts behind one)
       STAMP(23);
     }
     // ---- phase 4c (LDS classes): the matcher's hand-out order ---------------------------------------------------------
@@ -1134,23 +1048,13 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
     // not handed out at all.  The four lists lie one behind the other, longest class first, in ONE u32 array in the workgroup's global
     // scratch (no LDS left in class S); an entry is rank | candidate count << 15 | filter bits << 21.  Model: wave-trips per job
     // 45.3 -> 34.1, pulls 20.3 -> 13.2 on wiki-synth; results unchanged (the order of the walks does not enter them).
-    // Dictionary jobs: only chunk positions WITHOUT a diagonal hint are listed (rule 2c: the others were written by the pre-pass above);
-    // a job has ~2.6 of them per lane, so its matcher phase is as long as its longest walks make it — started first here.
-    // WHO BUILDS THE LIST.  Plain jobs of classes S and S2 (SORT_ORD): the ordered sort above, from its rewrite step — nothing is left to
-    // do here.  The plain jobs of SG, SG2 and SG3 (no idle 8 KiB of LDS for the bucket starts while they sort) run the two passes below
-    // over the finished sort's ranks; they cost 4.9 % of a plain class-S job's clocks and 4.2 % of S2 + SG where they ran
-    // (tools/deflate_stamps.py).  Dictionary jobs (whether a chunk position is listed depends on the anchors, which
-    // need the finished sort) run two passes as well, but over their CHUNK POSITIONS (POS_ORD): half of a
-    // near-duplicate's ranks are dictionary positions, which are never listed, and the sort left each chunk position's rank behind.
-#if defined(HMSE_NO_ORD)
-    constexpr bool ORD = false;   // (A/B build: round 3's hand-out in rank order)
-#elif defined(HMSE_NO_DICT_ORD)
-    constexpr bool ORD = !DICT && LDSM;
-#else
-    constexpr bool ORD = LDSM;
-#endif
+    // Dictionary jobs: only chunk positions WITHOUT a diagonal hint are listed (rule 2c); a job has ~2.6 of them per lane, so its matcher
+    // phase is as long as its longest walks make it — started first here.
+    // The table at the kernel's top says who builds the list: the sort has done it already (BySort), or the two passes below do, over the
+    // wavefront's sorted ranks (ByRanks) or over the thread's chunk positions (ByChunkPos: half of a near-duplicate's ranks are dictionary
+    // positions, which are never listed, and the sort left each chunk position's rank behind).
     auto ord_of = [&]() -> uint32_t* { return (uint32_t*)(scratch2_wg() + 98304u); };
-    if constexpr (ORD && !SORT_ORD) {
+    if constexpr (LIST == HandOut::ByRanks || LIST == HandOut::ByChunkPos) {
       const uint32_t depth = kargs()->depth;
       uint32_t* const ord = ord_of();
       // Two passes over this wavefront's ranks (64 per step, a step every NT ranks; ITER steps at most): the first classifies — all
@@ -1169,9 +1073,12 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
       uint32_t n0 = 0, n1 = 0, n2 = 0, n3 = 0;
       // (branch-free and staged — all S reads, then all window reads, then all cursor reads: three LDS round trips per wavefront
       // instead of three per step; as nested ifs the compiler serialised the steps, 27 dependent round trips in class S)
-      if constexpr (!POS_ORD) {
+      if constexpr (LIST == HandOut::ByRanks) {
         const uint32_t last = nh ? nh - 1u : 0u;
-        constexpr int G = DICT ? 2 : ITER > 12 ? 4 : 8;   // steps staged together (registers: the larger classes run under a 64-VGPR cap)
+        constexpr int G = ITER > 12 ? 4 : 8;   // steps staged together (registers: the larger classes run under a 64-VGPR cap)
+        // (Nothing reads this pointer: its reader was the dictionary arm of this pass, which no class instantiates any more.  Deriving it still
+        // launders kargs() once — an s_mov_b64 of the kernarg pointer in SG, SG2 and SG3 —, so it stays until a change that is measured on the
+        // GPU takes it out: the commit that retired the arm left the device code byte for byte as it was.)
         [[maybe_unused]] const uint8_t* const mlen_h = mlen_of();
 #pragma unroll
         for (int g = 0; g < ITER; g += G) if ((uint32_t)g * NT < nh) {   // (whole stage groups past the job's last rank are skipped: the unroll is over the class cap)
@@ -1190,17 +1097,6 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
             km = km < depth ? km : depth;
             km = km < 63u ? km : 63u;   // (6 bits in the entry; a deeper configuration recomputes the count at the pull)
             km = r < nh ? km : 0u;
-            if constexpr (DICT) {
-              const uint32_t pp = pv[u];
-              if constexpr (!MLG) {
-                // the pre-pass has decided already: a non-zero length at this point means "hinted" (nothing else has been matched yet)
-                km = (pp < Dl || mlen_h[pp >= Dl ? pp - Dl : 0u] != 0) ? 0u : km;
-              } else {
-                uint32_t bq;
-                const uint32_t bm = pp >= Dl ? hint_of(pp, (T - pp) < MAXM ? (T - pp) : MAXM, bq) : 16u;
-                km = bm >= 16u ? 0u : km;   // a dictionary position (a candidate only) or a hinted chunk position: no walk
-              }
-            }
             pk[it / 3] |= (km | ((hv[u] >> 10) & 0x3C0u)) << (10 * (it % 3));   // km (6 bits) | bits 16..19 of the hash product << 6
             // (cumulative here — one compare per ballot; the class counts are differences, taken once behind the steps)
             n0 += (uint32_t)__builtin_popcountll(__ballot(km >= 24u)); n1 += (uint32_t)__builtin_popcountll(__ballot(km >= 12u));
@@ -1208,7 +1104,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
           }
         }
       } else {
-        // POS_ORD (dictionary jobs): the first pass runs over this thread's CHUNK POSITIONS x = t, t + NT, ... instead of the wavefront's
+        // ByChunkPos (dictionary jobs): the first pass runs over this thread's CHUNK POSITIONS x = t, t + NT, ... instead of the wavefront's
         // ranks — no step is spent on a dictionary rank (half of a near-duplicate's window), and a step's reads no longer hang on each
         // other: the two anchor words, the position's rank (the sort left it in mdist[x]) and the window dwords are fetched for several
         // steps together, the bucket start of the position's own hash product behind them.  It is also the hinted-position pass: the hint
@@ -1272,7 +1168,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
 #ifdef HMSE_DIAG
       // check build: the sorted ranks classified as the passes over the ranks do (a chunk position without a hint, by its in-bucket index),
       // for the class counts alone; compared below with the sizes of the list built from the chunk positions
-      if constexpr (POS_ORD) {
+      if constexpr (LIST == HandOut::ByChunkPos) {
         uint32_t k0 = 0, k1 = 0, k2 = 0, k3 = 0;
         for (uint32_t r0 = wv << 6; r0 < nh; r0 += NT) {   // (wave-uniform bounds: the ballots run under the full EXEC)
           const uint32_t r = r0 + lane;
@@ -1295,7 +1191,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         if (lane < 4u) atomicAdd(&sm.otot[lane], lane == 0u ? k0 : lane == 1u ? k1 : lane == 2u ? k2 : k3);
       }
 #endif
-      if constexpr (POS_ORD) {
+      if constexpr (LIST == HandOut::ByChunkPos) {
         // the second pass, over the same positions: an entry's rank is read back from mdist[x] (this thread stored or kept it; several
         // steps' reads together — the array is global memory in all classes but S), the rest sits packed in registers as below
         constexpr int G = 8;
@@ -1348,7 +1244,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
       __syncthreads();
 #ifdef HMSE_DIAG
       // check build: the list the pass over the chunk positions laid out against the counts of the pass over the ranks (status bit 5)
-      if constexpr (POS_ORD) if (t < 4u && sm.otot[t] != sm.ocnt[t]) atomicOr(kargs()->status, 32u);
+      if constexpr (LIST == HandOut::ByChunkPos) if (t < 4u && sm.otot[t] != sm.ocnt[t]) atomicOr(kargs()->status, 32u);
 #endif
       STAMP(8);
     }
@@ -1359,20 +1255,13 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
       // (the matcher's wave-uniform values: read once in front of its loop)
       const uint32_t depth = kargs()->depth;
       uint8_t* const mlen = mlen_of(); uint16_t* const mdist = mdist_of();
-      const uint32_t* const ord = ORD ? ord_of() : nullptr;
+      const uint32_t* const ord = LIST != HandOut::None ? ord_of() : nullptr;
       enum { FETCH = 0, PROBE = 1, EXTEND = 2, DONE = 3 };
-#ifndef HMSE_FETCH_BATCH
-#define HMSE_FETCH_BATCH 16
-#endif
-#ifndef HMSE_FETCH_BATCH_DICT
-#define HMSE_FETCH_BATCH_DICT 8
-#endif
-      constexpr uint32_t FETCH_BATCH = DICT ? HMSE_FETCH_BATCH_DICT : HMSE_FETCH_BATCH;
+      // idle lanes a wavefront waits for before it pulls.  (Measured: 8 / 24 in plain jobs and 4 / 16 in dictionary jobs are within 0.5 % of these.)
+      constexpr uint32_t FETCH_BATCH = DICT ? 8 : 16;
       uint32_t st = FETCH, i = 0, p = 0, kk = 0, kmax = 0, best = 0, bd = 0, probe = 0, maxlen = 0, ml = 0, q = 0, qn = 0, kn = 0;
       uint32_t pw0 = 0, pw1 = 0;
-#ifndef HMSE_NO_PROBE16
       uint32_t pw2 = 0, pw3 = 0;   // bytes 8..15 of the position: a candidate that agrees on 8 bytes is compared on 8 more in the same trip
-#endif
       uint32_t pkey = 0;   // classes with the filter array: this position's own filter byte
       [[maybe_unused]] uint32_t kf = 0;   // dictionary jobs: the one candidate whose common length the next anchors know (known_of), per lane
       // Can candidate with filter byte kb be skipped without a window read?  Filter array classes: kb = (byte 4 & 15) | 4 further
@@ -1383,23 +1272,19 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         if constexpr (NOK) return best >= 4 && kb != (pw1 & 0xFFu);
         else { const uint32_t x = kb ^ pkey; return (x & 0xF0u) != 0 || (best >= 4 && (x & 0x0Fu) != 0); }
       };
-      // dictionary jobs: this wavefront's window of pending work ranks (wave-uniform)
+      // class B's dictionary jobs (no hand-out list): this wavefront's window of pending work ranks (wave-uniform) ...
       uint64_t wq_mask = 0; uint32_t wq_base = 0; bool wq_done = false;
       const uint32_t nh_s = uni32(nh);
-      // plain jobs: ranks per class -> ends of the four list segments in hand-out order
-      const uint32_t* const ocnt_m = SORT_ORD ? sm.otot : sm.ocnt;   // (a list the sort wrote: the totals it was laid out by)
-      const uint32_t n_ord = ORD ? uni32(ocnt_m[0]) + uni32(ocnt_m[1]) + uni32(ocnt_m[2]) + uni32(ocnt_m[3]) : nh_s;
-      uint8_t* const wtab = sm.wtab + (wave << 6);
+      // what there is to pull: the list's entries (the four class counts; a list the sort wrote: the totals it was laid out by), or every sorted rank
+      const uint32_t* const ocnt_m = LIST == HandOut::BySort ? sm.otot : sm.ocnt;
+      const uint32_t n_ord = LIST != HandOut::None ? uni32(ocnt_m[0]) + uni32(ocnt_m[1]) + uni32(ocnt_m[2]) + uni32(ocnt_m[3]) : nh_s;
+      uint8_t* const wtab = sm.wtab + (wave << 6);   // ... and the wavefront's slice of Small::wtab (class B's dictionary jobs again)
       // state of a freshly pulled position (rank ii holds chunk position pp)
       auto begin_walk = [&](uint32_t ii, uint32_t pp) {
         i = ii; p = pp;
         qn = i ? S[i - 1] : 0u;  // first candidate (used iff kmax != 0)
         kn = NOK ? (uint32_t)W[qn + 4] : (i ? (uint32_t)K[i - 1] : 0u);  // its byte 4 (class SG2 has no filter array)
-#ifndef HMSE_NO_PROBE16
         { uint64_t pp__[2]; ldNa<2>(W, p, pp__); pw0 = (uint32_t)pp__[0]; pw1 = (uint32_t)(pp__[0] >> 32); pw2 = (uint32_t)pp__[1]; pw3 = (uint32_t)(pp__[1] >> 32); }
-#else
-        ld64a(W, p, pw0, pw1);
-#endif
         const uint32_t hxp = pw0 * 0x9E3779B1u;
         const uint32_t h = hxp >> (32 - HB);
         pkey = (pw1 & 0x0Fu) | ((hxp >> 12) & 0xF0u);
@@ -1408,9 +1293,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         kmax = i - lo;
         if (kmax > depth) kmax = depth;
         best = MINM - 1; bd = 0; probe = pw0; kk = 1;
-#ifndef HMSE_NO_PROBE16
-        if constexpr (DICT) kf = known_of(p, maxlen);   // (asked where a candidate has agreed on 16 bytes: the 8-byte experiment build has no such place)
-#endif
+        if constexpr (DICT) kf = known_of(p, maxlen);   // (asked where a candidate has agreed on 16 bytes)
 #ifdef HMSE_DFL_STAMPS
         if (DICT && t == 0) stamp_acc[7]++;  // lane 0's walked positions
 #endif
@@ -1422,11 +1305,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         p = S[i];
         qn = S[i - 1];
         kn = NOK ? (uint32_t)W[qn + 4] : (uint32_t)K[i - 1];
-#ifndef HMSE_NO_PROBE16
         { uint64_t pp__[2]; ldNa<2>(W, p, pp__); pw0 = (uint32_t)pp__[0]; pw1 = (uint32_t)(pp__[0] >> 32); pw2 = (uint32_t)pp__[1]; pw3 = (uint32_t)(pp__[1] >> 32); }
-#else
-        ld64a(W, p, pw0, pw1);
-#endif
         pkey = (pw1 & 0x0Fu) | ((e >> 17) & 0xF0u);
         if (kmax == 63u) {   // (the entry's count saturates at 63: a deeper configuration recomputes it — no lane comes here at depth <= 62)
           const uint32_t h = hash4(pw0), lo = h ? cur_get(cur, h - 1) : 0u;
@@ -1434,9 +1313,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         }
         maxlen = (T - p) < MAXM ? (T - p) : MAXM;
         best = MINM - 1; bd = 0; probe = pw0; kk = 1;
-#ifndef HMSE_NO_PROBE16
-        if constexpr (DICT) kf = known_of(p, maxlen);   // (asked where a candidate has agreed on 16 bytes: the 8-byte experiment build has no such place)
-#endif
+        if constexpr (DICT) kf = known_of(p, maxlen);   // (asked where a candidate has agreed on 16 bytes)
 #ifdef HMSE_DFL_STAMPS
         if (DICT && t == 0) stamp_acc[7]++;
 #endif
@@ -1460,8 +1337,10 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
           break;
         }
         uint64_t need = uni64(__ballot(st == FETCH));
-        if constexpr (DICT && !ORD) {
-          // serve the idle lanes from the wavefront's window; scan the next 64 sorted ranks when it is empty.  Everything that
+        if constexpr (DICT && LIST == HandOut::None) {
+          // class B's dictionary jobs, the window queue: every wavefront scans the sorted ranks 64 at a time, keeps the ranks that need a
+          // walk (chunk positions without a hint) as a 64-bit mask and hands them to its idle lanes in order through wtab.
+          // Serve the idle lanes from the wavefront's window; scan the next 64 sorted ranks when it is empty.  Everything that
           // steers this loop (need, wq_mask, wq_base, wq_done, nh_s) is wave-uniform AND scalar (uni32 / uni64)
           for (int it = 0; need != 0 && it < 6; it++) {
             if (wq_mask == 0) {
@@ -1512,7 +1391,7 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
           if (st == FETCH) {
             const uint32_t f = base + mbcnt64(need);
             if (f >= n_ord) st = DONE;
-            else if constexpr (ORD) begin_walk_listed(ord[f]);
+            else if constexpr (LIST != HandOut::None) begin_walk_listed(ord[f]);
             else begin_walk(f, (uint32_t)S[f]);
           }
         }
@@ -1526,14 +1405,6 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         }
 #endif
         bool fin = false;  // candidate kk finished with length ml
-#ifdef HMSE_EXT_MIN
-        // (experiment) the EXTEND block's ~120 instructions are issued for the whole wavefront however few lanes extend: run it only when
-        // HMSE_EXT_MIN lanes wait for it, or nothing else can run
-        const uint64_t em__ = uni64(__ballot(st == EXTEND));
-        const bool run_ext = (uint32_t)__builtin_popcountll(em__) >= (uint32_t)HMSE_EXT_MIN || uni64(__ballot(st == PROBE)) == 0;
-#else
-        constexpr bool run_ext = true;
-#endif
         if (st == PROBE) {
           q = qn;
           uint32_t kb = kn;
@@ -1558,7 +1429,6 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
             if (cprobe != probe) { }                                   // cannot beat the current best
             else if ((x = c0 ^ pw0) != 0) ml = (uint32_t)__builtin_ctz(x) >> 3;
             else if ((x = c1 ^ pw1) != 0) ml = 4 + ((uint32_t)__builtin_ctz(x) >> 3);
-#ifndef HMSE_NO_PROBE16
             else if (maxlen > 8) {
               // 8 bytes agree: 8 more at once (95 % of such candidates end there on text: tools/lz_study "extend trips at 32 / 16 / 8 B"),
               // so the EXTEND block — ~55 vector instructions issued for the whole wavefront, for ~4 lanes — is entered by the rare
@@ -1571,11 +1441,8 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
               else if (DICT && kf >= (16u << 16) && (kf & 0xFFFFu) == q) ml = kf >> 16;
               else { ml = 16; if (maxlen > 16) { fin = false; st = EXTEND; } }
             } else ml = 8;
-#else
-            else { ml = 8; if (maxlen > 8) { fin = false; st = EXTEND; } }
-#endif
           }
-        } else if (st == EXTEND && run_ext) {
+        } else if (st == EXTEND) {
           // 32 bytes per trip, all reads of each side issued together (one LDS round trip): the dictionary jobs
           // (near-duplicate chunks) spend most of their trips here, a full-length match is 258 bytes
           // (64 bytes where the class runs one workgroup per CU and so may use 128 VGPRs: SG3 and B, the classes of the
@@ -1670,10 +1537,9 @@ __global__ __launch_bounds__(NT, (LDSM ? (NT == 1024 && TCAP <= TCAP_SG2 ? 8 : 4
         // doubled TOGETHER (independent gathers: one LDS-crossbar round trip serves PWX windows) and the entries resolved afterwards,
         // in order.  Measured, round 4: three windows together are 1.8 % SLOWER on the plain kernels (38.8 -> 39.5 ms at 2 GB) —
         // the walks' latency is already hidden behind the CU's other workgroup, the extra registers and selects are not.
-#ifndef HMSE_DFL_PW
-#define HMSE_DFL_PW 1
-#endif
-        constexpr int PWX = HMSE_DFL_PW;
+        // (The loop stays written over PWX windows: written out for one — scalars for the one-element arrays, no inner loops — the compiler
+        // rotates the doubling loop differently and merges its two exits, four scalar instructions more per round.)
+        constexpr int PWX = 1;
         const uint32_t sw_s = uni32(sw), send_s = uni32(send);   // (wave-uniform, and said so: the window loop is a scalar loop)
         for (uint32_t wb0 = sw_s; wb0 < send_s; wb0 += 64u * PWX) {
           uint32_t hop[PWX], rlo[PWX], rhi[PWX], wendv[PWX];

@@ -33,14 +33,13 @@ ebuf = np.zeros(8, dtype=np.uint64)
 lib.hmse_debug_encode_stamps.argtypes = [C.c_void_p, C.c_int]
 lib.hmse_debug_encode_stamps(ebuf.ctypes.data, 0)
 # (plain jobs of S and S2 build the hand-out list inside the sort — their slot 8 is empty and slot 2 holds both: compare the SUM of 2 and 8
-# with a build that keeps the two passes, -DHMSE_NO_SORT_ORD)
-# (dictionary jobs: phase 4b, the hinted-position pre-pass and the lists are stamped apart — 22, 23, 8.  The product build of the LDS classes
-# has no pre-pass: its one pass over the chunk positions writes the hinted positions' results and classifies the others, all in slot 8;
-# a build with -DHMSE_NO_DICT_POSLIST keeps the pre-pass and the two passes over the sorted ranks.  Phase 4b is stamped in its three stages —
-# 22 bucket search, 24 choice of the member, 25 runs; a build with -DHMSE_NO_ANCH_STAGES has the whole phase in 22)
+# with that of a commit from before DESIGN.md §11.34, built as a variant library)
+# (dictionary jobs: phase 4b, the hinted-position pre-pass and the lists are stamped apart — 22, 24, 25; 23; 8.  Only class B has the pre-pass:
+# the LDS classes' one pass over the chunk positions writes the hinted positions' results and classifies the others, all in slot 8.
+# Phase 4b is stamped in its three stages — 22 bucket search, 24 choice of the member, 25 runs)
 names = ["0 load+clear", "1 hist+scan", "2 scatter+rank (+ list: plain S, S2)", "3 match: state machine", "4 parse: stitch", "5 tokens + histograms", "6 -", "7 -", "8 hand-out order lists", "9 record out", "10 job fetch", "11 parse: next-pointers", "12 parse: speculative walks"]
 dict_names = {22: "22 dictionary: anchors, bucket search (phase 4b, stage A)", 24: "24 dictionary: anchors, member choice (stage B)", 25: "25 dictionary: anchors, runs (stage C)",
-              23: "23 dictionary: hinted-position pre-pass"}
+              23: "23 dictionary: class B's hinted-position pre-pass"}
 lens = (cuts[1:] - cuts[:-1])[uniq]
 hb = base >= 0
 Tfull = lens
