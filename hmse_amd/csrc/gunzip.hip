@@ -6,8 +6,8 @@
 //                           load and one 4-byte test per position.
 //   (2) measure_kernel    — one wavefront per candidate, persistent wavefronts pulling candidates in index order: the header by RFC 1952;
 //                           then either the BGZF fast path (the header says how long the block is: nothing is decoded) or a walk of the
-//                           DEFLATE stream FOR ITS LENGTH ONLY with the bit reader and code tables of inflate_core.h — every validity rule
-//                           of ifl::l1_inflate_kernel, no store, no window.
+//                           DEFLATE stream FOR ITS LENGTH ONLY: ifl::walk_stream of inflate_core.h, the very walk ifl::l1_inflate_kernel
+//                           decodes with and so every validity rule of it, here with a sink that counts — no store, no window.
 // A candidate inside compressed data is measured like any other and comes out invalid or with some end; the caller follows the ends from
 // offset 0 (hmse_amd/gunzip.py), and only real ends lead to the next member.
 // The CONVERGENCE RULE of l1_inflate.hip holds in measure_kernel: every loop has a wave-uniform trip count, every value that steers control
@@ -114,6 +114,17 @@ __device__ __forceinline__ uint32_t header_crc(const uint8_t* d, uint64_t a, uin
   return ~c;
 }
 
+// The Sink of ifl::walk_stream (inflate_core.h) that measures: nothing is stored and there is no window, so a stored block of any length
+// fits and the one refusal is a match that starts in front of the stream.
+struct CountSink {
+  uint64_t pos;                                        // bytes the stream has decoded to so far
+  __device__ __forceinline__ bool fits(uint32_t) const { return true; }
+  __device__ __forceinline__ void stored(const uint8_t*, uint32_t len) { pos += len; }
+  __device__ __forceinline__ bool literal(uint32_t) { pos++; return true; }
+  __device__ __forceinline__ bool match(uint32_t len, uint32_t dist) { if (dist > pos) return false; pos += len; return true; }
+  __device__ __forceinline__ void trace(uint32_t) const {}
+};
+
 __global__ __launch_bounds__(GZ_NT, 8) void measure_kernel(MeasureArgs a) {
   __shared__ ifl::WaveTables s_tab[GZ_NT / 64];
   const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
@@ -170,98 +181,13 @@ __global__ __launch_bounds__(GZ_NT, 8) void measure_kernel(MeasureArgs a) {
     }
     // ---- any other member: walk the stream for its length ----
     if (!why && !bgzf) {
-      ifl::Bits br; br.s = d; br.p = q; br.end = n; br.acc = 0; br.n = 0;
-      uint64_t pos = 0;
-      bool bad = false, last = false;
-      // every block costs >= 3 bits and every symbol >= 1 bit (ifl::l1_inflate_kernel's budget): the wavefront reaches its exit
-      uint64_t budget = 8ull * (n - q) + 64;
-      ifl::LaneCode LL{0, 0, 0}, LD{0, 0, 0};
-      while (!bad && !last) {
-        if (budget-- == 0) { bad = true; break; }
-        last = br.take(1) != 0;
-        const uint32_t type = br.take(2);
-        if (type == 0) {  // stored
-          br.drop(br.n & 7u);
-          const uint32_t len = br.take(16), nlen = br.take(16);
-          if ((len ^ nlen) != 0xFFFFu) { bad = true; break; }
-          const uint64_t src = br.p - (br.n >> 3);
-          if (src + len > br.end) { bad = true; break; }
-          pos += len;
-          br.p = src + len; br.acc = 0; br.n = 0;
-          continue;
-        }
-        if (type == 3) { bad = true; break; }
-        if (type == 1) {  // fixed codes
-          for (uint32_t s0 = 0; s0 < 320; s0 += 64) {
-            const uint32_t s = s0 + lane;
-            if (s < 288) T.lens[s] = (uint8_t)(s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8);
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-          ifl::build_table(T.lens, 288, T.lsym, false, LL);
-          if (lane < 32) T.lens[lane] = 5;
-          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-          ifl::build_table(T.lens, 32, T.dsym, false, LD);
-        } else {  // dynamic codes
-          const uint32_t nlit = br.take(5) + 257, ndist = br.take(5) + 1, ncl = br.take(4) + 4;
-          if (nlit > 286 || ndist > 30) { bad = true; break; }
-          if (lane < 19) T.lens[lane] = 0;
-          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-          for (uint32_t i = 0; i < ncl; i++) {
-            const uint32_t v = br.take(3);
-            const uint32_t o = i < 3 ? 16 + i : i == 3 ? 0 : (i & 1) ? (19 - i) >> 1 : 6 + (i >> 1);   // RFC 1951 §3.2.7
-            T.lens[o] = (uint8_t)v;  // every lane, same address and value
-          }
-          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-          ifl::LaneCode LC;
-          if (!ifl::build_table(T.lens, 19, T.dsym, true, LC)) { bad = true; break; }
-          uint32_t i = 0, prev = 0;
-          const uint32_t tot = nlit + ndist;
-          while (i < tot) {
-            const uint32_t s = ifl::decode_sym(br, LC, T.dsym);
-            if (s > 18) { bad = true; break; }
-            uint32_t rep = 1, val = s;
-            if (s == 16) { if (i == 0) { bad = true; break; } rep = 3 + br.take(2); val = prev; }
-            else if (s == 17) { rep = 3 + br.take(3); val = 0; }
-            else if (s == 18) { rep = 11 + br.take(7); val = 0; }
-            if (i + rep > tot) { bad = true; break; }
-            for (uint32_t j0 = 0; j0 < rep; j0 += 64) {
-              const uint32_t j = j0 + lane;
-              if (j < rep) T.lens[i + j] = (uint8_t)val;
-            }
-            i += rep; prev = val;
-          }
-          if (bad) break;
-          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-          if (uni32(T.lens[256]) == 0) { bad = true; break; }  // no end-of-block code
-          if (!ifl::build_table(T.lens, nlit, T.lsym, false, LL)) { bad = true; break; }
-          if (!ifl::build_table(T.lens + nlit, ndist, T.dsym, false, LD)) { bad = true; break; }
-        }
-        // ---- symbols of this block: counted, not stored ----
-        for (;;) {
-          if (budget-- == 0) { bad = true; break; }
-          const uint32_t s = ifl::decode_sym(br, LL, T.lsym);
-          if (s < 256) { pos++; continue; }
-          if (s == 256) break;
-          if (s > 285) { bad = true; break; }  // 286, 287 and the undefined-code marker 0xFFFF
-          const uint32_t lc = s - 257;
-          uint32_t len;
-          if (lc < 8) len = 3 + lc;
-          else if (lc == 28) len = 258;
-          else { const uint32_t e = (lc - 4) >> 2; len = 3 + ((4 + (lc & 3)) << e) + br.take(e); }
-          const uint32_t ds = ifl::decode_sym(br, LD, T.dsym);
-          if (ds > 29) { bad = true; break; }
-          uint32_t dist;
-          if (ds < 4) dist = 1 + ds;
-          else { const uint32_t e = (ds >> 1) - 1; dist = 1 + ((2 + (ds & 1)) << e) + br.take(e); }
-          if (dist > pos) { bad = true; break; }
-          pos += len;
-        }
-      }
-      const uint64_t s_end = br.p - (br.n >> 3);       // the byte after the final block's last bit
-      if (bad) why = HMSE_GZIP_WHY_STREAM;
+      CountSink sk; sk.pos = 0;
+      uint64_t s_end;                                  // the byte after the final block's last bit
+      const bool walked = ifl::walk_stream(d, q, n, T, sk, s_end);
+      if (!walked) why = HMSE_GZIP_WHY_STREAM;
       else if (s_end > n || n - s_end < 8) why = HMSE_GZIP_WHY_BOUNDS;
-      else if (pos > 0xFFFFFFFFull || s_end - q > 0xFFFFFFFFull || (uint32_t)pos != u32le(d, s_end + 4)) why = HMSE_GZIP_WHY_LENGTH;
-      else { m_end = s_end + 8; m_raw = pos; m_crc = u32le(d, s_end); }
+      else if (sk.pos > 0xFFFFFFFFull || s_end - q > 0xFFFFFFFFull || (uint32_t)sk.pos != u32le(d, s_end + 4)) why = HMSE_GZIP_WHY_LENGTH;
+      else { m_end = s_end + 8; m_raw = sk.pos; m_crc = u32le(d, s_end); }
     }
     // every lane stores the same words (the convergence rule)
     a.stream_off[k] = q;

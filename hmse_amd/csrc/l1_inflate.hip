@@ -16,6 +16,8 @@
 // release/acquire as in the guide's hand-off recipe) — forward progress is guaranteed.
 // The bit reader keeps a 64-bit window refilled from global memory; the output is re-read (match sources)
 // with agent-scope (L1-bypassing) loads after the wave's own stores have drained.
+// The walk over a stream's blocks and symbols, and with it what a valid stream is, is ifl::walk_stream of
+// inflate_core.h, shared with gz::measure_kernel (gunzip.hip); what happens to the bytes is StoreSink's, below.
 #include "common.h"
 #include "blockops.h"
 #include "inflate_core.h"
@@ -34,8 +36,12 @@ struct Args {
   uint32_t* trace;  // diagnostics only (tools/inflate_debug.py): host-visible progress words, 8 per wavefront
 };
 
+// progress words of a wavefront (HMSE_DIAG build): 0 = phase, 1 = record, 2 = pos
 #ifdef HMSE_DIAG
-#define IFL_TRACE(slot, val) do { if (a.trace && lane == 0) __hip_atomic_store(&a.trace[(blockIdx.x * (NT / 64) + wave) * 8 + (slot)], (uint32_t)(val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); } while (0)
+__device__ __forceinline__ void trace_put(uint32_t* trace, uint32_t slot, uint32_t val) {
+  if (trace && lane_id() == 0) __hip_atomic_store(&trace[(blockIdx.x * (NT / 64) + (threadIdx.x >> 6)) * 8 + slot], val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+#define IFL_TRACE(slot, val) trace_put(a.trace, slot, (uint32_t)(val))
 #else
 #define IFL_TRACE(slot, val) do { } while (0)
 #endif
@@ -49,6 +55,58 @@ struct Args {
 // Everything that steers control flow is wave-uniform and is kept in SGPRs: values that arrive through a vector
 // load (same address in every lane) are made scalar with readfirstlane, so the decoder's loops are scalar branches.
 __device__ __forceinline__ uint64_t uload64(const uint64_t* p) { return uni64(*p); }
+
+// The Sink of walk_stream (inflate_core.h) that decodes: the bytes go to out[0, L), and a match may reach Dl bytes back into dict.
+struct StoreSink {
+  uint8_t* out; uint32_t L; const uint8_t* dict; uint32_t Dl; uint32_t lane;
+  uint32_t pos;      // bytes decoded, including literals still pending in `pend`
+  uint32_t npend;    // literals not yet stored: lane i of `pend` holds byte pos - npend + i
+  uint32_t pend;
+  __device__ __forceinline__ void flush() {
+    if (npend) { if (lane < npend) out[pos - npend + lane] = (uint8_t)pend; npend = 0; }
+  }
+  __device__ __forceinline__ bool fits(uint32_t len) const { return pos + len <= L; }
+  __device__ __forceinline__ void stored(const uint8_t* src, uint32_t len) {
+    flush();
+    for (uint32_t i0 = 0; i0 < len; i0 += 64) {
+      const uint32_t i = i0 + lane;
+      if (i < len) out[pos + i] = src[i];
+    }
+    pos += len;
+  }
+  __device__ __forceinline__ bool literal(uint32_t s) {  // parked in lane npend of `pend`, stored 64 at a time
+    if (pos >= L) return false;
+    pend = lane == npend ? s : pend;
+    pos++; npend++;
+    if (npend == 64) { out[pos - 64 + lane] = (uint8_t)pend; npend = 0; }
+    return true;
+  }
+  __device__ __forceinline__ bool match(uint32_t len, uint32_t dist) {
+    if (!fits(len) || dist > pos + Dl) return false;
+    flush();
+    // the wave's own earlier stores must have landed before they are read back
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // every byte of a match equals out[pos - dist + (i mod dist)], which lies before the match: one pass,
+    // no read-after-write inside the match even when it overlaps itself (dist < len)
+    for (uint32_t i0 = 0; i0 < len; i0 += 64) {
+      const uint32_t i = i0 + lane;
+      if (i < len) {
+        const uint32_t j = dist >= len ? i : i % dist;
+        const int64_t sp = (int64_t)pos - dist + j;  // < 0: inside the dictionary
+        const uint8_t* srcp = sp >= 0 ? out + sp : dict + (int64_t)Dl + sp;
+        out[pos + i] = __hip_atomic_load(srcp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+    pos += len;
+    return true;
+  }
+#ifdef HMSE_DIAG
+  uint32_t* trace_words;
+  __device__ __forceinline__ void trace(uint32_t phase) const { trace_put(trace_words, 0, phase); trace_put(trace_words, 2, pos); }
+#else
+  __device__ __forceinline__ void trace(uint32_t) const {}
+#endif
+};
 
 __global__ __launch_bounds__(NT, 8) void l1_inflate_kernel(Args a) {
   __shared__ WaveTables s_tab[NT / 64];
@@ -89,130 +147,16 @@ __global__ __launch_bounds__(NT, 8) void l1_inflate_kernel(Args a) {
     const uint64_t s0 = uload64(a.stream_off + k);
     const uint64_t s1 = a.stream_len ? s0 + uni32(a.stream_len[k]) : uload64(a.stream_off + k + 1);
     if (s1 < s0 || s1 > a.streams_bytes) bad = true;
-    Bits br; br.s = a.streams; br.p = s0; br.end = bad ? s0 : s1; br.acc = 0; br.n = 0;
-    uint32_t pos = 0;      // bytes decoded, including literals still pending in `pend`
-    uint32_t npend = 0;    // literals not yet stored: lane i of `pend` holds byte pos - npend + i
-    uint32_t pend = 0;
-    bool last = false;
-    // every block costs >= 3 bits and every symbol >= 1 bit: a step budget no valid stream can exceed, so that a
-    // wavefront reaches its exit whatever the bytes are
-    uint64_t budget = 8ull * (br.end - s0) + 64;
-    LaneCode LL{0, 0, 0}, LD{0, 0, 0};
-    while (!bad && !last) {
-      if (budget-- == 0) { bad = true; break; }
-      IFL_TRACE(0, 3); IFL_TRACE(2, pos);
-      last = br.take(1) != 0;
-      const uint32_t type = br.take(2);
-      if (type == 0) {  // stored
-        br.drop(br.n & 7u);
-        const uint32_t len = br.take(16), nlen = br.take(16);
-        if ((len ^ nlen) != 0xFFFFu || pos + len > L) { bad = true; break; }
-        const uint64_t src = br.p - (br.n >> 3);  // whole bytes still in the window come first
-        if (src + len > br.end) { bad = true; break; }
-        if (npend) { if (lane < npend) out[pos - npend + lane] = (uint8_t)pend; npend = 0; }
-        for (uint32_t i0 = 0; i0 < len; i0 += 64) {
-          const uint32_t i = i0 + lane;
-          if (i < len) out[pos + i] = a.streams[src + i];
-        }
-        pos += len;
-        br.p = src + len; br.acc = 0; br.n = 0;
-        continue;
-      }
-      if (type == 3) { bad = true; break; }
-      if (type == 1) {  // fixed codes
-        for (uint32_t s0 = 0; s0 < 320; s0 += 64) {
-          const uint32_t s = s0 + lane;
-          if (s < 288) T.lens[s] = (uint8_t)(s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-        build_table(T.lens, 288, T.lsym, false, LL);
-        if (lane < 32) T.lens[lane] = 5;   // 32 five-bit distance codes; 30 and 31 are rejected where they are used
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-        build_table(T.lens, 32, T.dsym, false, LD);
-      } else {  // dynamic codes
-        const uint32_t nlit = br.take(5) + 257, ndist = br.take(5) + 1, ncl = br.take(4) + 4;
-        if (nlit > 286 || ndist > 30) { bad = true; break; }
-        if (lane < 19) T.lens[lane] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-        for (uint32_t i = 0; i < ncl; i++) {
-          const uint32_t v = br.take(3);
-          // order of the code-length code lengths (RFC 1951 §3.2.7): 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15
-          const uint32_t o = i < 3 ? 16 + i : i == 3 ? 0 : (i & 1) ? (19 - i) >> 1 : 6 + (i >> 1);
-          T.lens[o] = (uint8_t)v;  // every lane, same address and value
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-        LaneCode LC;
-        if (!build_table(T.lens, 19, T.dsym, true, LC)) { bad = true; break; }  // code-length code borrows dsym
-        // lengths are decoded into lens[LB..): lens[0..19) still feeds nothing, dsym is read by decode_sym
-        uint32_t i = 0, prev = 0;
-        const uint32_t tot = nlit + ndist;
-        while (i < tot) {
-          const uint32_t s = decode_sym(br, LC, T.dsym);
-          if (s > 18) { bad = true; break; }
-          uint32_t rep = 1, val = s;
-          if (s == 16) { if (i == 0) { bad = true; break; } rep = 3 + br.take(2); val = prev; }
-          else if (s == 17) { rep = 3 + br.take(3); val = 0; }
-          else if (s == 18) { rep = 11 + br.take(7); val = 0; }
-          if (i + rep > tot) { bad = true; break; }
-          for (uint32_t j0 = 0; j0 < rep; j0 += 64) {
-            const uint32_t j = j0 + lane;
-            if (j < rep) T.lens[i + j] = (uint8_t)val;
-          }
-          i += rep; prev = val;
-        }
-        if (bad) break;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-        if (uni32(T.lens[256]) == 0) { bad = true; break; }  // no end-of-block code
-        if (!build_table(T.lens, nlit, T.lsym, false, LL)) { bad = true; break; }
-        if (!build_table(T.lens + nlit, ndist, T.dsym, false, LD)) { bad = true; break; }
-      }
-      IFL_TRACE(0, 6);
-      // ---- symbols of this block ----
-      for (;;) {
-        if (budget-- == 0) { bad = true; break; }
-        const uint32_t s = decode_sym(br, LL, T.lsym);
-        if (s < 256) {  // literal: parked in lane npend of `pend`, stored 64 at a time
-          if (pos >= L) { bad = true; break; }
-          pend = lane == npend ? s : pend;
-          pos++; npend++;
-          if (npend == 64) { out[pos - 64 + lane] = (uint8_t)pend; npend = 0; }
-          continue;
-        }
-        if (s == 256) break;
-        if (s > 285) { bad = true; break; }  // 286, 287 and the undefined-code marker 0xFFFF
-        // length and distance (RFC 1951 §3.2.5)
-        const uint32_t lc = s - 257;
-        uint32_t len;
-        if (lc < 8) len = 3 + lc;
-        else if (lc == 28) len = 258;
-        else { const uint32_t e = (lc - 4) >> 2; len = 3 + ((4 + (lc & 3)) << e) + br.take(e); }
-        const uint32_t ds = decode_sym(br, LD, T.dsym);
-        if (ds > 29) { bad = true; break; }
-        uint32_t dist;
-        if (ds < 4) dist = 1 + ds;
-        else { const uint32_t e = (ds >> 1) - 1; dist = 1 + ((2 + (ds & 1)) << e) + br.take(e); }
-        if (pos + len > L || dist > pos + Dl) { bad = true; break; }
-        if (npend) { if (lane < npend) out[pos - npend + lane] = (uint8_t)pend; npend = 0; }
-        // the wave's own earlier stores must have landed before they are read back
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        // every byte of a match equals out[pos - dist + (i mod dist)], which lies before the match: one pass,
-        // no read-after-write inside the match even when it overlaps itself (dist < len)
-        for (uint32_t i0 = 0; i0 < len; i0 += 64) {
-          const uint32_t i = i0 + lane;
-          if (i < len) {
-            const uint32_t j = dist >= len ? i : i % dist;
-            const int64_t sp = (int64_t)pos - dist + j;  // < 0: inside the dictionary
-            const uint8_t* srcp = sp >= 0 ? out + sp : dict + (int64_t)Dl + sp;
-            out[pos + i] = __hip_atomic_load(srcp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
-        pos += len;
-      }
-    }
-    if (npend && !bad) { if (lane < npend) out[pos - npend + lane] = (uint8_t)pend; }
+    StoreSink sk; sk.out = out; sk.L = L; sk.dict = dict; sk.Dl = Dl; sk.lane = lane; sk.pos = 0; sk.npend = 0; sk.pend = 0;
+#ifdef HMSE_DIAG
+    sk.trace_words = a.trace;
+#endif
+    uint64_t stop = s0;
+    if (!bad) bad = !walk_stream(a.streams, s0, s1, T, sk, stop);
+    if (!bad) sk.flush();
     // the storage contract: exactly the recorded raw length, and the final block ends in the stream's last byte
-    if (!bad && (pos != L || br.p - (br.n >> 3) != br.end)) bad = true;
-    IFL_TRACE(0, 7); IFL_TRACE(2, pos);
+    if (!bad && (sk.pos != L || stop != s1)) bad = true;
+    IFL_TRACE(0, 7); IFL_TRACE(2, sk.pos);
     // publish: every lane's stores drained, agent-scope release, then the flag
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -462,9 +406,7 @@ __global__ __launch_bounds__(64, 2) void l1_inflate_lanes_kernel(Args a) {
               for (uint32_t i = 0; i < ncl; i++) {
                 if (n < 3) LREFILL();
                 const uint32_t v = (uint32_t)acc & 7u; acc >>= 3; n -= 3;
-                // order of the code-length code lengths (RFC 1951 §3.2.7): 16 17 18 0 8 7 9 6 10 5 11 4 12 3 13 2 14 1 15
-                const uint32_t o = i < 3 ? 16 + i : i == 3 ? 0 : (i & 1) ? (19 - i) >> 1 : 6 + (i >> 1);
-                cl57 |= (uint64_t)v << (3 * o);
+                cl57 |= (uint64_t)v << (3 * cl_order(i));
               }
               uint64_t cnt8 = 0;   // symbols per length, 8-bit fields
               for (uint32_t s = 0; s < 19; s++) { const uint32_t l = (uint32_t)(cl57 >> (3 * s)) & 7u; cnt8 += 1ull << (8 * l); }

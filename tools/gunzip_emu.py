@@ -1,7 +1,8 @@
 """The import kernels (hmse_amd/csrc/gunzip.hip) on the CPU against the byte filter and against zlib: no GPU needed.
     python tools/gunzip_emu.py [--iters 6] [--seed 12345] [--sanitize]
-Cuts the kernels out of gunzip.hip (everything between its geometry constants and its entry points; the bit reader, the code tables and
-the symbol decode come with hmse_amd/csrc/inflate_core.h as they are, the block-sum scan with blockops.h), compiles them with
+Cuts the kernels out of gunzip.hip (everything between its geometry constants and its entry points; the bit reader, the code tables, the
+symbol decode and the walk over a stream — ifl::walk_stream, which the measure kernel runs with its counting sink — come with
+hmse_amd/csrc/inflate_core.h as they are, the block-sum scan with blockops.h), compiles them with
 tools/gunzip_emu.cpp (g++ -std=c++20: one std::thread per lane, std::barrier under __syncthreads, __ballot, readlane and readfirstlane)
 and runs the candidate passes on planted buffers and the measure kernel on known answers that this script takes from zlib
 (tests/gunzip_ref.py): small members of every block type and header, BGZF blocks, damaged ones, candidates inside other members, and

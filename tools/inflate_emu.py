@@ -1,7 +1,8 @@
 """The two decoders of hmse_l1_inflate (hmse_amd/csrc/l1_inflate.hip) on the CPU against zlib: no GPU needed.
     python tools/inflate_emu.py [--sanitize]
 Cuts ifl::l1_inflate_kernel (one stream per wavefront) and ifl::l1_inflate_lanes_kernel (one stream per lane) out of l1_inflate.hip —
-everything between the geometry constant and the assemble kernel; the bit reader, the code tables and the symbol decode of the first
+everything between the geometry constant and the assemble kernel; the bit reader, the code tables, the symbol decode and the walk over a
+stream (ifl::walk_stream, which the first shares with gz::measure_kernel; its storing sink is in the cut)
 come with hmse_amd/csrc/inflate_core.h as they are — compiles them with tools/inflate_emu.cpp (g++ -std=c++20: one std::thread per lane,
 a barrier per wavefront under __ballot, readlane and readfirstlane) and runs both over the catalogue of tests/deflate_vectors.py: streams
 zlib's decoder accepts and its encoder never writes, and the rejections beside them (those that would decode to some bytes once more, told that length), with zlib's decision and bytes as
