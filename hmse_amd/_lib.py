@@ -18,6 +18,7 @@ GUNZIP_LIB_PATH = os.path.join(_CSRC, "libhmse_gunzip.so")     # include/hmse_gu
 REGEXA_LIB_PATH = os.path.join(_CSRC, "libhmse_regexa.so")     # include/hmse_regexa.h: the regex search with assertions, likewise
 TALLY_LIB_PATH = os.path.join(_CSRC, "libhmse_tally.so")       # include/hmse_tally.h: the tally of search results, likewise
 SUBST_LIB_PATH = os.path.join(_CSRC, "libhmse_subst.so")       # include/hmse_subst.h: the substitution of ranges, likewise
+ORDER_LIB_PATH = os.path.join(_CSRC, "libhmse_order.so")       # include/hmse_order.h: the order of search results, likewise
 
 
 class HmseCfg(C.Structure):
@@ -220,10 +221,18 @@ TALLY_SIGNATURES = {
                        "u64 n, u32 flags, u8*? same, u32* status, stream",
 }
 # The entry point of include/hmse_subst.h (the substitution of ranges, csrc/libhmse_subst.so); tests/test_subst_host.py holds this table
-# against that header.  Parsed into a table of its own (PARSED_SUBST); ops._call looks a name up there last.
+# against that header.  Parsed into a table of its own (PARSED_SUBST); ops._call looks a name up there after PARSED_TALLY.
 SUBST_SIGNATURES = {
     "hmse_subst_apply": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, u64*? start, u64*? end, u64*? sel, "
                         "u64 n, u8*? rep, u64 rep_bytes, u64*? rep_off, u64 n_rep, u32 flags, u64* out_off, u8*? out, u64 out_cap, u32* status, stream",
+}
+# The entry points of include/hmse_order.h (the order of search results, csrc/libhmse_order.so); tests/test_order_host.py holds this table
+# against that header.  Parsed into a table of its own (PARSED_ORDER); ops._call looks a name up there after PARSED_SUBST.
+ORDER_SIGNATURES = {
+    "hmse_order_keys": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, u64*? start, u64*? end, u64*? depth, "
+                       "u64 n, u32 flags, u64*? key, u32* status, stream",
+    "hmse_order_lcp": "int: u8*? raw, u64 raw_bytes, u64* raw_off, u64 n_rec, u64* cuts, u64*? slot, u64 n_chunks, u64*? start, u64*? end, u64*? rep, "
+                      "u64*? from, u64 n, u32 flags, u64*? lcp, u32* status, stream",
 }
 
 _ELEM = {"u8": C.c_uint8, "u32": C.c_uint32, "i32": C.c_int32, "u64": C.c_uint64, "i64": C.c_int64, "f64": C.c_double}
@@ -265,6 +274,7 @@ PARSED = {name: _parse(sig) for name, sig in {**SIGNATURES, **GUNZIP_SIGNATURES}
 PARSED_REGEXA = {name: _parse(sig) for name, sig in REGEXA_SIGNATURES.items()}
 PARSED_TALLY = {name: _parse(sig) for name, sig in TALLY_SIGNATURES.items()}
 PARSED_SUBST = {name: _parse(sig) for name, sig in SUBST_SIGNATURES.items()}
+PARSED_ORDER = {name: _parse(sig) for name, sig in ORDER_SIGNATURES.items()}
 
 _hip = None
 _corpus = None
@@ -310,6 +320,13 @@ def hip_lib():
         L._subst = S = C.CDLL(SUBST_LIB_PATH)            # (it links against libhmse_hip.so as well)
         for name, (restype, params) in PARSED_SUBST.items():
             fn = getattr(S, name)
+            fn.restype, fn.argtypes = restype, [p.ctype for p in params]
+            setattr(L, name, fn)
+        if not os.path.exists(ORDER_LIB_PATH):
+            raise ImportError(f"{ORDER_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+        L._order = O = C.CDLL(ORDER_LIB_PATH)            # (it links against libhmse_hip.so as well)
+        for name, (restype, params) in PARSED_ORDER.items():
+            fn = getattr(O, name)
             fn.restype, fn.argtypes = restype, [p.ctype for p in params]
             setattr(L, name, fn)
         _hip = L

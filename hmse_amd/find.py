@@ -62,6 +62,16 @@ tests/subst_ref.py restates them in plain Python).  The groups' ranges are merge
 hmse_subst_apply call proves them again, and the out_off it is given, before it writes a byte.  substitute_regex =
 substitute(nonoverlapping(find_regex(rx))).  Out of scope: captures and back-references, `&` (the whole match inside a replacement),
 case-preserving replacement, editing the store's records in place without re-ingest, several stores, fill patterns longer than one byte.
+
+Sort: StoreFinder.sort orders the ranges of a RegexFound, a Lines, a Tally or any (start, end) pair by the texts they cover, as Python
+orders bytes (grep -o RX | sort; with unique=True sort -u, with its counts sort | uniq -c): per group the input indices in order, which
+positions open a new text, and every range's rank (hmse_amd/csrc/order.hip; include/hmse_order.h has the definitions, tests/order_ref.py
+restates them in plain Python).  A most-significant-bytes-first radix sort in rounds (order_ranges): the unresolved ranges are keyed by
+seven bytes at their bucket's depth (hmse_order_keys) and stable-sorted by (bucket, key); what the key could not split is compared with
+its bucket's first member (hmse_order_lcp), and the bucket goes on at the smallest common prefix.  sort_regex =
+sort(nonoverlapping(find_regex(rx))).  Out of scope: descending order (flip a group), numeric, version, locale or key-field (-k)
+comparison, merging several Sorteds or several stores, sorting the store's records themselves, several short ranges packed into one
+wavefront.
 """
 from __future__ import annotations
 
@@ -120,6 +130,20 @@ class Tally:
     total: torch.Tensor          # int64 [G] ranges per group
     value_of: torch.Tensor       # int64 [n] aligned with the input: the index of each occurrence's value, -1 where `top` cut it
     rounds: int = 0              # key / compare rounds the grouping took (1 unless keys collided)
+
+
+@dataclass
+class Sorted:
+    ptr: torch.Tensor            # int64 [G + 1]: group j's positions are [ptr[j] : ptr[j + 1]), texts ascending, equal ones by (start, index)
+    index: torch.Tensor          # int64 the input index at every position (of a Tally: the index of the value)
+    start: torch.Tensor          # int64 the ranges in order
+    end: torch.Tensor            # int64
+    first: torch.Tensor          # bool  this position's text differs from its predecessor's in the group (a group's first position: True)
+    count: torch.Tensor          # int64 the size of the run of equal texts a `first` position opens; with unique=False 1 everywhere
+    distinct: torch.Tensor       # int64 [G] distinct texts per group
+    total: torch.Tensor          # int64 [G] ranges per group
+    rank_of: torch.Tensor        # int64 [n] aligned with the input: every range's position inside its group in the full order, before `unique`
+    rounds: int = 0              # key / LCP rounds the ordering took
 
 
 @dataclass
@@ -197,6 +221,81 @@ def tally_ranges(start, end, group, n_groups: int, keys, same, top=None, max_rou
     index_of = torch.full((n + 1,), -1, dtype=torch.int64, device=dev)
     index_of[reps] = ar(reps.numel())
     return Tally(ptr, start[reps], end[reps], cnt, distinct, total, index_of[value_rep], rounds)
+
+
+ORDER_KEY_BYTES, ORDER_R_MORE = 7, 8          # include/hmse_order.h: text bytes in a key; the r of a text that goes on behind them
+
+
+def order_ranges(start, end, group, n_groups: int, keys, lcp, unique: bool = False, max_rounds: int = 64, _skip: bool = True) -> Sorted:
+    """The rounds of StoreFinder.sort over any tensors' device (tests run it on CPU tensors with plain-Python stand-ins):
+    `keys(start, end, depth)` -> int64 keys and `lcp(start, end, rep, frm)` -> int64 common prefixes are the two ops calls.  Torch
+    plumbing only, no host loop over the ranges.  P holds the ranges in their order so far — first by (group, start, index), and every
+    sort is stable, so equal texts stay that way.  A bucket is a run of positions whose texts agree in their first `depth` bytes; it
+    starts where `opens` is set.  A round keys the positions of the unfinished buckets at their depth and stable-sorts them by (bucket,
+    key) in place; every run of equal keys is a sub-bucket, finished when it has one member or its key says the texts end within it
+    (r <= 7: equal texts).  Every other sub-bucket asks lcp for its members' common prefix with its first member from depth + 7 on and
+    goes on at the smallest of them, where the next keys split or finish it (_skip=False: at depth + 7, without the lcp call; the same
+    result in more rounds).  RuntimeError naming the figures when more than max_rounds would be needed."""
+    n, dev = start.numel(), start.device
+    ar = lambda k: torch.arange(k, dtype=torch.int64, device=dev)
+    P = torch.sort(start, stable=True)[1]                                        # by (group, start, index): two stable sorts
+    P = P[torch.sort(group[P], stable=True)[1]]
+    gP = group[P]
+    opens = torch.ones(n, dtype=torch.bool, device=dev)
+    opens[1:] = gP[1:] != gP[:-1]
+    depth = torch.zeros(n, dtype=torch.int64, device=dev)                        # per position: its bucket's
+    active = torch.ones(n, dtype=torch.bool, device=dev)
+    rounds = 0
+    while True:
+        U = torch.nonzero(active).reshape(-1)
+        m = U.numel()
+        if m == 0:
+            break
+        if rounds >= int(max_rounds):
+            raise RuntimeError(f"sort: {m} of {n} ranges are unresolved after max_rounds = {max_rounds} rounds "
+                               f"(their buckets stand at depths {int(depth[U].min())}..{int(depth[U].max())})")
+        idx, d = P[U], depth[U]
+        bucket = torch.cumsum(opens, 0)[U]                                       # ascends with the positions
+        k = keys(start[idx].contiguous(), end[idx].contiguous(), d.contiguous())
+        o = torch.sort(k, stable=True)[1]                                        # by (bucket, key): two stable sorts; every bucket keeps its positions
+        o = o[torch.sort(bucket[o], stable=True)[1]]
+        idx, k = idx[o], k[o]
+        P[U] = idx
+        new = torch.ones(m, dtype=torch.bool, device=dev)
+        new[1:] = (k[1:] != k[:-1]) | (bucket[1:] != bucket[:-1])
+        opens[U] = new
+        head = torch.nonzero(new).reshape(-1)                                    # every sub-bucket's first member
+        sub = torch.cumsum(new, 0) - 1
+        size = torch.diff(head, append=torch.full((1,), m, dtype=torch.int64, device=dev))
+        done = (size[sub] == 1) | ((k & 15) < ORDER_R_MORE)
+        active[U[done]] = False
+        rest = torch.nonzero(~done).reshape(-1)
+        if rest.numel():
+            if _skip:
+                at = torch.full((m,), -1, dtype=torch.int64, device=dev)
+                at[rest] = ar(rest.numel())
+                rep = at[head[sub[rest]]]                                        # the first member, as an index into the call's ranges
+                ir = idx[rest]
+                c = lcp(start[ir].contiguous(), end[ir].contiguous(), rep.contiguous(), (d[rest] + ORDER_KEY_BYTES).contiguous())
+                least = torch.full((head.numel(),), 1 << 62, dtype=torch.int64, device=dev).scatter_reduce_(0, sub[rest], c, "amin")
+                depth[U[rest]] = least[sub[rest]]                                # (the first member's own answer is its length: never below the others')
+            else:
+                depth[U[rest]] = d[rest] + ORDER_KEY_BYTES
+        rounds += 1
+    total = torch.bincount(group, minlength=n_groups)
+    full_ptr = torch.zeros(n_groups + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(total, 0, out=full_ptr[1:])
+    rank_of = torch.empty(n, dtype=torch.int64, device=dev)
+    rank_of[P] = ar(n) - full_ptr[gP]
+    distinct = torch.bincount(gP[opens], minlength=n_groups)
+    if not unique:
+        return Sorted(full_ptr, P, start[P], end[P], opens, torch.ones(n, dtype=torch.int64, device=dev), distinct, total, rank_of, rounds)
+    head = torch.nonzero(opens).reshape(-1)
+    count = torch.diff(head, append=torch.full((1,), n, dtype=torch.int64, device=dev))
+    ptr = torch.zeros(n_groups + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(distinct, 0, out=ptr[1:])
+    Ph = P[head]
+    return Sorted(ptr, Ph, start[Ph], end[Ph], torch.ones(head.numel(), dtype=torch.bool, device=dev), count, distinct, total, rank_of, rounds)
 
 
 # Something that can be searched for — a group of at most 32 patterns, a PatternSet's long entries, one Regex: its scan and seams calls
@@ -492,9 +591,9 @@ class StoreFinder:
 
     def text(self, lines, max_bytes: int = 1 << 30):
         """The bytes of every extent back to back -> (uint8 tensor, int64 off[L + 1]: extent i is bytes[off[i] : off[i + 1]]).  `lines`:
-        a Lines, a Tally (the representative occurrence of every value) or a (start, end) pair of int64 device tensors (any ranges of
-        the corpus; they may overlap and be empty).  One hmse_lines_gather call.  ValueError naming the total if it exceeds max_bytes."""
-        if isinstance(lines, (Lines, Tally)):                                    # (a Tally: the representative occurrence of every value)
+        a Lines, a Tally (the representative occurrence of every value), a Sorted (the ranges in their order) or a (start, end) pair of
+        int64 device tensors (any ranges of the corpus; they may overlap and be empty).  One hmse_lines_gather call.  ValueError naming the total if it exceeds max_bytes."""
+        if isinstance(lines, (Lines, Tally, Sorted)):                            # (a Tally: the representative occurrence of every value; a Sorted: the ranges in order)
             start, end = lines.start, lines.end
         elif isinstance(lines, (tuple, list)) and len(lines) == 2 and all(isinstance(t, torch.Tensor) for t in lines):
             start, end = (t.reshape(-1) for t in lines)
@@ -567,6 +666,54 @@ class StoreFinder:
         """tally(nonoverlapping(find_regex(rx, max_hits)), ignore_case, top): per regex the values its leftmost-longest matches took,
         most frequent first (grep -o RX | sort | uniq -c | sort -rn).  ignore_case folds the VALUES; how the regex matches is the Regex's own."""
         return self.tally(nonoverlapping(self.find_regex(rx, max_hits)), ignore_case, top)
+
+    # ------------------------------------------------------------------ from ranges to their lexicographic order
+    def sort(self, what, ignore_case: bool = False, unique: bool = False, max_rounds: int = 64, _skip: bool = True) -> Sorted:
+        """Per group the ranges in the order of their texts, as Python orders bytes; equal texts by (start, index) (module docstring;
+        include/hmse_order.h).  `what`: what tally takes — a RegexFound (one group per regex), a Lines, a (start, end) pair of int64
+        device tensors taken as one group, a (start, end, ptr) triple with group j's ranges at [ptr[j] : ptr[j + 1]) — or a Tally: its
+        representatives are ordered and `index` points into the tally's values, so t.count[s.index] is uniq -c in lexicographic order.
+        ignore_case folds A..Z before comparing.  unique=True keeps the first position of every run of equal texts (sort -u), `count`
+        then has the runs' sizes (sort | uniq -c).  One hmse_order_keys and at most one hmse_order_lcp call per round; the rest is torch
+        sorts.  ValueError for a plain Found or ApproxFound (they carry no lengths: use spans() or pass a (start, end) pair), ranges
+        that descend or leave the corpus; RuntimeError when max_rounds rounds do not resolve every range (a chain a, aa, aaa, ...
+        finishes eight ranges a round)."""
+        dev = self.dev
+        if isinstance(what, RegexFound):
+            start, end, ptr = what.offsets, what.offsets + what.lengths, what.ptr
+        elif isinstance(what, (Lines, Tally)):
+            start, end, ptr = what.start, what.end, what.ptr
+        elif isinstance(what, Found):
+            raise ValueError(f"sort: what is a {type(what).__name__}, which has offsets but no lengths; sort takes a RegexFound, a Lines, a Tally, the (start, end) of "
+                             "spans(), or any (start, end) pair of tensors")
+        elif isinstance(what, (tuple, list)) and len(what) in (2, 3) and all(isinstance(t, torch.Tensor) for t in what):
+            start, end = (t.reshape(-1) for t in what[:2])
+            ptr = what[2].reshape(-1) if len(what) == 3 else None
+        else:
+            raise ValueError(f"sort: what is a RegexFound, a Lines, a Tally, a (start, end) pair or a (start, end, ptr) triple of tensors, got a {type(what).__name__}")
+        if any(t.dtype != torch.int64 or t.device != self.raw.device for t in (start, end) + (() if ptr is None else (ptr,))) or start.numel() != end.numel():
+            raise ValueError(f"sort: start, end and ptr are int64 tensors on the finder's device {self.raw.device}, start and end of one length")
+        n = start.numel()
+        if ptr is None:
+            ptr = torch.tensor([0, n], dtype=torch.int64, device=dev)
+        G = ptr.numel() - 1
+        per = ptr[1:] - ptr[:-1]
+        if G < 0 or (G == 0 and n) or (G > 0 and (int(ptr[0]) != 0 or int(ptr[-1]) != n or bool((per < 0).any()))):
+            raise ValueError(f"sort: ptr does not split the {n} ranges into groups (it ascends from 0 to {n})")
+        z = lambda k, dt=torch.int64: torch.zeros(k, dtype=dt, device=dev)
+        if n == 0 or G == 0:
+            return Sorted(z(max(G, 0) + 1), z(0), z(0), z(0), z(0, torch.bool), z(0), z(max(G, 0)), z(max(G, 0)), z(0), 0)
+        if bool(((start < 0) | (end < start) | (end > self.n_bytes)).any()):
+            raise ValueError(f"sort: a range descends or leaves the corpus of n_bytes = {self.n_bytes}")
+        group = torch.repeat_interleave(torch.arange(G, dtype=torch.int64, device=dev), per)
+        keys = lambda s, e, d: ops.order_keys(self.raw, self.raw_off, self.cuts, self.slot, s, e, d, ignore_case)
+        lcp = lambda s, e, rep, frm: ops.order_lcp(self.raw, self.raw_off, self.cuts, self.slot, s, e, rep, frm, ignore_case)
+        return order_ranges(start.contiguous(), end.contiguous(), group, G, keys, lcp, unique, max_rounds, _skip)
+
+    def sort_regex(self, rx, ignore_case: bool = False, unique: bool = False, max_hits: int = 1 << 24) -> Sorted:
+        """sort(nonoverlapping(find_regex(rx, max_hits)), ignore_case, unique): per regex its leftmost-longest matches in the order of
+        their texts (grep -o RX | sort [-u]).  ignore_case folds the VALUES; how the regex matches is the Regex's own."""
+        return self.sort(nonoverlapping(self.find_regex(rx, max_hits)), ignore_case, unique)
 
     # ------------------------------------------------------------------ from ranges to the corpus without them
     def _edits(self, where: str, what, repl, fill: bool):
@@ -920,6 +1067,11 @@ def find_regex(store, rx, device, max_hits: int = 1 << 24, verify: bool = True) 
 def tally_regex(store, rx, device, ignore_case: bool = False, top=None, max_hits: int = 1 << 24, verify: bool = True) -> Tally:
     """One-off form of StoreFinder(store, device, verify).tally_regex(rx, ignore_case, top, max_hits)."""
     return StoreFinder(store, device, verify).tally_regex(rx, ignore_case, top, max_hits)
+
+
+def sort_regex(store, rx, device, ignore_case: bool = False, unique: bool = False, max_hits: int = 1 << 24, verify: bool = True) -> Sorted:
+    """One-off form of StoreFinder(store, device, verify).sort_regex(rx, ignore_case, unique, max_hits)."""
+    return StoreFinder(store, device, verify).sort_regex(rx, ignore_case, unique, max_hits)
 
 
 def substitute_regex(store, rx, repl, device, max_hits: int = 1 << 24, max_bytes: int = 1 << 34, verify: bool = True) -> Substituted:

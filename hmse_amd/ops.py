@@ -82,7 +82,7 @@ def _call(name: str, *args) -> None:
     address (NULL when it is empty and the table says `?`); None is NULL; an int is a raw address.  An IngestConfig, a StreamArrays (whatever holds
     its struct as `.c`) or a mirror struct goes by reference; a host array as it is; a scalar as int().  A non-zero return raises HmseError (an _ex entry point
     under the name of the one it extends)."""
-    params = (_lib.PARSED.get(name) or _lib.PARSED_REGEXA.get(name) or _lib.PARSED_TALLY.get(name) or _lib.PARSED_SUBST[name])[1]
+    params = (_lib.PARSED.get(name) or _lib.PARSED_REGEXA.get(name) or _lib.PARSED_TALLY.get(name) or _lib.PARSED_SUBST.get(name) or _lib.PARSED_ORDER[name])[1]
     if len(args) != len(params) - 1:
         raise TypeError(f"{name} takes {len(params) - 1} arguments and the stream, got {len(args)}")
     out = list(args)
@@ -849,6 +849,39 @@ def tally_same(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slo
           FIND_IGNORE_CASE if ignore_case else 0, same, status)
     _refuse(status, _BAD_TALLY, "hmse_tally_same")
     return same
+
+
+_BAD_ORDER = ((2, -1, "{where} device status {st:#x}: inconsistent tables, a range that descends or leaves the corpus, a depth beyond its text's end, "
+                      "a rep outside the ranges, or a from beyond the shorter of the two texts"),)
+
+
+def order_keys(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, start: torch.Tensor, end: torch.Tensor,
+               depth: torch.Tensor, ignore_case: bool = False) -> torch.Tensor:
+    """hmse_order_keys: seven (folded) corpus bytes of every range from text index depth[i] on and the state of its end, as one integer
+    that sorts like the texts (include/hmse_order.h defines it bit for bit; below 2^60).  The tables are lines_gather's.  -> key int64[n].
+    HmseError for inconsistent tables, a range that descends or leaves the corpus, or a depth[i] above the text's length (status bit 1)."""
+    n = _tally_ranges("order_keys", raw, raw_off, cuts, slot, start, end, depth=depth)
+    key = _buf(n, torch.int64, cuts.device)
+    status = _status_word(cuts.device)
+    _call("hmse_order_keys", raw, raw.numel(), raw_off, raw_off.numel() - 1, cuts, slot, slot.numel(), start, end, depth, n,
+          FIND_IGNORE_CASE if ignore_case else 0, key, status)
+    _refuse(status, _BAD_ORDER, "hmse_order_keys")
+    return key
+
+
+def order_lcp(raw: torch.Tensor, raw_off: torch.Tensor, cuts: torch.Tensor, slot: torch.Tensor, start: torch.Tensor, end: torch.Tensor,
+              rep: torch.Tensor, frm: torch.Tensor, ignore_case: bool = False) -> torch.Tensor:
+    """hmse_order_lcp: lcp[i] = frm[i] + the number of (folded) bytes the ranges i and rep[i] share from text index frm[i] on; the caller
+    promises that the bytes in front of frm[i] agree, and they are not read.  rep[i] == i gives the text's length.  -> int64[n].
+    HmseError for inconsistent tables, a range that descends or leaves the corpus, a rep[i] outside [0, n) or a frm[i] beyond the
+    shorter of the two texts (status bit 1)."""
+    n = _tally_ranges("order_lcp", raw, raw_off, cuts, slot, start, end, rep=rep, **{"from": frm})
+    lcp = _buf(n, torch.int64, cuts.device)
+    status = _status_word(cuts.device)
+    _call("hmse_order_lcp", raw, raw.numel(), raw_off, raw_off.numel() - 1, cuts, slot, slot.numel(), start, end, rep, frm, n,
+          FIND_IGNORE_CASE if ignore_case else 0, lcp, status)
+    _refuse(status, _BAD_ORDER, "hmse_order_lcp")
+    return lcp
 
 
 SUBST_LITERAL, SUBST_FILL = 0, 1

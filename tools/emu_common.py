@@ -1,4 +1,4 @@
-"""What the eleven tools/*_emu.py share: cut the kernels out of a .hip file (everything between two markers) into <name>_kernels.inc, compile
+"""What the thirteen tools/*_emu.py share: cut the kernels out of a .hip file (everything between two markers) into <name>_kernels.inc, compile
 tools/<name>_emu.cpp with it into a stand-alone program (g++ -std=c++20, tools/hip_on_cpu.h under the kernels), run it.  The two regex
 emulators cut nothing: tools/regex_emu.cpp includes hmse_amd/csrc/regex_core.h as it is and is compiled once per form."""
 import argparse

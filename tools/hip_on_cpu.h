@@ -1,4 +1,4 @@
-// hip_on_cpu.h — what the emulators (find_emu, findset_emu, lines_emu, regex_emu in both its forms, approx_emu, export_emu, sync_emu, gunzip_emu, inflate_emu, tally_emu) put under a HIP kernel to run it on the CPU:
+// hip_on_cpu.h — what the emulators (find_emu, findset_emu, lines_emu, regex_emu in both its forms, approx_emu, export_emu, sync_emu, gunzip_emu, inflate_emu, tally_emu, order_emu) put under a HIP kernel to run it on the CPU:
 // one std::thread per lane, a std::barrier under __syncthreads and one per wavefront under __ballot (a loop that is not wave-uniform hangs
 // it), a plain prefix sum for block_exclusive_scan, and the launcher.  Include it after "hmse.h" and in front of hmse_amd/csrc/chunkmap.h,
 // blockops.h and the kernels cut out of a .hip file.
